@@ -144,8 +144,8 @@ class yolov3(object):
 
     def choose_inference_streams(self, inputs, candidates=(1, 2), iters=3, rounds=4):
         """Measure the inference forward of `inputs` with each stream count and keep the fastest in self.inference_streams.
-        Whether two streams overlap depends on how the HIP runtime maps streams to its hardware queues (GPU_MAX_HW_QUEUES, 4
-        by default): with RCCL initialised in the process the same code measured 12.1 ms on two streams against 10.9 on one,
+        Whether two streams overlap depends on how the HIP runtime maps streams to its hardware queues (GPU_MAX_HW_QUEUES; the
+        runtime's default is 4): with RCCL initialised in the process the same code measured 12.1 ms on two streams against 10.9 on one,
         and 10.4 with 2 or 8 hardware queues (profiles/r04_streams_ab.txt) - so a caller that cannot set the variable before
         HIP starts asks the hardware.
         The candidates are timed in alternation (`rounds` times `iters` synchronised forwards each, after one untimed forward
