@@ -457,8 +457,9 @@ int y3_net_train_step(y3_net* net, const y3_train_var* vars, const float* x, int
 /* Optional second stream for backward: a layer's weight gradient is off the critical path of the pass (only the optimizer
  * reads it), its data gradient and the BN backward below it are on it.  With a stream set here (a hipStream_t of the net's
  * device, not the context's; NULL switches it off) the weight gradients run there, ordered against the context's stream by
- * events, and overlap the HBM-bound BN passes of the next layer.  Everything the caller sees keeps its stream order: `ready`
- * for a layer is called once the context's stream has been made to wait for that layer's weight gradient, and backward
+ * events, and overlap the HBM-bound BN passes of the next layer.  Everything the caller sees keeps its stream order:
+ * `ready(g_end)` is called once the context's stream has been made to wait for every weight gradient in flat_grad[0:g_end)
+ * (the calls come in increasing g_end order, whichever variables are trainable), and backward
  * returns with the context's stream waiting for all of them.  The workspace is a little larger (one layer's dz lives one
  * layer longer): size it after this call.  Y3_OWN_STREAM: the library creates (once per net, destroyed with it) a stream of
  * the device's LOWEST priority for it - the recommended form: the weight gradient is the work that can wait, and a stream

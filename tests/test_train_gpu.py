@@ -397,6 +397,31 @@ def _conv_name(i):
     return 'yolov3/%s/%s' % (sub, 'Conv' if j == 0 else 'Conv_%d' % j)
 
 
+# Partial update_vars that split layers (ref: train.py --update_part, variables_to_restore on name prefixes).  Every prefix
+# ends in '/' or a whole variable name ('.../Conv_1' would also take Conv_10 ... Conv_19).  Head conv j is layer 52 + j; the
+# detection convs (bias, no BN) are head 6, 14, 22.
+_DET = (6, 14, 22)
+_head = lambda j: _conv_name(52 + j) + '/'
+SELECTIONS = {
+    # layer 57's kernel on the second stream, layer 56's gamma / beta under an untrainable kernel: the smallest case of a
+    # `ready` edge that covers a weight gradient still pending on the side stream
+    'split_minimal': [_head(5) + 'weights', _head(4) + 'BatchNorm/'],
+    # the same, alternating over the head
+    'bn_all_weights_odd': [_head(j) + 'BatchNorm/' for j in range(23) if j not in _DET] +
+                          [_head(j) + 'weights' for j in range(1, 23, 2)],
+    # dgamma / dbeta into the scratch, the detection biases untrainable
+    'weights_only': [_head(j) + 'weights' for j in range(23)],
+    # nothing on the side stream: every `ready` immediate
+    'no_weights': [_head(j) + 'BatchNorm/' for j in range(23) if j not in _DET] + [_head(j) + 'biases' for j in _DET],
+    # first trainable layer 5: data gradients through ~70 untrainable layers to two isolated trainable ones
+    'deep_sparse': [_conv_name(5) + '/weights', _head(22) + 'biases'],
+}
+
+
+def _selected(y3, prefixes):
+    return [v for v in y3.global_variables(scope='yolov3') if any(v.op_name.startswith(p) for p in prefixes)]
+
+
 @pytest.mark.parametrize('optimizer,update_scopes,dtype', [
     ('sgd', None, 'f32'), ('momentum', None, 'f32'), ('adam', None, 'f32'), ('rmsprop', None, 'f32'),
     ('momentum', ['yolov3/yolov3_head'], 'f32'),
@@ -405,6 +430,22 @@ def _conv_name(i):
     # Winograd forward for the stride-1 3x3 convs (backward unchanged)
     ('sgd', None, 'f32_wino')])
 def test_one_train_step_matches_oracle(optimizer, update_scopes, dtype, isolated_graph):
+    _step_matches_oracle(optimizer, update_scopes, dtype, 'auto', None)
+
+
+@pytest.mark.parametrize('wgrad_stream', [False, True])
+@pytest.mark.parametrize('selection,optimizer,dtype', [
+    ('weights_only', 'sgd', 'f32'), ('bn_all_weights_odd', 'sgd', 'f32'), ('deep_sparse', 'sgd', 'f32'),
+    ('bn_all_weights_odd', 'momentum', 'f32_wino')])
+def test_one_train_step_on_split_layers_matches_oracle(selection, optimizer, dtype, wgrad_stream, isolated_graph):
+    """test_one_train_step_matches_oracle for update_vars that train PART of a layer (SELECTIONS): the kernel without its
+    gamma / beta (dgamma / dbeta go to a scratch), gamma / beta without the kernel, a detection kernel without its biases,
+    and a selection whose first trainable layer is 5 - with the weight gradients on the context's stream and on the second
+    one (set explicitly, not by 'auto').  Same oracle, same tolerances."""
+    _step_matches_oracle(optimizer, SELECTIONS[selection], dtype, wgrad_stream, selection)
+
+
+def _step_matches_oracle(optimizer, update_scopes, dtype, wgrad_stream, label):
     """One whole train step (ref: train.py:105-115) at 256 px, bs=4 (every BN layer reduces over >= 256 samples) against
     the fp64 autograd oracle: loss 5-tuple 1e-4, EVERY clipped gradient tensor within 2e-4 of its max magnitude,
     updated variables and BN moving statistics.
@@ -429,7 +470,7 @@ def test_one_train_step_matches_oracle(optimizer, update_scopes, dtype, isolated
     model.compute_dtype = dtype
     upd = None if update_scopes is None else [v for v in y3.global_variables(scope='yolov3')
                                               if any(v.op_name.startswith(s) for s in update_scopes)]
-    trainer = training.Trainer(model, config_optimizer(optimizer, lr), update_vars=upd)
+    trainer = training.Trainer(model, config_optimizer(optimizer, lr), update_vars=upd, wgrad_stream=wgrad_stream)
     trainer.capture = []
     with y3.variable_scope('yolov3'):
         loss = trainer.step(x, yts)
@@ -456,8 +497,9 @@ def test_one_train_step_matches_oracle(optimizer, update_scopes, dtype, isolated
     GRAD_TOL = 2e-4      # measured: worst 2.0e-5 over all tensors, modes and optimizers (vs 1.1e-1 on the oracle's own branches)
     errs = {name: rel_err(trainer.views[name].cpu().numpy(), g) for name, g in ref['grads'].items()}
     worst = max(errs, key=errs.get)
-    msg = '%s/%s: gradient rel err vs fp64 oracle on the GPU\'s branches: worst %.2e (%s), median %.2e over %d tensors' % (
-        optimizer, dtype, errs[worst], worst, float(np.median(list(errs.values()))), len(errs))
+    msg = '%s%s/%s: gradient rel err vs fp64 oracle on the GPU\'s branches: worst %.2e (%s), median %.2e over %d tensors' % (
+        '' if label is None else '%s wgrad_stream=%s ' % (label, wgrad_stream), optimizer, dtype, errs[worst], worst,
+        float(np.median(list(errs.values()))), len(errs))
     if optimizer == 'sgd' and update_scopes is None:
         own = _REF_CACHE.get(('own', None))
         if own is None:
@@ -487,10 +529,15 @@ def test_one_train_step_matches_oracle(optimizer, update_scopes, dtype, isolated
             solid = g > 1e-2 * g.max()
             assert diff.max() <= 2.2 * lr + 1e-6, v.op_name
             assert diff[solid].max() <= 5e-2 * lr + 1e-4 * scale, v.op_name
+    # every variable outside the selection (the moving statistics aside) is left exactly as it was
+    kept = 0
+    for v in y3.global_variables(scope='yolov3'):
+        if v.op_name in trainer.views or '/moving_' in v.op_name:
+            continue
+        np.testing.assert_array_equal(v.numpy(), params[v.op_name], err_msg=v.op_name)
+        kept += 1
     if update_scopes is not None:
-        body_w = 'yolov3/darknet53_body/Conv_5/weights'
-        np.testing.assert_array_equal(dict((v.op_name, v) for v in y3.global_variables())[body_w].numpy(),
-                                      params[body_w])
+        assert kept > 0
 
 
 def test_train_step_is_deterministic_and_loss_decreases(isolated_graph):
@@ -551,6 +598,130 @@ def test_weight_gradients_on_the_second_stream_change_no_bit(dtype, isolated_gra
         assert torch.equal(other[1], runs[0][1])
         assert other[2] == runs[0][2] and len(other[2]) > 10
     assert runs[1][3] >= runs[0][3]
+
+
+def _record_ready(trainer, edges, also=None):
+    """Replace the `ready` hook the library calls (not GradientExchange.ready itself, which finish() calls once more):
+    every edge goes to `edges`, then to `also(edge)`, then on to the exchange."""
+    from yolov3_tensorflow_amd import _lib
+
+    def hook(user, edge):
+        edges.append(int(edge))
+        if also is not None:
+            also(int(edge))
+        trainer.exchange.ready(int(edge))
+    trainer._cb = _lib.GradReadyFn(hook)
+
+
+@pytest.mark.parametrize('dtype', ['f32', 'f32_wino'])
+@pytest.mark.parametrize('selection', sorted(SELECTIONS))
+def test_partial_update_vars_on_the_second_stream_change_no_bit(selection, dtype, isolated_graph):
+    """The second stream with update_vars that split layers (SELECTIONS).  `ready(e)` tells the gradient exchange that
+    flat[0:e) is complete; gradient_layout puts layer i+1's gradients below layer i's, so the edges must come in strictly
+    increasing order, exactly one per layer with a trainable variable, the last at the end of the buffer - and each only
+    after the main stream has joined every weight gradient below it.  A layer whose kernel does not train but whose gamma /
+    beta (or bias) does is not on the side stream: its edge must not overtake the pending one of the layer above.
+    Losses, gradients and edges must be those of the one-stream pass, and every trainable element is WRITTEN (the last step
+    starts from a buffer full of NaN)."""
+    import yolov3_tensorflow_amd as y3
+    from yolov3_tensorflow_amd import training
+    from yolov3_tensorflow_amd.utils.misc_utils import config_optimizer
+    from oracle import yolo_ref, train_ref
+    params = yolo_ref.synthetic_params(80, seed=4)
+    x = blob_images(7, 3, 128)
+    yts = train_ref.synthetic_targets(8, 3, [128, 128], 80, COCO_ANCHORS, max_boxes=4)
+    runs = []
+    # off from zeros / off from NaN / the library's low-priority stream / a stream of the caller's (both from NaN)
+    for side, fill in ((False, 0.0), (False, float('nan')), (True, float('nan')), (torch.cuda.Stream(), float('nan'))):
+        model = _fresh_model(params, batch_norm_decay=0.99)
+        model.compute_dtype = dtype
+        upd = _selected(y3, SELECTIONS[selection])
+        trainer = training.Trainer(model, config_optimizer('momentum', 1e-3), update_vars=upd, wgrad_stream=side)
+        edges = []
+        with y3.variable_scope('yolov3'):
+            losses = [float(trainer.step(x, yts)[0]) for _ in range(3)]
+            _record_ready(trainer, edges)
+            trainer.flat.fill_(fill)
+            losses.append(float(trainer.step(x, yts)[0]))
+        torch.cuda.synchronize()
+        assert set(trainer.views) == set(v.op_name for v in upd if v.trainable)
+        views = {k: v.clone() for k, v in trainer.views.items()}
+        for k, v in views.items():
+            assert bool(torch.isfinite(v).all()), '%s (wgrad_stream=%s): gradient not written' % (k, side)
+        for v in upd:
+            assert np.isfinite(v.numpy()).all(), v.op_name
+        ends = sorted(trainer.layer_ends.values())
+        assert edges == ends, '%s wgrad_stream=%s: ready edges %s, layer ends %s' % (selection, side, edges, ends)
+        assert all(a < b for a, b in zip(edges, edges[1:])) and edges[-1] == max(trainer.layer_ends.values())
+        runs.append((losses, views, edges))
+    for other in runs[1:]:
+        assert other[0] == runs[0][0]
+        assert other[2] == runs[0][2]
+        for k, v in runs[0][1].items():
+            assert torch.equal(other[1][k], v), k
+
+
+def _sleep_cycles(ms=50.0):
+    """torch.cuda._sleep cycles for about `ms` (at most 200) of stream time, measured once with events."""
+    probe = 1 << 22
+    s = torch.cuda.Stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(s):
+        e0.record()
+        torch.cuda._sleep(probe)
+        e1.record()
+    e1.synchronize()
+    per_cycle = max(e0.elapsed_time(e1), 0.05) / probe
+    return int(min(ms, 200.0) / per_cycle)
+
+
+@pytest.mark.parametrize('selection', ['split_minimal', 'bn_all_weights_odd', None])
+def test_every_ready_edge_follows_the_weight_gradients_it_covers(selection, isolated_graph):
+    """Completeness at `ready` time, made deterministic: the second stream is a caller's stream held back ~50 ms by a sleep
+    enqueued on it before backward (the library's side stream only waits on the main stream, so every weight gradient
+    lands after the sleep).  At each `ready(e)` a copy of flat[prev:e) is enqueued on the current stream - the stream an
+    all-reduce of that bucket would be ordered on.  Any edge issued before the main stream joined the side stream copies
+    stale data (NaN here); after synchronising, every trainable view of the copy must equal the buffer bit for bit."""
+    import yolov3_tensorflow_amd as y3
+    from yolov3_tensorflow_amd import training
+    from yolov3_tensorflow_amd.utils.misc_utils import config_optimizer
+    from oracle import yolo_ref, train_ref
+    params = yolo_ref.synthetic_params(80, seed=4)
+    x = blob_images(7, 3, 128)
+    yts = train_ref.synthetic_targets(8, 3, [128, 128], 80, COCO_ANCHORS, max_boxes=4)
+    cycles = _sleep_cycles()
+    side = torch.cuda.Stream()
+    model = _fresh_model(params, batch_norm_decay=0.99)
+    model.compute_dtype = 'f32'
+    model.wgrad_stream = side                       # the split API reads the model's setting
+    upd = None if selection is None else _selected(y3, SELECTIONS[selection])
+    trainer = training.Trainer(model, config_optimizer('sgd', 1e-3), update_vars=upd, wgrad_stream=side)
+    with y3.variable_scope('yolov3'):
+        fms = model.forward(x, is_training=True)
+        training.compute_loss(model, fms, yts)
+        trainer._alloc_grads(model._train['layer_vars'], fms[0].device)
+        trainer.flat.fill_(float('nan'))
+        snap = torch.full_like(trainer.flat, float('nan'))
+        done = [0]
+
+        def copy_upto(edge):
+            if edge > done[0]:
+                snap[done[0]:edge].copy_(trainer.flat[done[0]:edge])
+                done[0] = edge
+        edges = []
+        _record_ready(trainer, edges, copy_upto)
+        with torch.cuda.stream(side):
+            torch.cuda._sleep(cycles)
+        trainer.backward()
+    torch.cuda.synchronize()
+    assert edges and done[0] == max(trainer.layer_ends.values())
+    stale = []
+    for name, view in trainer.views.items():
+        o = trainer.offsets[name]
+        assert bool(torch.isfinite(view).all()), name
+        if not torch.equal(snap[o:o + view.numel()].view(view.shape), view):
+            stale.append(name)
+    assert not stale, 'ready edges %s issued before these gradients were joined: %s' % (edges, stale)
 
 
 def test_train_workspace_follows_the_dtype_and_a_small_one_is_refused_before_launch(isolated_graph):

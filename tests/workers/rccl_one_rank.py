@@ -37,12 +37,21 @@ def data():
     return blob_images(40, N, SIZE), train_ref.synthetic_targets(50, N, [SIZE, SIZE], 80, COCO_ANCHORS, max_boxes=3)
 
 
-def one_step(group, premul):
-    """Returns (variables after the step, flat gradient buffer, meta)."""
+def one_step(group, premul, split=False):
+    """Returns (variables after the step, flat gradient buffer, meta).  split: update_vars of the selection
+    'bn_all_weights_odd' of tests/test_train_gpu.py with the weight gradients on the second stream (the `ready` edges of
+    layers that train gamma / beta only must not overtake the weight gradients still on that stream)."""
     from yolov3_tensorflow_amd import training
     from yolov3_tensorflow_amd.utils.misc_utils import config_optimizer
     y3, model = setup()
-    trainer = training.Trainer(model, config_optimizer('momentum', LR), process_group=group, bucket_bytes=16 << 20)
+    upd = None
+    if split:
+        from test_train_gpu import SELECTIONS
+        upd = [v for v in y3.global_variables(scope='yolov3')
+               if any(v.op_name.startswith(p) for p in SELECTIONS['bn_all_weights_odd'])]
+        model.wgrad_stream = True           # read by the split API (forward / backward), set before the forward
+    trainer = training.Trainer(model, config_optimizer('momentum', LR), process_group=group, bucket_bytes=16 << 20,
+                               update_vars=upd)
     x, yts = data()
     meta = {}
     with y3.variable_scope('yolov3'):
@@ -62,6 +71,8 @@ def one_step(group, premul):
         meta['works_in_flight'] = len(trainer.exchange._works)
         meta['compute_stream'] = int(torch.cuda.current_stream().cuda_stream)
         trainer.apply_gradients()
+        meta['issued'] = [list(b) for b in trainer.exchange.issued]
+        meta['flat_end'] = max(trainer.layer_ends.values())
     torch.cuda.synchronize()
     return ({v.op_name: v.numpy() for v in y3.global_variables(scope='yolov3')}, trainer.flat.cpu().numpy(), meta)
 
@@ -80,16 +91,16 @@ def main():
         premul = False
         meta['premul_error'] = '%s: %s' % (type(e).__name__, e)
     meta['premul'] = premul
-    for tag, pm in (('sum', False),) + ((('premul', True),) if premul else ()):
+    for tag, pm, split in (('sum', False, False),) + ((('premul', True, False), ('premul_split', True, True)) if premul else ()):
         try:
-            v_g, g_g, m_g = one_step(dist.group.WORLD, pm)
+            v_g, g_g, m_g = one_step(dist.group.WORLD, pm, split)
         except Exception as e:  # noqa: BLE001
             if pm:              # the backend may accept the op object and reject it at launch
                 meta['premul'] = False
                 meta['premul_error'] = '%s: %s' % (type(e).__name__, e)
                 continue
             raise
-        v_l, g_l, m_l = one_step(None, pm)
+        v_l, g_l, m_l = one_step(None, pm, split)
         np.savez(os.path.join(out_dir, '%s_group.npz' % tag), flat=g_g, **v_g)
         np.savez(os.path.join(out_dir, '%s_local.npz' % tag), flat=g_l, **v_l)
         meta[tag] = m_g

@@ -380,6 +380,19 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
         long long g_end = -1;
     };
     std::vector<Deferred> pend;         // oldest first
+    // Every exit joins the side stream, the early error returns included: the caller may free the workspace or flat_grad as
+    // soon as this returns, and a weight gradient still queued behind `pend` reads the one and writes the other.  (On the
+    // normal path the final drain has emptied `pend`; no `ready` calls here.)
+    struct JoinSide {
+        const std::vector<Deferred>& pend;
+        hipStream_t main;
+        bool dry;
+        ~JoinSide() {
+            if (dry) return;
+            for (const Deferred& q : pend)
+                if (q.done) (void)hipStreamWaitEvent(main, q.done, 0);
+        }
+    } join_side{pend, ctx ? ctx->stream : nullptr, dry};     // (the dry run of a size query may have no context)
     int flip = 0;
     auto flush_oldest = [&]() -> int {
         Deferred q = pend.front();
@@ -451,7 +464,8 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
             }
             Buf tmp;
             float *dgam = gptr(v.g_gamma), *dbet = gptr(v.g_beta);
-            if (!dgam || !dbet) tmp = A.alloc((size_t)2 * cout * 4);
+            // (asked of the offsets, not the pointers: the dry run's flat_grad is null, and an offset of 0 must not look untrainable)
+            if (!trainable(v.g_gamma) || !trainable(v.g_beta)) tmp = A.alloc((size_t)2 * cout * 4);
             const float* st = A.p(S.stats[i]);
             if (fused_nb[i] > 0) {
                 Y3_TRY(y3_bn_train_bwd_partials(ctx, A.p(S.z[i]), A.p(dy), v.gamma, st + 2 * cout, st + 3 * cout, st, st + cout, rows,
@@ -492,8 +506,16 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
                 Y3_TRY(y3_conv_wgrad(wctx, &d, xin, dz, dz_stride, gptr(v.g_weights), A.p(S.wgrad_sc), S.wgrad_sc.bytes));
             if (on_side && !dry) Y3_CHECK_HIP(hipEventRecord(S.ev_done[flip], sctx->stream));
         }
-        // this layer's gradients are complete (enqueued) - with two streams: once the main stream waits for the side one (flush)
-        if (!on_side && ready && v.g_end >= 0 && !dry) ready(user, v.g_end);
+        // this layer's gradients are complete (enqueued) - with two streams: once the main stream waits for the side one (flush).
+        // ready(g_end) promises all of flat[0:g_end), which holds the gradients of the layers above this one (gradient_layout):
+        // a layer that is not on the side stream (a trainable gamma / beta / bias under an untrainable kernel) first joins
+        // every weight gradient still pending, so the calls come in increasing g_end order, each behind the waits for all
+        // it covers.  (The dry run drains alike: the releases move with it.)
+        if (!on_side && v.g_end >= 0) {
+            while (!pend.empty())
+                if (int rc = flush_oldest()) return rc;
+            if (ready && !dry) ready(user, v.g_end);
+        }
         const int src = l.src, up = l.up;
         const bool need_src = needs(src), need_up = up >= 0 && needs(up);
         if (need_src || need_up) {

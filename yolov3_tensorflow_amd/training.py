@@ -160,7 +160,7 @@ def _opts(model):
 def _prepare(model, x):
     """Everything a training forward needs before the library call: the train net in the model's mode, the variables (created
     on first use, in the reference's order), their table, the workspace (sized for every variable trainable: an upper bound
-    for any update_vars subset), the options."""
+    for any update_vars subset, checked for layer-splitting ones by tests/test_train_workspace_cpu.py), the options."""
     st = _train_state(model)
     topo = st['topo']
     L = _lib.lib()
