@@ -110,7 +110,7 @@ static const char* kStreamKTimeout =
     "partial sum): the output of that launch is INVALID; y3_ctx_check clears the condition";
 
 // Sticky device-side failure of an earlier launch (no synchronisation: reads the pinned word as it is now).
-static int ctx_pending_error(const y3_ctx* ctx) {
+int ctx_pending_error(const y3_ctx* ctx) {
     if (ctx && ctx->err_host && __atomic_load_n(ctx->err_host, __ATOMIC_RELAXED) != 0u) {
         y3_set_error("%s", kStreamKTimeout);
         return Y3_EHIP;
@@ -357,7 +357,7 @@ extern "C" int y3_net_set_dtype(y3_net* net, int dtype) {
     Y3_CHECK_ARG(dtype >= 0 && dtype <= 4,
                  "y3_net_set_dtype: dtype must be 0 (fp32), 1 (bf16), 2 (fp32 via bf16x6), 3 (fp32 via bf16x3) or "
                  "4 (fp32, Winograd for the eligible 3x3 convs)");
-    net->dtype = dtype;
+    net->dtype = static_cast<NetDtype>(dtype);
     net->pn = net->ph = net->pw = 0;   // re-plan
     return Y3_OK;
 }
@@ -437,42 +437,97 @@ extern "C" size_t y3_net_workspace_bytes(const y3_net* net, int n, int h, int w)
     return net->plan_bytes;
 }
 
-// Layers that exist to move bytes run fused with their only reader (round 5):
-//   bf16 storage: the stem and the stride-2 conv behind it are ONE kernel when nothing else reads the stem's output
-//   (y3_conv_bf16s.hip: the 378 MB tensor between them at 608x608, bs=16 never exists); fp32 (dtypes 0 and 4 - both run these
-//   two layers on the direct kernels -): the same fusion, y3_conv_f32s.hip;
-static bool net_fuses_01(const y3_net* net, int n, int h, int w) {
-    const size_t nl = net->layers.size();
-    const bool f32_direct01 = net->dtype == 0 || net->dtype == 4;
-    if (!((net->dtype == 1 || f32_direct01) && nl >= 2)) return false;
-    const Layer &l0 = net->layers[0], &l1 = net->layers[1];
-    y3_conv_desc d0 = {n, h, w, l0.cin, l0.c_up, l0.cout, l0.k, l0.stride, l0.act};
-    y3_conv_desc d1 = {n, h / net->tensors[l1.src].sdiv, w / net->tensors[l1.src].sdiv, l1.cin, l1.c_up, l1.cout, l1.k,
-                       l1.stride, l1.act};
-    return l0.src == 0 && l1.src == l0.dst && net->tensors[l0.dst].last_use == 1 && net->tensors[l0.dst].ext < 0 &&
-           l0.resid < 0 && l1.resid < 0 && net->tensors[l1.dst].ext < 0 &&
-           (net->dtype == 1 ? y3_conv_bf16_stem_s2_takes(&d0, &d1) : y3_conv_f32_stem_s2_takes(&d0, &d1)) == 1;
+// ---- routes: the only net-level callers of the kernels' eligibility predicates
+// Layers j = 0 / 2 run inside their only reader's launch (round 5): the stem + stride-2 conv (y3_conv_bf16s.hip, fp32 F32 and
+// F32_WINO: y3_conv_f32s.hip), and in bf16 the first residual block (y3_conv_bf16b.hip).
+static bool fuses_with_next(const y3_net& net, int j, int n, int h, int w) {
+    const NetDtype dt = net.dtype;
+    const Layer &a = net.layers[j], &b = net.layers[j + 1];
+    const Tensor &mid = net.tensors[a.dst], &out = net.tensors[b.dst];
+    const y3_conv_desc da = net.desc(j, n, h, w), db = net.desc(j + 1, n, h, w);
+    const bool pair = b.src == a.dst && mid.last_use == j + 1 && mid.ext < 0 && out.ext < 0 && a.resid < 0;
+    if (j == 0)
+        return pair && a.src == 0 && b.resid < 0 &&
+               (dt == NetDtype::BF16 ? y3_conv_bf16_stem_s2_takes(&da, &db)
+                : (dt == NetDtype::F32 || dt == NetDtype::F32_WINO) && y3_conv_f32_stem_s2_takes(&da, &db)) == 1;
+    return j == 2 && dt == NetDtype::BF16 && pair && b.resid == a.src && a.src != 0 && net.tensors[a.src].ext < 0 &&
+           y3_conv_bf16_resblock64_takes(&da, &db) == 1;
 }
-//   ... and, bf16 only, the first residual block (layers 2 and 3: 1x1 64 -> 32, 3x3 32 -> 64 + shortcut) likewise (y3_conv_bf16b.hip).
-static bool net_fuses_23(const y3_net* net, int n, int h, int w) {
-    if (!(net->dtype == 1 && net->layers.size() >= 4)) return false;
-    const Layer &l2 = net->layers[2], &l3 = net->layers[3];
-    const int sd = net->tensors[l2.src].sdiv;
-    y3_conv_desc d2 = {n, h / sd, w / sd, l2.cin, l2.c_up, l2.cout, l2.k, l2.stride, l2.act};
-    y3_conv_desc d3 = {n, h / net->tensors[l3.src].sdiv, w / net->tensors[l3.src].sdiv, l3.cin, l3.c_up, l3.cout, l3.k,
-                       l3.stride, l3.act};
-    return l3.src == l2.dst && l3.resid == l2.src && l2.resid < 0 && l2.src != 0 && net->tensors[l2.dst].last_use == 3 &&
-           net->tensors[l2.dst].ext < 0 && net->tensors[l3.dst].ext < 0 && net->tensors[l2.src].ext < 0 &&
-           y3_conv_bf16_resblock64_takes(&d2, &d3) == 1;
+
+static int split_planes(NetDtype dt) { return dt == NetDtype::F32_BF16X6 ? 3 : dt == NetDtype::F32_BF16X3 ? 2 : 0; }
+
+// conv d on the F(4x4,3x3) kernel, F(2x2,3x3), the split-plane kernel or the direct one, with the scratch that launch needs
+static ConvRoute fp32_route(const y3_conv_desc& d, bool wino44, bool wino, int planes) {
+    ConvRoute r;
+    r.kind = wino44 ? RouteKind::Wino44 : wino ? RouteKind::Wino : planes ? RouteKind::Split : RouteKind::Direct;
+    r.planes = planes;
+    r.two_pass = wino44 && y3_conv_wino44_two_pass_impl(&d);
+    r.streamk = !wino44 && !wino && y3_conv_schedule_impl(&d);      // (a Winograd kernel has no fix-up)
+    r.scratch = wino44 ? (r.two_pass ? y3_conv_wino44_workspace_bytes_impl(&d) : 0)
+                : wino ? y3_conv_wino_workspace_bytes_impl(&d) : y3_conv_workspace_bytes_impl(&d);
+    return r;
+}
+
+ConvRoute y3_route_infer(const y3_net& net, int i, int n, int h, int w) {
+    ConvRoute r;
+    const NetDtype dt = net.dtype;
+    const y3_conv_desc d = net.desc(i, n, h, w);
+    if ((i == 0 || i == 2) && fuses_with_next(net, i, n, h, w)) r.kind = RouteKind::InNext;
+    else if ((i == 1 || i == 3) && fuses_with_next(net, i - 1, n, h, w))
+        r.kind = i == 3 ? RouteKind::ResBlock64Bf16 : dt == NetDtype::BF16 ? RouteKind::StemS2Bf16 : RouteKind::StemS2F32;
+    else if (dt == NetDtype::BF16) r.kind = RouteKind::Bf16;       // (the bf16 kernels use no stream-K scratch)
+    else
+        r = fp32_route(d, dt == NetDtype::F32_WINO && net.layers[i].w_alt && y3_conv_wino44_preferred_impl(&d),
+                       dt == NetDtype::F32_WINO && y3_conv_wino_eligible_impl(&d), split_planes(dt));
+    return r;
+}
+
+ConvRoute y3_route_train_fwd(const y3_net& net, int i, int n, int h, int w) {
+    const Layer& l = net.layers[i];
+    const y3_conv_desc d = net.desc(i, n, h, w, true);
+    const bool wino = net.dtype == NetDtype::F32_WINO && y3_conv_wino_eligible_impl(&d);
+    // F(4x4,3x3) where it fills the chip (y3_conv_wino44_preferred); the Cin = 3 stem reads its HWIO kernel as it is
+    return fp32_route(d, wino && l.bn && y3_conv_wino44_preferred_impl(&d), wino, l.cin == 3 ? 0 : split_planes(net.dtype));
+}
+
+#ifndef Y3_BN_FUSE
+#define Y3_BN_FUSE 1
+#endif
+// The data gradient: a conv over dz [n, ho, wo, dz_stride] (Cout; the detection convs' padded to det_pad), channel axes swapped.
+ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w) {
+    const Layer& l = net.layers[i];
+    const y3_conv_desc d = net.desc(i, n, h, w, true);
+    const y3_conv_desc g = {n, d.h, d.w, l.bn ? l.cout : ((3 * (5 + net.class_num) + 31) / 32) * 32, 0, l.cin, l.k, l.stride, 0};
+    const bool wino = net.dtype == NetDtype::F32_WINO && l.up < 0 && l.k == 3 && l.stride == 1 && y3_conv_wino_eligible_impl(&g);
+    const int planes = (l.cin != 3 && l.stride == 1 && l.cin % 4 == 0 && g.cin % 32 == 0) ? split_planes(net.dtype) : 0;
+    ConvRoute r = fp32_route(g, wino && y3_conv_wino44_preferred_impl(&g), wino, planes);
+    // The BN backward reduction of layer pj (column sums of g' and g' * zhat over its dy and z) rides in the epilogue of the data
+    // gradient that writes that dy last - its first consumer in forward order - where that is a stride-1 1x1 conv on the direct
+    // kernel: the finished dy is in registers there, and the separate pass over z and dy is skipped.
+    const int pj = l.src - 1;
+    bool fuse = Y3_BN_FUSE && r.kind == RouteKind::Direct && l.up < 0 && pj >= 0 && net.layers[pj].bn;
+    for (int j = 0; j < i; ++j)        // (no earlier layer reads l.src)
+        fuse = fuse && net.layers[j].src != l.src && net.layers[j].up != l.src && net.layers[j].resid != l.src;
+    r.bn_blocks = fuse ? y3_conv_dgrad_stats_blocks_impl(&d) : 0;
+    return r;
+}
+
+ConvRoute y3_route_wgrad(const y3_net& net, int i, int n, int h, int w) {
+    ConvRoute r;
+    const y3_conv_desc d = net.desc(i, n, h, w, true);
+    const bool wino = net.dtype == NetDtype::F32_WINO && y3_conv_wgrad_wino_eligible_impl(&d);
+    r.kind = wino ? RouteKind::Wino : RouteKind::Direct;
+    // (the Winograd kernel's scratch is reserved in every dtype: the workspace size the train step has always asked for)
+    r.scratch = std::max(y3_conv_wgrad_wino_scratch_bytes_impl(&d), wino ? 0 : y3_conv_wgrad_scratch_bytes(&d));
+    return r;
 }
 
 // 0: layer i has its own launch; 1: it runs inside the NEXT layer's launch (its output tensor never exists; its profiled time
 // is 0); 2: its launch also runs the layer before it.
 extern "C" int y3_net_layer_fused(const y3_net* net, int i, int n, int h, int w) {
     if (!net || i < 0 || i >= (int)net->layers.size() || n <= 0 || h <= 0 || w <= 0) return 0;
-    if (i <= 1 && net_fuses_01(net, n, h, w)) return i == 0 ? 1 : 2;
-    if ((i == 2 || i == 3) && net_fuses_23(net, n, h, w)) return i == 2 ? 1 : 2;
-    return 0;
+    const RouteKind k = y3_route_infer(*net, i, n, h, w).kind;
+    return k == RouteKind::InNext ? 1 : k >= RouteKind::StemS2F32 ? 2 : 0;      // (the fused kinds come last)
 }
 
 extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, void* workspace,
@@ -517,56 +572,36 @@ extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, 
     // every stream-K layer polls its own pre-zeroed flag region: ONE memset per forward instead of one per launch
     unsigned* flag_base = reinterpret_cast<unsigned*>(base + net->arena_bytes + net->scratch_bytes);
     if (net->flags_bytes) Y3_CHECK_HIP(hipMemsetAsync(flag_base, 0, net->flags_bytes, st));
-    const bool fuse01 = net_fuses_01(net, n, h, w), fuse23 = net_fuses_23(net, n, h, w);
+    void* scratch = base + net->arena_bytes; const size_t sb = net->scratch_bytes;      // (the routes' largest scratch)
     for (size_t i = 0; i < nl; ++i) {
         const Layer& l = net->layers[i];
-        const Tensor& in = net->tensors[l.src];
-        y3_conv_desc d;
-        d.n = n; d.h = h / in.sdiv; d.w = w / in.sdiv;
-        d.cin = l.cin; d.c_up = l.c_up; d.cout = l.cout; d.k = l.k; d.stride = l.stride; d.act = l.act;
+        const ConvRoute& r = net->routes[i];
+        const y3_conv_desc d = net->desc((int)i, n, h, w);
         y3_sk_opts o;
         o.err = net->ctx->err_host;
         o.flags = net->flags_bytes ? flag_base + i * y3_net::FLAG_WORDS : nullptr;
-        if (fuse23 && (i == 2 || i == 3)) {
-            int rc = Y3_OK;
-            if (i == 3) {
-                const Layer& l2 = net->layers[2];
-                const int sd = net->tensors[l2.src].sdiv;
-                rc = y3_launch_conv_bf16_resblock64(st, n, h / sd, w / sd, ptr(l2.src), l2.w, l2.scale, l2.shift, l2.act, l.w,
-                                                    l.scale, l.shift, l.act, ptr(l.dst));
-            }
-            if (rc != Y3_OK) return rc;
-            if (ev) Y3_CHECK_HIP(hipEventRecord(ev[i + 1], st));
-            continue;
+        o.wino44_form = r.two_pass;
+        const Layer& p = net->layers[i ? i - 1 : 0];      // the fused kinds: the layer before, whose launch this is too
+        float *src = ptr(l.src), *up = ptr(l.up), *res = ptr(l.resid), *y = ptr(l.dst);
+        int rc = Y3_OK;
+        switch (r.kind) {
+        case RouteKind::InNext: break;
+        case RouteKind::StemS2F32:
+            rc = y3_launch_conv_f32_stem_s2(st, n, h, w, x, p.w, p.scale, p.shift, p.act, l.w, l.scale, l.shift, l.act, y); break;
+        case RouteKind::StemS2Bf16:
+            rc = y3_launch_conv_bf16_stem_s2(st, n, h, w, x, p.w, p.scale, p.shift, p.act, l.w, l.scale, l.shift, l.act, y); break;
+        case RouteKind::ResBlock64Bf16:
+            rc = y3_launch_conv_bf16_resblock64(st, n, d.h, d.w, ptr(p.src), p.w, p.scale, p.shift, p.act, l.w, l.scale, l.shift,
+                                                l.act, y);
+            break;
+        case RouteKind::Bf16:
+            rc = y3_launch_conv_bf16(st, &d, src, up, l.w, l.scale, l.shift, res, y, net->tensors[l.dst].ext >= 0 ? 1 : 0); break;
+        case RouteKind::Wino44: rc = y3_launch_conv_wino44(st, &d, src, l.w_alt, l.scale, l.shift, res, y, scratch, sb, &o); break;
+        case RouteKind::Wino: rc = y3_launch_conv_wino(st, &d, src, l.w, l.scale, l.shift, res, y, scratch, sb, &o); break;
+        case RouteKind::Split:
+            rc = y3_launch_conv_split(st, &d, r.planes, src, up, l.w, l.scale, l.shift, res, y, scratch, sb, &o); break;
+        case RouteKind::Direct: rc = y3_launch_conv(st, &d, src, up, l.w, l.scale, l.shift, res, y, scratch, sb, &o); break;
         }
-        if (fuse01 && i <= 1) {
-            int rc = Y3_OK;
-            if (i == 1) {
-                const Layer& l0 = net->layers[0];
-                rc = net->dtype == 1
-                    ? y3_launch_conv_bf16_stem_s2(st, n, h, w, x, l0.w, l0.scale, l0.shift, l0.act, l.w, l.scale, l.shift, l.act,
-                                                  ptr(l.dst))
-                    : y3_launch_conv_f32_stem_s2(st, n, h, w, x, l0.w, l0.scale, l0.shift, l0.act, l.w, l.scale, l.shift, l.act,
-                                                 ptr(l.dst));
-            }
-            if (rc != Y3_OK) return rc;
-            if (ev) Y3_CHECK_HIP(hipEventRecord(ev[i + 1], st));
-            continue;
-        }
-        const int rc = net->dtype == 1
-            ? y3_launch_conv_bf16(st, &d, ptr(l.src), ptr(l.up), l.w, l.scale, l.shift, ptr(l.resid), ptr(l.dst),
-                                  net->tensors[l.dst].ext >= 0 ? 1 : 0)
-            : (net->dtype == 4 && l.w_alt && y3_conv_wino44_preferred_impl(&d))
-            ? y3_launch_conv_wino44(st, &d, ptr(l.src), l.w_alt, l.scale, l.shift, ptr(l.resid), ptr(l.dst),
-                                    base + net->arena_bytes, net->scratch_bytes, &o)
-            : (net->dtype == 4 && y3_conv_wino_eligible_impl(&d))
-            ? y3_launch_conv_wino(st, &d, ptr(l.src), l.w, l.scale, l.shift, ptr(l.resid), ptr(l.dst),
-                                  base + net->arena_bytes, net->scratch_bytes, &o)
-            : (net->dtype == 2 || net->dtype == 3)
-            ? y3_launch_conv_split(st, &d, net->dtype == 2 ? 3 : 2, ptr(l.src), ptr(l.up), l.w, l.scale, l.shift,
-                                   ptr(l.resid), ptr(l.dst), base + net->arena_bytes, net->scratch_bytes, &o)
-            : y3_launch_conv(st, &d, ptr(l.src), ptr(l.up), l.w, l.scale, l.shift, ptr(l.resid),
-                             ptr(l.dst), base + net->arena_bytes, net->scratch_bytes, &o);
         if (rc != Y3_OK) return rc;
         if (ev) Y3_CHECK_HIP(hipEventRecord(ev[i + 1], st));
     }
@@ -574,15 +609,8 @@ extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, 
 }
 
 extern "C" int y3_net_layer_is_streamk(const y3_net* net, int i, int n, int h, int w) {
-    if (!net || i < 0 || i >= (int)net->layers.size() || n <= 0 || h <= 0 || w <= 0 || net->dtype == 1) return 0;
-    if (y3_net_layer_fused(net, i, n, h, w)) return 0;      // the fused first layers have no stream-K schedule
-    const Layer& l = net->layers[i];
-    const Tensor& in = net->tensors[l.src];
-    y3_conv_desc d;
-    d.n = n; d.h = h / in.sdiv; d.w = w / in.sdiv;
-    d.cin = l.cin; d.c_up = l.c_up; d.cout = l.cout; d.k = l.k; d.stride = l.stride; d.act = l.act;
-    if (net->dtype == 4 && y3_conv_wino_eligible_impl(&d)) return 0;   // one Winograd kernel, no fix-up
-    return y3_conv_schedule_impl(&d);
+    if (!net || i < 0 || i >= (int)net->layers.size() || n <= 0 || h <= 0 || w <= 0) return 0;
+    return y3_route_infer(*net, i, n, h, w).streamk;
 }
 
 extern "C" int y3_net_set_profiling(y3_net* net, int enabled) {

@@ -397,8 +397,8 @@ int dispatch_bn(hipStream_t stream, const ConvArgs& a) {
 // 1 if y3_launch_conv would pick the stream-K schedule for this conv when given a workspace.
 int y3_conv_schedule_impl(const y3_conv_desc* d) {
     if (!d || d->k != 3 || d->cin == 3 || d->c_up > 0) return 0;
-    ConvArgs a;
-    a.xu = nullptr;
+    ConvArgs a{};        // (value-initialised: use_streamk reads Cin, tmode and ntaps too)
+    a.Cin = d->cin;
     a.Cout = d->cout;
     a.M = d->n * (d->h / d->stride) * (d->w / d->stride);
     return use_streamk(a, d->k, true) ? 1 : 0;

@@ -414,23 +414,12 @@ int forced_rtile() {
 #endif
 constexpr int RS = R_STAGES;       // ring depth of the tiles whose LDS leaves room for more than three stages (probe builds)
 
-// Tile rule, from the per-layer measurements with every tile forced in turn at bs = 16 and bs = 8, 608x608
-// (profiles/r05_bf16_tiles.txt): the largest of 192x128 / 96x128 / 64x64 that still gives ~200 tiles (a tile per CU: the
-// workgroups are resident, one or two per CU by their LDS), Cout <= 64 layers on 128x32 / 128x64.
+constexpr RTile kRTiles[7] = {rtile<1, 1, 4, 1, RS>(), rtile<2, 1, 2, 2, RS>(), rtile<2, 2, 2, 2, 3>(), rtile<3, 2, 2, 2, 3>(),
+                               rtile<3, 1, 1, 4, RS>(), rtile<1, 1, 2, 2, RS>(), rtile<1, 2, 2, 2, RS>()};   // 'a'..'g'
+
 template <bool UPCAT>
-int dispatch_r(hipStream_t stream, const ConvArgsR& a) {
-    constexpr RTile T[7] = {rtile<1, 1, 4, 1, RS>(), rtile<2, 1, 2, 2, RS>(), rtile<2, 2, 2, 2, 3>(), rtile<3, 2, 2, 2, 3>(),
-                            rtile<3, 1, 1, 4, RS>(), rtile<1, 1, 2, 2, RS>(), rtile<1, 2, 2, 2, RS>()};
-    int t = forced_rtile();
-    if (t < 0 || (T[t].bn > 32 && a.Cout <= 32) || (T[t].bn > 64 && a.Cout <= 64)) {
-        auto tiles = [&](int c) { return (long long)((a.M + T[c].bm - 1) / T[c].bm) * ((a.Cout + T[c].bn - 1) / T[c].bn); };
-        if (a.Cout <= 32) t = 0;
-        else if (a.Cout <= 64) t = 1;
-        else if (tiles(3) >= 200) t = 3;
-        else if (tiles(4) >= 200) t = 4;
-        else t = 5;
-    }
-    switch (t) {
+int dispatch_r(hipStream_t stream, const ConvArgsR& a, int tile) {
+    switch (tile) {
     case 0: return launch_r<1, 1, 4, 1, RS, UPCAT>(stream, a);
     case 1: return launch_r<2, 1, 2, 2, RS, UPCAT>(stream, a);
     case 2: return launch_r<2, 2, 2, 2, 3, UPCAT>(stream, a);
@@ -460,15 +449,18 @@ int y3_conv_bf16r_takes(int k, int cin) {
     if (mode >= 0) return mode;
     return cin >= 512 ? 1 : 0;
 }
-// the tile letter dispatch_r picks for this conv (host-only, see y3_conv_bf16_tile)
+// Tile rule, from the per-layer measurements with every tile forced in turn at bs = 16 and bs = 8, 608x608
+// (profiles/r05_bf16_tiles.txt): the largest of 192x128 / 96x128 / 64x64 that still gives ~200 tiles (a tile per CU: the
+// workgroups are resident, one or two per CU by their LDS), Cout <= 64 layers on 128x32 / 128x64.
 int y3_conv_bf16r_tile(const y3_conv_desc* d) {
-    const long long M = (long long)d->n * d->h * d->w;
-    auto tiles = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((d->cout + bn - 1) / bn); };
-    if (d->cout <= 32) return 'a';
-    if (d->cout <= 64) return 'b';
-    if (tiles(192, 128) >= 200) return 'd';
-    if (tiles(96, 128) >= 200) return 'e';
-    return 'f';
+    int t = forced_rtile();
+    if (t < 0 || (kRTiles[t].bn > 32 && d->cout <= 32) || (kRTiles[t].bn > 64 && d->cout <= 64)) {
+        const long long M = (long long)d->n * d->h * d->w;
+        auto tiles = [&](int c) {
+            return ((M + kRTiles[c].bm - 1) / kRTiles[c].bm) * ((d->cout + kRTiles[c].bn - 1) / kRTiles[c].bn); };
+        t = d->cout <= 32 ? 0 : d->cout <= 64 ? 1 : tiles(3) >= 200 ? 3 : tiles(4) >= 200 ? 4 : 5;
+    }
+    return t;
 }
 
 int y3_launch_conv_bf16r(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* x_up, const void* w,
@@ -483,7 +475,7 @@ int y3_launch_conv_bf16r(hipStream_t stream, const y3_conv_desc* d, const void* 
     if (x_up) {
         Y3_CHECK_ARG(d->c_up % 64 == 0 && d->c_up < d->cin && d->h % 2 == 0 && d->w % 2 == 0,
                      "y3_conv2d_fwd_bf16: bad fused upsample+concat configuration (c_up must be a multiple of 64)");
-        return dispatch_r<true>(stream, a);
+        return dispatch_r<true>(stream, a, y3_conv_bf16r_tile(d));
     }
-    return dispatch_r<false>(stream, a);
+    return dispatch_r<false>(stream, a, y3_conv_bf16r_tile(d));
 }

@@ -767,24 +767,32 @@ int choose_tile(long long M, int cout, int S) {
     return best;
 }
 
+// The tile a conv runs on here: A..E = 0..4, or a narrow form (Cin = 32, any Cout: 64-byte rows; Cout <= 32 / 64)
+enum XTile { XA, XB, XC, XD, XE, X_CIN32, X_COUT32, X_COUT64 };
+int bf16x_tile(const y3_conv_desc* d) {
+    if (d->cin % 64 != 0) return X_CIN32;
+    if (d->cout <= 32) return X_COUT32;
+    if (d->cout <= 64) return X_COUT64;
+    const int t = forced_tile();
+    const long long M = (long long)d->n * (d->h / d->stride) * (d->w / d->stride);
+    return (t < 0 || (kTiles[t].bn > 128 && d->cout < 256)) ? choose_tile(M, d->cout, d->k * d->k * (d->cin / 64)) : t;
+}
+
 template <int KS, bool UPCAT>
-int dispatch_x(hipStream_t stream, const ConvArgsX& a) {
-    if (a.Cin % 64 != 0)            // Cin = 32: 64-byte rows (Cout <= 32 too: the rows past Cout read as zeros)
-        return launch_x<128, 64, 4, 1, 32, KS, UPCAT>(stream, a);
-    if (a.Cout <= 32) return launch_x<128, 32, 4, 1, 64, KS, UPCAT>(stream, a);
-    if (a.Cout <= 64) return launch_x<128, 64, 4, 1, 64, KS, UPCAT>(stream, a);
-    int t = forced_tile();
-    if (t < 0 || (kTiles[t].bn > 128 && a.Cout < 256)) t = choose_tile(a.M, a.Cout, KS * KS * (a.Cin / 64));
+int dispatch_x(hipStream_t stream, const ConvArgsX& a, int tile) {
     static int pipe = -1;           // Y3_BF16X_PIPE=0: the two-stage kernel on the 256-row tiles too (A/B runs)
     if (pipe < 0) {
         const char* e = y3_exp_env("Y3_BF16X_PIPE");
         pipe = (e && e[0] == '0') ? 0 : 1;
     }
-    switch (t) {
-    case 0: return pipe ? launch_p<4, 2, 2, 4, KS, UPCAT>(stream, a) : launch_x<256, 256, 2, 4, 64, KS, UPCAT>(stream, a);
-    case 1: return pipe ? launch_p<2, 2, 4, 2, KS, UPCAT>(stream, a) : launch_x<256, 128, 4, 2, 64, KS, UPCAT>(stream, a);
-    case 3: return launch_p<3, 2, 2, 4, KS, UPCAT>(stream, a);
-    case 4: return launch_p<3, 1, 2, 4, KS, UPCAT>(stream, a);
+    switch (tile) {
+    case X_CIN32: return launch_x<128, 64, 4, 1, 32, KS, UPCAT>(stream, a);
+    case X_COUT32: return launch_x<128, 32, 4, 1, 64, KS, UPCAT>(stream, a);
+    case X_COUT64: return launch_x<128, 64, 4, 1, 64, KS, UPCAT>(stream, a);
+    case XA: return pipe ? launch_p<4, 2, 2, 4, KS, UPCAT>(stream, a) : launch_x<256, 256, 2, 4, 64, KS, UPCAT>(stream, a);
+    case XB: return pipe ? launch_p<2, 2, 4, 2, KS, UPCAT>(stream, a) : launch_x<256, 128, 4, 2, 64, KS, UPCAT>(stream, a);
+    case XD: return launch_p<3, 2, 2, 4, KS, UPCAT>(stream, a);
+    case XE: return launch_p<3, 1, 2, 4, KS, UPCAT>(stream, a);
     default: return launch_x<128, 128, 2, 2, 64, KS, UPCAT>(stream, a);
     }
 }
@@ -807,16 +815,15 @@ int y3_conv_bf16x_takes(int k, int cin) {
 
 // Which tile the bf16 path runs this conv on (host-only; tests/test_wino44_tiling_cpu.py holds the configs[4] table against it):
 // 'A'..'E' = the 3x3 tiles above, 'a'..'g' = the ring kernel's tiles, 'x' = the narrow 3x3 forms (Cin = 32 / Cout <= 64), 'o' = the
-// register-staged kernel of y3_conv_bf16.hip, 's' = the Cin = 3 stem
+// register-staged kernel of y3_conv_bf16.hip, 's' = the Cin = 3 stem.  The launches switch on the same two functions.
 extern "C" int y3_conv_bf16_tile(const y3_conv_desc* d) {
     if (!d) return 0;
     if (d->cin == 3) return 's';
     if (y3_conv_bf16x_takes(d->k, d->cin)) {
-        if (d->cin % 64 != 0 || d->cout <= 64) return 'x';
-        const long long M = (long long)d->n * (d->h / d->stride) * (d->w / d->stride);
-        return 'A' + choose_tile(M, d->cout, d->k * d->k * (d->cin / 64));
+        const int t = bf16x_tile(d);
+        return t >= X_CIN32 ? 'x' : 'A' + t;
     }
-    if (y3_conv_bf16r_takes(d->k, d->cin)) return y3_conv_bf16r_tile(d);
+    if (y3_conv_bf16r_takes(d->k, d->cin)) return 'a' + y3_conv_bf16r_tile(d);
     return 'o';
 }
 
@@ -841,5 +848,5 @@ int y3_launch_conv_bf16x(hipStream_t stream, const y3_conv_desc* d, const void* 
     a.N = d->n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Cu = d->c_up; a.Cx = d->cin - d->c_up;
     a.Ho = Ho; a.Wo = Wo; a.Cout = d->cout; a.stride = d->stride; a.pad = d->k / 2; a.act = d->act;
     a.out_f32 = out_f32; a.M = (int)M;
-    return dispatch_x<3, false>(stream, a);      // (the launcher in y3_conv_bf16.hip sends only 3x3 convs here)
+    return dispatch_x<3, false>(stream, a, bf16x_tile(d));      // (the launcher in y3_conv_bf16.hip sends only 3x3 convs here)
 }

@@ -11,7 +11,7 @@
 //
 // TWO forms, one arithmetic (same transforms, same K order, same output tail):
 //
-//   (1) two kernels (round 6; the one y3_net_forward / y3_net_train_* use wherever the caller hands in a workspace):
+//   (1) two kernels (round 6; y3_net_forward / y3_net_train_* plan it by y3_conv_wino44_two_pass_impl and size the V for it):
 //       wino44_input_transform_kernel writes V = B^T d B ONCE per layer, laid out as the byte image of the LDS stages the second
 //       kernel wants - [16-tile block][Cin / 16][2 K-steps][18 position pairs][4 lane quarters][16 tiles][2 positions][2 channels]
 //       = 36 KB per (tile block, 16 channels) - and conv_wino44v_f32_kernel is then 36 batched GEMMs with nothing in its K-loop
@@ -19,8 +19,8 @@
 //       one barrier per 16 channels.  The fp32 forward uses 1.2 of the 8 TB/s of the HBM: the 2.25x larger V (100 MB for a
 //       52-grid 128-channel layer of the bs=32 batch) buys back the issue slots the in-kernel transform took (rounds 4 / 5:
 //       2.4 non-MFMA instructions per 32-cycle MFMA, matrix pipe 44 % busy).
-//   (2) one kernel (rounds 3-5): raw 6x6 patches by LDS-DMA, B^T d B inside the K-loop.  Runs when the caller has no
-//       workspace, and where policy says the extra pass does not pay (y3_conv_wino44_two_pass_impl).
+//   (2) one kernel (rounds 3-5): raw 6x6 patches by LDS-DMA, B^T d B inside the K-loop.  Runs where policy says the extra pass
+//       does not pay (y3_conv_wino44_two_pass_impl), and on a C-ABI call without a workspace that holds V.
 //
 //   * weights U = G g G^T transformed once at load time and packed [18 position pairs][Cin/8][Cout][4 channel pairs][2 positions]
 //     [2 channels] (y3_pack_conv_weights_wino44): a lane's fragments of two neighbouring positions are 16 contiguous bytes;
@@ -858,8 +858,10 @@ int y3_launch_conv_wino44(hipStream_t stream, const y3_conv_desc* d, const float
     a.xb = xb;
     const unsigned grid = (unsigned)(8 * ((nblocks + 7) / 8));
     const size_t vbytes = y3_conv_wino44_workspace_bytes_impl(d);
-    const bool two_pass = workspace != nullptr && workspace_bytes >= vbytes && ((uintptr_t)workspace & 15) == 0 &&
-                          y3_conv_wino44_two_pass_impl(d);
+    const bool fits = workspace != nullptr && workspace_bytes >= vbytes && ((uintptr_t)workspace & 15) == 0;
+    Y3_CHECK_ARG(!sk || sk->wino44_form != 1 || fits, "y3_conv2d_fwd_wino44: the planned two-kernel form has no V scratch "
+                 "(%zu bytes, %zu needed)", workspace_bytes, vbytes);
+    const bool two_pass = sk && sk->wino44_form >= 0 ? sk->wino44_form == 1 : fits && y3_conv_wino44_two_pass_impl(d);
     if (two_pass) {
         a.v = static_cast<float*>(workspace);
         const long long items = (long long)nbt * (d->cin / 16);

@@ -22,6 +22,7 @@ struct y3_ctx {
 int y3_ctx_stage_acquire(y3_ctx* ctx, size_t bytes, void** out);
 // records that an asynchronous copy out of the staging buffer was just enqueued on ctx->stream
 int y3_ctx_stage_release(y3_ctx* ctx);
+int ctx_pending_error(const y3_ctx* ctx);   // Y3_EHIP while an earlier launch's stream-K hand-off has timed out (y3_ctx_check)
 
 // stream-K plumbing handed down to the conv launchers by the ctx entry points / y3_net_forward
 struct y3_sk_opts {
@@ -35,6 +36,8 @@ struct y3_sk_opts {
     // reduction, y3_bn_train_bwd_partials consumes them)
     const float* bwd_z = nullptr;
     const float* bwd_vec = nullptr;
+    // y3_launch_conv_wino44: -1 = two kernels where the workspace holds V (C ABI); 0 / 1 = the route's form (1 needs the V)
+    int wino44_form = -1;
 };
 // rows of the `stats` output of the exact-fp32 conv launchers for this conv (0: not available); wino != 0: the Winograd kernel
 int y3_conv_stats_blocks_impl(const y3_conv_desc* d, int wino);

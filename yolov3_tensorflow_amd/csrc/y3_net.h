@@ -5,6 +5,26 @@
 #include <algorithm>
 #include "y3_internal.h"
 
+// y3_net_set_dtype: exact fp32 MFMA | bf16 storage | fp32 from 3 / 2 bf16 planes (y3_conv_split.hip) | fp32 + Winograd kernels
+enum class NetDtype { F32 = 0, BF16 = 1, F32_BF16X6 = 2, F32_BF16X3 = 3, F32_WINO = 4 };
+
+// How a conv layer runs in one role, decided only by y3_route_* (y3_abi.hip).  InNext: inside the next layer's launch; the last
+// three: this launch also runs the layer before it.
+enum class RouteKind { Direct, Split, Wino, Wino44, Bf16, InNext, StemS2F32, StemS2Bf16, ResBlock64Bf16 };
+struct ConvRoute {
+    RouteKind kind = RouteKind::Direct;
+    int planes = 0;          // Split: 3 or 2
+    bool two_pass = false;   // Wino44: the two-kernel form (V = B^T d B in the scratch)
+    bool streamk = false;    // Direct / Split: y3_conv_schedule_impl
+    size_t scratch = 0;      // bytes of the conv scratch the launch needs (weight gradient: of its own scratch)
+    int bn_blocks = 0;       // data gradient: rows of the fused BN-backward partial sums of the layer below (0: none)
+};
+struct y3_net;
+ConvRoute y3_route_infer(const y3_net& net, int i, int n, int h, int w);
+ConvRoute y3_route_train_fwd(const y3_net& net, int i, int n, int h, int w);
+ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w);
+ConvRoute y3_route_wgrad(const y3_net& net, int i, int n, int h, int w);
+
 struct Tensor {
     int c;        // channels
     int sdiv;     // spatial divisor relative to the input (1,2,4,8,16,32)
@@ -17,7 +37,7 @@ struct Layer {
     int src, up, resid, dst;  // tensor ids (-1 = none)
     int c_up;
     const float *w, *scale, *shift;
-    const float* w_alt = nullptr;   // dtype 4: the F(4x4,3x3) packing of a y3_conv_wino44_candidate layer (y3_net_set_layer_alt)
+    const float* w_alt = nullptr;   // F32_WINO: the F(4x4,3x3) packing of a y3_conv_wino44_candidate layer (y3_net_set_layer_alt)
 };
 
 struct y3_train_state;                       // y3_net_train.hip: what a training forward leaves for loss / backward
@@ -29,9 +49,7 @@ struct y3_net {
     y3_train_state* train = nullptr;
     void* wgrad_stream = nullptr;   // y3_net_train_set_wgrad_stream: the weight gradients of backward run on this stream (nullptr: on the context's)
     void* own_stream = nullptr;     // the low-priority stream y3_net_train_set_wgrad_stream(net, Y3_OWN_STREAM) created (destroyed with the net)
-    int dtype = 0;            // 0: fp32 (exact fp32 MFMA), 1: bf16 storage with fp32 accumulation,
-                              // 2 / 3: fp32 tensors, products rebuilt from 3 / 2 bf16 planes (y3_conv_split.hip)
-                              // 4: fp32, Winograd F(2x2,3x3) kernel for the layers y3_conv_wino_eligible accepts
+    NetDtype dtype = NetDtype::F32;
     std::vector<Tensor> tensors;
     std::vector<Layer> layers;
     // cached plan
@@ -39,8 +57,8 @@ struct y3_net {
     std::vector<size_t> offsets;  // byte offset of each tensor in the workspace (SIZE_MAX if external)
     size_t plan_bytes = 0;    // arena + conv scratch + flag regions
     size_t arena_bytes = 0;   // activations only; the conv (stream-K) scratch follows at this offset
-    size_t scratch_bytes = 0; // stream-K accumulator slots / the V tensor of the two-kernel F(4x4,3x3) form (shared by all
-                              // layers: launches on one stream are ordered)
+    size_t scratch_bytes = 0; // the largest scratch of the routes (shared by all layers: launches on one stream are ordered)
+    std::vector<ConvRoute> routes;   // per layer, y3_route_infer
     size_t flags_bytes = 0;   // one region of FLAG_WORDS "partial published" words per layer, after the scratch:
                               // all regions are zeroed by ONE memset at the start of a forward
     static constexpr size_t FLAG_WORDS = 512;   // >= the largest stream-K grid (512 direct / 256 Winograd workers)
@@ -117,9 +135,16 @@ struct y3_net {
         tensors[fm3].ext = 2;
     }
 
+    // layer i at input n x h x w; train: as the train step runs it (the concat materialised, BN and activation applied apart)
+    y3_conv_desc desc(int i, int n, int h, int w, bool train = false) const {
+        const Layer& l = layers[i];
+        const int sd = tensors[l.src].sdiv;
+        return {n, h / sd, w / sd, l.cin, train ? 0 : l.c_up, l.cout, l.k, l.stride, train ? 0 : l.act};
+    }
+
     size_t tensor_bytes(int id, int n, int h, int w) const {
         const Tensor& t = tensors[id];
-        const size_t esize = (dtype == 1 && t.ext < 0 && id != 0) ? 2 : sizeof(float);
+        const size_t esize = (dtype == NetDtype::BF16 && t.ext < 0 && id != 0) ? 2 : sizeof(float);
         return (size_t)n * (h / t.sdiv) * (w / t.sdiv) * t.c * esize;
     }
 
@@ -180,16 +205,10 @@ struct y3_net {
         }
         arena_bytes = (peak + 255) & ~(size_t)255;
         scratch_bytes = 0;
-        for (const Layer& l : layers) {
-            y3_conv_desc d;
-            d.n = n; d.h = h / tensors[l.src].sdiv; d.w = w / tensors[l.src].sdiv;
-            d.cin = l.cin; d.c_up = l.c_up; d.cout = l.cout; d.k = l.k; d.stride = l.stride; d.act = l.act;
-            if (dtype == 1) break;   // the bf16 kernels use no stream-K scratch
-            scratch_bytes = std::max(scratch_bytes, y3_conv_workspace_bytes_impl(&d));
-            if (dtype == 4) scratch_bytes = std::max(scratch_bytes, y3_conv_wino_workspace_bytes_impl(&d));
-            // V = B^T d B of the two-kernel F(4x4,3x3) form, for the layers that can run on it at this size
-            if (dtype == 4 && l.w_alt && y3_conv_wino44_preferred_impl(&d) && y3_conv_wino44_two_pass_impl(&d))
-                scratch_bytes = std::max(scratch_bytes, y3_conv_wino44_workspace_bytes_impl(&d));
+        routes.clear();
+        for (size_t li = 0; li < layers.size(); ++li) {
+            routes.push_back(y3_route_infer(*this, (int)li, n, h, w));
+            scratch_bytes = std::max(scratch_bytes, routes.back().scratch);
         }
         scratch_bytes = (scratch_bytes + 255) & ~(size_t)255;
         flags_bytes = scratch_bytes ? layers.size() * FLAG_WORDS * sizeof(unsigned) : 0;

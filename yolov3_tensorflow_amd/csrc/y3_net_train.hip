@@ -95,6 +95,8 @@ struct y3_train_state {
     std::vector<Buf> tens;                   // activation of every tensor id (0: the caller's x)
     std::vector<Buf> xin;                    // per layer: the materialised concat input (fused-upsample layers), else empty
     std::vector<Buf> z, stats;               // per BN layer: raw conv output, [4][cout] mean / inv_std / scale / shift
+    struct Routes { ConvRoute fwd, dgrad, wgrad; };
+    std::vector<Routes> routes;              // per layer, at the shape of the last forward (y3_route_*: what is sized is what runs)
     Buf fm_grad[3];                          // d loss / d feature_map_i, [n,g,g,det_pad]
     int fm_tensor[3] = {-1, -1, -1};         // tensor ids of feature maps 1..3 (13-, 26-, 52-grid)
     // the second stream of backward (y3_net_train_set_wgrad_stream): its context and the events that order it against the
@@ -118,17 +120,6 @@ void y3_train_state_free(y3_train_state* s) {
 namespace {
 
 int det_pad_of(int class_num) { return ((3 * (5 + class_num) + 31) / 32) * 32; }
-
-y3_conv_desc desc_of(const y3_net* net, const Layer& l, int n, int h, int w) {
-    y3_conv_desc d;
-    const int sd = net->tensors[l.src].sdiv;
-    d.n = n; d.h = h / sd; d.w = w / sd;
-    d.cin = l.cin; d.c_up = 0; d.cout = l.cout; d.k = l.k; d.stride = l.stride; d.act = 0;
-    return d;
-}
-
-bool wino_layer(const y3_net* net, const y3_conv_desc& d) { return net->dtype == 4 && y3_conv_wino_eligible(&d) == 1; }
-int split_planes(const y3_net* net, const Layer& l) { return l.cin == 3 ? 0 : (net->dtype == 2 ? 3 : net->dtype == 3 ? 2 : 0); }
 
 #define Y3_TRY(expr)                    \
     do {                                \
@@ -159,25 +150,12 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
     S.ones = A.alloc(MAXC * 4);
     S.zeros = A.alloc(MAXC * 4);
     size_t sk = 0, wg = 0;
-    for (const Layer& l : net->layers) {
-        y3_conv_desc d = desc_of(net, l, n, h, w);
-        sk = std::max(sk, y3_conv_workspace_bytes(&d));
-        sk = std::max(sk, y3_conv_wino_workspace_bytes(&d));
-        // the data gradient of a stride-1 3x3 conv runs as a conv with the channel axes swapped
-        y3_conv_desc g = d;
-        g.cin = l.bn ? l.cout : det_pad; g.cout = l.cin;
-        if (l.k == 3 && l.stride == 1) sk = std::max(sk, y3_conv_wino_workspace_bytes(&g));
-        // V of the two-kernel F(4x4,3x3) form, forward and data gradient
-        if (net->dtype == 4 && l.bn && y3_conv_wino44_preferred(&d) == 1 && y3_conv_wino44_two_pass_impl(&d))
-            sk = std::max(sk, y3_conv_wino44_workspace_bytes(&d));
-        if (net->dtype == 4 && l.k == 3 && l.stride == 1 && l.up < 0 && y3_conv_wino44_preferred(&g) == 1 && y3_conv_wino44_two_pass_impl(&g))
-            sk = std::max(sk, y3_conv_wino44_workspace_bytes(&g));
-        wg = std::max(wg, y3_conv_wgrad_scratch_bytes(&d));
-        if (y3_conv_wgrad_wino_eligible(&d)) wg = std::max(wg, y3_conv_wgrad_wino_scratch_bytes(&d));
-    }
-    {
-        y3_conv_desc d128 = {1, 8, 8, 128, 0, 128, 3, 1, 0};      // the library's stream-K scratch for any 3x3 conv, Cout >= 128
-        sk = std::max(sk, y3_conv_workspace_bytes(&d128));
+    S.routes.resize(nl);
+    for (size_t i = 0; i < nl; ++i) {
+        S.routes[i] = {y3_route_train_fwd(*net, (int)i, n, h, w), y3_route_dgrad(*net, (int)i, n, h, w),
+                       y3_route_wgrad(*net, (int)i, n, h, w)};
+        sk = std::max({sk, S.routes[i].fwd.scratch, S.routes[i].dgrad.scratch});
+        wg = std::max(wg, S.routes[i].wgrad.scratch);
     }
     S.sk_ws = A.alloc(std::max<size_t>(sk, 256));
     S.reduce_sc = A.alloc(y3_reduce_scratch_bytes(MAXC));
@@ -205,7 +183,9 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
     for (size_t i = 0; i < nl; ++i) {
         const Layer& l = net->layers[i];
         const y3_train_var& v = vars[i];
-        y3_conv_desc d = desc_of(net, l, n, h, w);
+        const ConvRoute& r = S.routes[i].fwd;
+        const y3_conv_desc d = net->desc((int)i, n, h, w, true);
+        Y3_TRY(ctx_pending_error(ctx));     // (the conv launches below go to the launchers: refuse after a stream-K time-out)
         const long long in_rows = (long long)n * d.h * d.w;
         const float* xin = tptr(l.src);
         if (l.up >= 0) {      // training materialises concat([upsample(up), route]) (model.py:61-62,71-72)
@@ -219,69 +199,59 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
         }
         const int cout = l.cout, ho = d.h / l.stride, wo = d.w / l.stride;
         const long long rows = (long long)n * ho * wo;
-        const bool wino = wino_layer(net, d);
-        // the F(4x4,3x3) kernel where it fills the chip (y3_conv_wino44_preferred: the layers with Cin >= 64 at the bench sizes)
-        const bool wino44 = wino && l.bn && y3_conv_wino44_preferred(&d) == 1;
-        const int planes = split_planes(net, l);
-        const int nblk = (l.bn && !planes) ? y3_conv_stats_blocks(&d, wino44 ? 2 : wino ? 1 : 0) : 0;
+        const int nblk = (l.bn && r.kind != RouteKind::Split)
+            ? y3_conv_stats_blocks(&d, r.kind == RouteKind::Wino44 ? 2 : r.kind == RouteKind::Wino ? 1 : 0) : 0;
         Buf part = nblk ? A.alloc((size_t)nblk * 2 * cout * 4) : Buf();
         // the kernel in this step's packing (the variable changes every step)
         const size_t kelems = (size_t)l.k * l.k * l.cin * cout;
         Buf wp;
-        const void* wdev = v.weights;                       // Cin = 3 stem: HWIO as it is
-        if (wino44) {
-            wp = A.alloc((size_t)36 * l.cin * cout * 4);
-            Y3_TRY(y3_pack_conv_weights_wino44(ctx, v.weights, l.cin, cout, A.p(wp)));
-            wdev = A.p(wp);
-        } else if (wino) {
-            wp = A.alloc((size_t)16 * l.cin * cout * 4);
-            Y3_TRY(y3_pack_conv_weights_wino(ctx, v.weights, l.cin, cout, A.p(wp)));
-            wdev = A.p(wp);
-        } else if (planes) {
-            wp = A.alloc(kelems * 2 * planes);
-            Y3_TRY(y3_pack_conv_weights_split(ctx, v.weights, l.k, l.cin, cout, planes, A.p(wp)));
-            wdev = A.p(wp);
-        } else if (l.cin != 3) {
-            wp = A.alloc(kelems * 4);
-            Y3_TRY(y3_pack_conv_weights(ctx, v.weights, l.k, l.cin, cout, A.p(wp)));
-            wdev = A.p(wp);
+        const float* wdev = v.weights;                      // Cin = 3 stem: HWIO as it is
+        if (l.cin != 3) {
+            wp = A.alloc(r.kind == RouteKind::Wino44 ? (size_t)36 * l.cin * cout * 4 : r.kind == RouteKind::Wino
+                         ? (size_t)16 * l.cin * cout * 4 : kelems * (r.kind == RouteKind::Split ? 2 * r.planes : 4));
+            float* p = A.p(wp);
+            switch (r.kind) {
+            case RouteKind::Wino44: Y3_TRY(y3_pack_conv_weights_wino44(ctx, v.weights, l.cin, cout, p)); break;
+            case RouteKind::Wino: Y3_TRY(y3_pack_conv_weights_wino(ctx, v.weights, l.cin, cout, p)); break;
+            case RouteKind::Split: Y3_TRY(y3_pack_conv_weights_split(ctx, v.weights, l.k, l.cin, cout, r.planes, p)); break;
+            default: Y3_TRY(y3_pack_conv_weights(ctx, v.weights, l.k, l.cin, cout, p));
+            }
+            wdev = p;
         }
         const float* ones = A.p(S.ones);
         const float* zeros = A.p(S.zeros);
+        // BN layers: the raw conv output z (with its column sums where the kernel has them); detection convs: bias, linear
+        // (model.py:55-57)
+        Buf& out = l.bn ? S.z[i] : S.tens[l.dst];
+        out = A.alloc((size_t)rows * cout * 4);
+        float* y = A.p(out);
+        const float* shift = l.bn ? zeros : v.biases;
+        y3_sk_opts so;
+        so.err = dry ? nullptr : ctx->err_host;
+        so.stats = nblk ? A.p(part) : nullptr;
+        so.wino44_form = r.two_pass;
+        hipStream_t s = dry ? nullptr : ctx->stream;
+        switch (r.kind) {
+        case RouteKind::Wino44: Y3_TRY(y3_launch_conv_wino44(s, &d, xin, wdev, ones, shift, nullptr, y, skp, skb, &so)); break;
+        case RouteKind::Wino: Y3_TRY(y3_launch_conv_wino(s, &d, xin, wdev, ones, shift, nullptr, y, skp, skb, &so)); break;
+        case RouteKind::Split:
+            Y3_TRY(y3_launch_conv_split(s, &d, r.planes, xin, nullptr, wdev, ones, shift, nullptr, y, skp, skb, &so)); break;
+        default: Y3_TRY(y3_launch_conv(s, &d, xin, nullptr, wdev, ones, shift, nullptr, y, skp, skb, &so));
+        }
+        A.release(wp);
         if (l.bn) {
-            S.z[i] = A.alloc((size_t)rows * cout * 4);
-            float* z = A.p(S.z[i]);
-            if (wino44)
-                Y3_TRY(y3_conv2d_fwd_wino44_stats(ctx, &d, xin, static_cast<const float*>(wdev), ones, zeros, z, A.p(part), skp, skb));
-            else if (wino)
-                Y3_TRY(y3_conv2d_fwd_wino_stats(ctx, &d, xin, static_cast<const float*>(wdev), ones, zeros, z, A.p(part), skp, skb));
-            else if (planes)
-                Y3_TRY(y3_conv2d_fwd_split(ctx, &d, planes, xin, nullptr, wdev, ones, zeros, nullptr, z, skp, skb));
-            else if (nblk)
-                Y3_TRY(y3_conv2d_fwd_stats(ctx, &d, xin, static_cast<const float*>(wdev), ones, zeros, z, A.p(part), skp, skb));
-            else
-                Y3_TRY(y3_conv2d_fwd(ctx, &d, xin, nullptr, static_cast<const float*>(wdev), ones, zeros, nullptr, z, skp, skb));
-            A.release(wp);
             S.stats[i] = A.alloc((size_t)4 * cout * 4);
             float* st = A.p(S.stats[i]);
             if (nblk)
                 Y3_TRY(y3_bn_train_stats_partials(ctx, A.p(part), nblk, rows, cout, v.gamma, v.beta, BN_EPS, o->bn_decay, st,
                                                   st + cout, st + 2 * cout, st + 3 * cout, v.moving_mean, v.moving_variance));
             else
-                Y3_TRY(y3_bn_train_stats(ctx, z, rows, cout, v.gamma, v.beta, BN_EPS, o->bn_decay, st, st + cout, st + 2 * cout,
+                Y3_TRY(y3_bn_train_stats(ctx, y, rows, cout, v.gamma, v.beta, BN_EPS, o->bn_decay, st, st + cout, st + 2 * cout,
                                          st + 3 * cout, v.moving_mean, v.moving_variance, A.p(S.reduce_sc)));
             A.release(part);
             S.tens[l.dst] = A.alloc((size_t)rows * cout * 4);
-            Y3_TRY(y3_bn_apply_fwd(ctx, z, st + 2 * cout, st + 3 * cout, l.resid >= 0 ? tptr(l.resid) : nullptr, rows, cout, 1,
+            Y3_TRY(y3_bn_apply_fwd(ctx, y, st + 2 * cout, st + 3 * cout, l.resid >= 0 ? tptr(l.resid) : nullptr, rows, cout, 1,
                                    A.p(S.tens[l.dst])));
-        } else {              // detection conv: bias, linear (model.py:55-57)
-            S.tens[l.dst] = A.alloc((size_t)rows * cout * 4);
-            float* y = A.p(S.tens[l.dst]);
-            if (planes)
-                Y3_TRY(y3_conv2d_fwd_split(ctx, &d, planes, xin, nullptr, wdev, ones, v.biases, nullptr, y, skp, skb));
-            else
-                Y3_TRY(y3_conv2d_fwd(ctx, &d, xin, nullptr, static_cast<const float*>(wdev), ones, v.biases, nullptr, y, skp, skb));
-            A.release(wp);
         }
         const int e = net->tensors[l.dst].ext;
         if (e >= 0) S.fm_tensor[e] = l.dst;
@@ -412,22 +382,7 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
         return Y3_OK;
     };
 
-    // The BN backward reduction (column sums of g' and g' * zhat over dy and z) rides in the epilogue of the data gradient
-    // that WRITES that dy, where it can: the gradient of tensor t is complete once its first consumer in forward order - the
-    // last one backward visits - has added its part; if that consumer is a stride-1 1x1 conv on the direct kernel, its data
-    // gradient's epilogue has the finished dy in registers (conv + what the later consumers had left) and reads z beside it.
-    // That is every residual block's output, every yolo-block 3x3 and every stride-2 conv: the large tensors.  The separate
-    // reduction pass (col_reduce<1>: z and dy from memory) is then skipped for that layer.
-#ifndef Y3_BN_FUSE
-#define Y3_BN_FUSE 1
-#endif
-    std::vector<int> first_consumer(nt, -1);
-    for (int li = (int)nl - 1; li >= 0; --li) {
-        const Layer& q = net->layers[li];
-        first_consumer[q.src] = li;
-        if (q.up >= 0) first_consumer[q.up] = li;
-        if (q.resid >= 0) first_consumer[q.resid] = li;
-    }
+    // the BN backward reduction of a layer whose dy the data gradient of its reader writes (y3_route_dgrad: bn_blocks)
     std::vector<Buf> fused_part(nl);
     std::vector<int> fused_nb(nl, 0);
 
@@ -436,7 +391,9 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
         const y3_train_var& v = vars[i];
         const int dst = l.dst;
         if (!have[dst]) continue;
-        y3_conv_desc d = desc_of(net, l, n, h, w);
+        const y3_conv_desc d = net->desc(i, n, h, w, true);
+        const ConvRoute& r = S.routes[i].dgrad;
+        Y3_TRY(ctx_pending_error(ctx));
         const int cout = l.cout, cin = l.cin;
         const float* xin = S.xin[i].ok() ? A.p(S.xin[i]) : tptr(l.src);
         Buf dy = grads[dst];
@@ -500,7 +457,7 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
                 Y3_CHECK_HIP(hipStreamWaitEvent(sctx->stream, S.ev_dz[flip], 0));
             }
             y3_ctx* wctx = on_side ? sctx : ctx;
-            if (net->dtype == 4 && y3_conv_wgrad_wino_eligible(&d) == 1)
+            if (S.routes[i].wgrad.kind == RouteKind::Wino)
                 Y3_TRY(y3_conv_wgrad_wino(wctx, &d, xin, dz, dz_stride, gptr(v.g_weights), A.p(S.wgrad_sc), S.wgrad_sc.bytes));
             else
                 Y3_TRY(y3_conv_wgrad(wctx, &d, xin, dz, dz_stride, gptr(v.g_weights), A.p(S.wgrad_sc), S.wgrad_sc.bytes));
@@ -519,31 +476,33 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
         const int src = l.src, up = l.up;
         const bool need_src = needs(src), need_up = up >= 0 && needs(up);
         if (need_src || need_up) {
-            const int planes = (l.stride == 1 && cin % 4 == 0 && dz_stride % 32 == 0) ? split_planes(net, l) : 0;
-            y3_conv_desc g = d;
-            g.cin = dz_stride; g.cout = cin; g.k = 3; g.stride = 1;
-            const bool wino_d = net->dtype == 4 && up < 0 && l.k == 3 && l.stride == 1 && y3_conv_wino_eligible(&g) == 1;
-            const bool wino44_d = wino_d && y3_conv_wino44_preferred(&g) == 1;
-            Buf wk;
-            if (wino44_d) {
-                wk = A.alloc((size_t)36 * cin * dz_stride * 4);
-                Y3_TRY(y3_pack_conv_weights_wino44_dgrad(ctx, w_d, cin, dz_stride, A.p(wk)));
-            } else if (wino_d) {
-                wk = A.alloc((size_t)16 * cin * dz_stride * 4);
-                Y3_TRY(y3_pack_conv_weights_wino_dgrad(ctx, w_d, cin, dz_stride, A.p(wk)));
-            } else if (planes) {
-                wk = A.alloc((size_t)planes * l.k * l.k * cin * dz_stride * 2);
-                Y3_TRY(y3_pack_conv_weights_split_dgrad(ctx, w_d, l.k, cin, dz_stride, planes, A.p(wk)));
+            Buf wk;                           // the kernel in the data gradient's packing
+            if (r.kind != RouteKind::Direct)
+                wk = A.alloc(r.kind == RouteKind::Wino44 ? (size_t)36 * cin * dz_stride * 4 : r.kind == RouteKind::Wino
+                             ? (size_t)16 * cin * dz_stride * 4 : (size_t)r.planes * l.k * l.k * cin * dz_stride * 2);
+            switch (r.kind) {
+            case RouteKind::Wino44: Y3_TRY(y3_pack_conv_weights_wino44_dgrad(ctx, w_d, cin, dz_stride, A.p(wk))); break;
+            case RouteKind::Wino: Y3_TRY(y3_pack_conv_weights_wino_dgrad(ctx, w_d, cin, dz_stride, A.p(wk))); break;
+            case RouteKind::Split:
+                Y3_TRY(y3_pack_conv_weights_split_dgrad(ctx, w_d, l.k, cin, dz_stride, r.planes, A.p(wk))); break;
+            default: break;                   // (the direct kernel reads w_d)
             }
-            auto dgrad = [&](int accumulate, float* dx) -> int {
-                if (wino44_d)
-                    Y3_TRY(y3_conv2d_dgrad_wino44(ctx, &d, dz, dz_stride, A.p(wk), ones, zeros, accumulate, dx, skp, skb));
-                else if (wino_d)
-                    Y3_TRY(y3_conv2d_dgrad_wino(ctx, &d, dz, dz_stride, A.p(wk), ones, zeros, accumulate, dx, skp, skb));
-                else if (planes)
-                    Y3_TRY(y3_conv2d_dgrad_split(ctx, &d, planes, dz, dz_stride, A.p(wk), ones, zeros, accumulate, dx, skp, skb));
-                else
-                    Y3_TRY(y3_conv2d_dgrad(ctx, &d, dz, dz_stride, w_d, ones, zeros, accumulate, dx, skp, skb));
+            const y3_conv_desc g = {n, d.h, d.w, dz_stride, 0, cin, 3, 1, 0};    // Winograd: a stride-1 3x3 conv, dz_stride -> Cin
+            y3_sk_opts so;
+            so.err = dry ? nullptr : ctx->err_host;
+            so.wino44_form = r.two_pass;
+            hipStream_t s = dry ? nullptr : ctx->stream;
+            auto dgrad = [&](int acc, float* dx) -> int {     // (acc: the Winograd forms read dx as the residual, same thread)
+                switch (r.kind) {
+                case RouteKind::Wino44:
+                    Y3_TRY(y3_launch_conv_wino44(s, &g, dz, A.p(wk), ones, zeros, acc ? dx : nullptr, dx, skp, skb, &so)); break;
+                case RouteKind::Wino:
+                    Y3_TRY(y3_launch_conv_wino(s, &g, dz, A.p(wk), ones, zeros, acc ? dx : nullptr, dx, skp, skb, &so)); break;
+                case RouteKind::Split:
+                    Y3_TRY(y3_launch_conv_dgrad_split(s, &d, r.planes, dz, dz_stride, A.p(wk), ones, zeros, acc, dx, skp, skb, &so));
+                    break;
+                default: Y3_TRY(y3_launch_conv_dgrad(s, &d, dz, dz_stride, w_d, ones, zeros, acc, dx, skp, skb, &so));
+                }
                 return Y3_OK;
             };
             if (up >= 0) {
@@ -563,25 +522,13 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
                 if (!have[src]) { grads[src] = A.alloc(tbytes(src)); own[src] = 1; }
                 // src is the output of layer src - 1: fuse its BN backward reduction where this is the last contribution
                 const int pj = src - 1;
-                const int nbf = (!wino44_d && !wino_d && !planes && pj >= first && pj >= 0 && net->layers[pj].bn &&
-                                 first_consumer[src] == i && S.z[pj].ok())
-                                    ? (Y3_BN_FUSE ? y3_conv_dgrad_stats_blocks_impl(&d) : 0) : 0;
-                if (nbf > 0) {
+                const int nbf = pj >= first ? r.bn_blocks : 0;
+                if (nbf > 0) {                // (a Direct route: the launch takes them through `so`)
                     fused_part[pj] = A.alloc((size_t)nbf * 2 * cin * 4);
                     fused_nb[pj] = nbf;
-                    if (!dry) {
-                        y3_sk_opts o;
-                        o.err = ctx->err_host;
-                        o.stats = A.p(fused_part[pj]);
-                        o.bwd_z = A.p(S.z[pj]);
-                        o.bwd_vec = A.p(S.stats[pj]);
-                        if (int rc = y3_launch_conv_dgrad(ctx->stream, &d, dz, dz_stride, w_d, ones, zeros, have[src] ? 1 : 0,
-                                                          A.p(grads[src]), skp, skb, &o))
-                            return rc;
-                    }
-                } else if (int rc = dgrad(have[src] ? 1 : 0, A.p(grads[src]))) {
-                    return rc;
+                    so.stats = A.p(fused_part[pj]); so.bwd_z = A.p(S.z[pj]); so.bwd_vec = A.p(S.stats[pj]);
                 }
+                if (int rc = dgrad(have[src] ? 1 : 0, A.p(grads[src]))) return rc;
                 have[src] = 1;
             }
             A.release(wk);
@@ -617,7 +564,7 @@ int check_common(const char* who, y3_net* net, int n, int h, int w) {
     Y3_CHECK_ARG(net, "%s: null net", who);
     Y3_CHECK_ARG(n > 0 && h > 0 && w > 0 && h % 32 == 0 && w % 32 == 0,
                  "%s: the batch must be positive and the input size a positive multiple of 32 (got %d x %dx%d)", who, n, h, w);
-    Y3_CHECK_ARG(net->dtype != 1, "%s: the train step is fp32 (net dtype 0, 2, 3 or 4)", who);
+    Y3_CHECK_ARG(net->dtype != NetDtype::BF16, "%s: the train step is fp32 (net dtype 0, 2, 3 or 4)", who);
     return Y3_OK;
 }
 
