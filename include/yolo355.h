@@ -13,8 +13,8 @@
  *   - every call returns 0 on success, a negative Y3_E* code otherwise; the message
  *     is available from y3_last_error() (thread-local);
  *   - the caller owns every device buffer; the library allocates no device memory
- *     and keeps no pointer beyond the call, except the per-layer parameter pointers
- *     registered in a y3_net (which the caller must keep alive);
+ *     and keeps no pointer beyond the call, except the parameter buffer bound to a
+ *     y3_net (which the caller must keep alive);
  *   - activations are NHWC fp32 contiguous; conv kernels in TF layout are HWIO
  *     (utils/misc_utils.py:117-120) and are re-packed once by y3_pack_conv_weights;
  *   - every launch goes to the hipStream_t bound to the context; no call synchronises
@@ -35,10 +35,11 @@ extern "C" {
 #define Y3_EHIP (-2)     /* a HIP runtime call failed */
 #define Y3_ESTATE (-3)   /* object used before it was fully configured */
 
-#define Y3_ABI_VERSION 3
+#define Y3_ABI_VERSION 4
 
 typedef struct y3_ctx y3_ctx; /* one per (device, stream) */
 typedef struct y3_net y3_net; /* the 75-conv YOLOv3 graph bound to caller-owned parameters */
+typedef struct y3_train_var y3_train_var; /* one layer's variables (below, with the train step) */
 
 /* Thread-local message of the last failing call on this thread ("" if none). */
 const char* y3_last_error(void);
@@ -193,7 +194,7 @@ int y3_conv2d_fwd_wino(y3_ctx* ctx, const y3_conv_desc* d, const float* x, const
  * workspace = NULL (or a smaller one) as ONE kernel that transforms inside its K-loop (form 2: rounds 3-5).  Same arithmetic
  * in the same order either way; the workspace needs no initialisation and carries nothing between calls. */
 int y3_conv_wino44_eligible(const y3_conv_desc* d);
-int y3_conv_wino44_candidate(const y3_conv_desc* d);   /* by shape: the convs worth an alternative packing (y3_net_set_layer_alt) */
+int y3_conv_wino44_candidate(const y3_conv_desc* d);   /* by shape: the convs worth an F(4x4,3x3) packing beside the F(2x2) one */
 int y3_conv_wino44_preferred(const y3_conv_desc* d);   /* for THIS n, h, w: a candidate with enough blocks to fill the CUs */
 int y3_pack_conv_weights_wino44(y3_ctx* ctx, const float* w_hwio, int cin, int cout, float* w_wino44);
 size_t y3_conv_wino44_workspace_bytes(const y3_conv_desc* d);   /* bytes of V (two-kernel form); workspace = NULL is allowed */
@@ -278,23 +279,28 @@ int y3_nms(y3_ctx* ctx, int mode, const float* boxes, const float* scores, int n
 /* ---- a5: yolov3.forward (model.py:30-80) as one call -------------------------------------------
  * The graph is fixed by class_num: 52 backbone convs (utils/layer_utils.py:24-68) + 23 head convs
  * (model.py:53-78), indexed 0..74 in variable-creation order (= darknet file order).
- * Per layer the caller registers device pointers: packed weights (HWIO for layer 0), scale, shift. */
+ * The net decides per layer and input size which kernel runs (y3_net_layer_fused, y3_net_layer_is_streamk) and packs the
+ * layers' weights for those kernels itself: the caller hands over the variables, never a packed kernel. */
 int y3_net_create(y3_ctx* ctx, int class_num, y3_net** out);
 int y3_net_destroy(y3_net* net);
-/* 0 = fp32 (default), 1 = bf16 storage: layer parameters must then be bf16-packed (fp32 HWIO for layer 0),
- * intermediate activations are bf16, the three feature maps stay fp32.  2 / 3 = fp32 tensors with the products on
- * the bf16 matrix pipe (y3_conv2d_fwd_split with planes = 3 / 2): layer weights from y3_pack_conv_weights_split.
- * 4 = fp32 with the Winograd kernel for the layers y3_conv_wino_eligible accepts (their weights from
- * y3_pack_conv_weights_wino) and the direct kernel for the rest.  A layer y3_conv_wino44_candidate names may also get
- * its F(4x4,3x3) packing (y3_net_set_layer_alt, weights from y3_pack_conv_weights_wino44): y3_net_forward then runs it on
- * that kernel whenever y3_conv_wino44_preferred says the launch is large enough (bs=32 at 416x416: yes; bs=4: no).  (The
- * train step, y3_net_train_*, packs its own kernels every step and uses F(2x2,3x3) throughout.) */
+/* 0 = fp32 (default); 1 = bf16 storage: intermediate activations are bf16, the three feature maps stay fp32; 2 / 3 = fp32
+ * tensors with the products on the bf16 matrix pipe (y3_conv2d_fwd_split with planes = 3 / 2); 4 = fp32 with the Winograd
+ * kernels for the layers they take: F(4x4,3x3) where y3_conv_wino44_preferred says the launch is large enough (bs=32 at
+ * 416x416: yes; bs=4: no), F(2x2,3x3) where y3_conv_wino_eligible holds, the direct kernel elsewhere.  The train step
+ * (y3_net_train_*) takes its kernels by the same rules for its own launches.  Unbinds the parameters (y3_net_set_params). */
 int y3_net_set_dtype(y3_net* net, int dtype);
 int y3_net_num_layers(const y3_net* net);
 /* geometry of layer i for input-independent fields: k, stride, cin, cout, has_bn */
 int y3_net_layer_info(const y3_net* net, int i, int* k, int* stride, int* cin, int* cout, int* has_bn);
-int y3_net_set_layer(y3_net* net, int i, const float* w_packed, const float* scale, const float* shift);
-int y3_net_set_layer_alt(y3_net* net, int i, const float* w_wino44);   /* optional, dtype 4: see y3_net_set_dtype */
+/* The inference parameters.  y3_net_params_bytes (host only) is the size of the buffer they live in; it depends on class_num
+ * and the dtype, not on the input size.  y3_net_set_params writes into `params` (256-byte aligned), on the context's stream,
+ * every layer's folded batch norm (y3_bn_fold, eps 1e-5; detection convs: scale 1, shift = the bias) and its kernel in every
+ * packing the dtype's kernels may read it in at any input size, and binds the net to the buffer.  vars: one y3_train_var per
+ * layer (only the variable pointers are read, by the work enqueued here; the g_* fields are ignored); a later change of a
+ * variable reaches the net through another call.  vars = NULL: only bind a buffer a net with the same class_num and dtype has filled (nets on several streams
+ * share one).  Changing the dtype unbinds; y3_net_forward without bound parameters is Y3_ESTATE. */
+size_t y3_net_params_bytes(const y3_net* net);
+int y3_net_set_params(y3_net* net, const y3_train_var* vars, void* params, size_t params_bytes);
 size_t y3_net_workspace_bytes(const y3_net* net, int n, int h, int w);
 /* x [n,h,w,3] -> fm1 [n,h/32,w/32,3*(5+C)], fm2 (/16), fm3 (/8).  h,w multiples of 32. */
 int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, void* workspace,
@@ -431,13 +437,13 @@ int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float* y_true, in
  * in layer order (y3_net_layer_info): HWIO kernel, BN gamma / beta / moving mean / moving variance or the bias.
  * workspace: y3_net_train_workspace_bytes(net, vars, n, h, w) bytes (it depends on which variables are trainable),
  * 256-byte aligned, untouched by the caller between forward and backward.  Deterministic (fixed reduction orders). */
-typedef struct y3_train_var {
+struct y3_train_var {
     float* weights;
     float *gamma, *beta, *moving_mean, *moving_variance;   /* BN layers (NULL otherwise) */
     float* biases;                                         /* detection convs (NULL otherwise) */
     long long g_weights, g_gamma, g_beta, g_biases;        /* element offsets into flat_grad; < 0: not trainable */
     long long g_end;                                       /* passed to `ready` once this layer's gradients are enqueued; < 0: no call */
-} y3_train_var;
+};
 typedef struct y3_train_opts {
     float bn_decay;                    /* model.py:36 batch_norm_decay */
     int use_label_smooth, use_focal_loss;

@@ -6,7 +6,7 @@ net dtype at several input shapes.  Host-only calls on a net created without a c
 Some entries depend on the device the library sees (the fused stem / residual block need the device to offer their kernels'
 LDS), so the file holds two tables: 'host' (made without a device) and 'device' (made on an MI355X, --device).
 
-Per (dtype, F(4x4) packings given or not, n, h, w) it records, per layer, y3_net_layer_fused, y3_net_layer_is_streamk and
+Per (dtype, n, h, w) it records, per layer, y3_net_layer_fused, y3_net_layer_is_streamk and
 y3_conv_bf16_tile of the layer's descriptor; y3_net_workspace_bytes; and, for the train dtypes (0, 2, 3, 4),
 y3_net_train_workspace_bytes with every variable trainable, the weight-gradient stream off and on.
 tests/test_conv_route_cpu.py holds the library against the file.  Y3_LIB_PATH selects the library it is made from.
@@ -69,22 +69,18 @@ def descs(L, h, n, H, W):
 
 
 def table():
-    """{key: entry} for every case; key = 'dtype<d>[+alt]/<n>x<h>x<w>'"""
+    """{key: entry} for every case; key = 'dtype<d>/<n>x<h>x<w>' ('dtype4+alt/...' for dtype 4)"""
     from yolov3_tensorflow_amd import _lib, training
     L = _lib.lib()
     h = ctypes.c_void_p()
     _lib.check(L.y3_net_create(None, CLASS_NUM, ctypes.byref(h)))
     all_table, _ = training._var_table(layer_vars())
     nl = L.y3_net_num_layers(h)
-    dummy = ctypes.c_void_p(0x1000)      # a non-null F(4x4) packing: the host plan only asks whether there is one
+    dummy = ctypes.c_void_p(0x1000)      # a weight-gradient stream: the dry run only asks whether there is one
     out = {}
     try:
-        for dtype, alt in ((0, False), (1, False), (2, False), (3, False), (4, False), (4, True)):
+        for dtype in (0, 1, 2, 3, 4):
             _lib.check(L.y3_net_set_dtype(h, dtype))
-            shape_descs = descs(L, h, 1, 96, 96)
-            for i in range(nl):
-                given = alt and L.y3_conv_wino44_candidate(ctypes.byref(shape_descs[i])) == 1
-                _lib.check(L.y3_net_set_layer_alt(h, i, dummy if given else None))
             for n, H, W in SHAPES:
                 ds = descs(L, h, n, H, W)
                 e = {
@@ -100,7 +96,8 @@ def table():
                         ws.append(L.y3_net_train_workspace_bytes(h, all_table, n, H, W))
                     _lib.check(L.y3_net_train_set_wgrad_stream(h, None))
                     e['train_workspace'] = ws
-                out['dtype%d%s/%dx%dx%d' % (dtype, '+alt' if alt else '', n, H, W)] = e
+                # (dtype 4 keeps the '+alt' of the tables made while its F(4x4,3x3) packings were optional: the net now has them)
+                out['dtype%d%s/%dx%dx%d' % (dtype, '+alt' if dtype == 4 else '', n, H, W)] = e
     finally:
         L.y3_net_destroy(h)
     return out

@@ -70,6 +70,21 @@ def test_forward_other_sizes_and_batches(gpu_model, with_dtype, dtype):
             _cmp(g.cpu().numpy(), r, 'forward %dx%dx%d' % (n, h, w))
 
 
+def test_wino_forward_with_a_one_pixel_map_equals_f32(gpu_model, with_dtype):
+    """A 32-pixel side leaves the /32 map one pixel wide: the Winograd kernels refuse its 3x3 convs there, and the direct kernel
+    that takes them must find the kernel in its own packing."""
+    import yolov3_tensorflow_amd as y3
+    model, _ = gpu_model
+    x = np.random.RandomState(32).rand(2, 32, 64, 3).astype(np.float32)
+    fms = {}
+    for dtype in ('f32', 'f32_wino'):
+        with_dtype(dtype)
+        with y3.variable_scope('yolov3'):
+            fms[dtype] = [f.cpu().numpy() for f in model.forward(x, False)]
+    for i, (g, r) in enumerate(zip(fms['f32_wino'], fms['f32'])):
+        _cmp(g, r, 'f32_wino vs f32 feature_map_%d at 32x64' % (i + 1))
+
+
 def test_fused_plan_equals_op_by_op_composition(gpu_model):
     import yolov3_tensorflow_amd as y3
     model, _ = gpu_model

@@ -109,8 +109,8 @@ PROTOTYPES = {
     "y3_net_num_layers": (c_int, [c_void_p]),
     "y3_net_layer_info": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                   POINTER(c_int), POINTER(c_int)]),
-    "y3_net_set_layer": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "y3_net_set_layer_alt": (c_int, [c_void_p, c_int, c_void_p]),
+    "y3_net_params_bytes": (c_size_t, [c_void_p]),
+    "y3_net_set_params": (c_int, [c_void_p, POINTER(TrainVar), c_void_p, c_size_t]),
     "y3_net_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "y3_net_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                c_void_p, c_void_p]),
@@ -184,7 +184,7 @@ def lib():
             fn = getattr(handle, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args
-        if handle.y3_abi_version() != 3:
+        if handle.y3_abi_version() != 4:
             raise Y3Error("libyolo355.so ABI version mismatch")
         _lib = handle
     return _lib

@@ -359,6 +359,10 @@ extern "C" int y3_net_set_dtype(y3_net* net, int dtype) {
                  "4 (fp32, Winograd for the eligible 3x3 convs)");
     net->dtype = static_cast<NetDtype>(dtype);
     net->pn = net->ph = net->pw = 0;   // re-plan
+    for (Layer& l : net->layers) {     // the bound parameters are packed for the old dtype
+        l.scale = l.shift = nullptr;
+        std::fill(std::begin(l.w), std::end(l.w), nullptr);
+    }
     return Y3_OK;
 }
 
@@ -405,22 +409,6 @@ extern "C" int y3_net_tensor_info(const y3_net* net, int t, int* channels, int* 
     if (channels) *channels = net->tensors[t].c;
     if (sdiv) *sdiv = net->tensors[t].sdiv;
     if (ext) *ext = net->tensors[t].ext;
-    return Y3_OK;
-}
-
-extern "C" int y3_net_set_layer(y3_net* net, int i, const float* w_packed, const float* scale,
-                                const float* shift) {
-    Y3_CHECK_ARG(net && i >= 0 && i < (int)net->layers.size(), "y3_net_set_layer: bad layer index %d", i);
-    Y3_CHECK_ARG(w_packed && scale && shift, "y3_net_set_layer: null parameter pointer");
-    Layer& l = net->layers[i];
-    l.w = w_packed; l.scale = scale; l.shift = shift;
-    return Y3_OK;
-}
-
-extern "C" int y3_net_set_layer_alt(y3_net* net, int i, const float* w_wino44) {
-    Y3_CHECK_ARG(net && i >= 0 && i < (int)net->layers.size(), "y3_net_set_layer_alt: bad layer index %d", i);
-    net->layers[i].w_alt = w_wino44;       // NULL: the layer runs on its y3_net_set_layer packing at every size
-    net->pn = net->ph = net->pw = 0;       // re-plan: the layer's V scratch (two-kernel form) is part of the workspace
     return Y3_OK;
 }
 
@@ -477,7 +465,7 @@ ConvRoute y3_route_infer(const y3_net& net, int i, int n, int h, int w) {
         r.kind = i == 3 ? RouteKind::ResBlock64Bf16 : dt == NetDtype::BF16 ? RouteKind::StemS2Bf16 : RouteKind::StemS2F32;
     else if (dt == NetDtype::BF16) r.kind = RouteKind::Bf16;       // (the bf16 kernels use no stream-K scratch)
     else
-        r = fp32_route(d, dt == NetDtype::F32_WINO && net.layers[i].w_alt && y3_conv_wino44_preferred_impl(&d),
+        r = fp32_route(d, dt == NetDtype::F32_WINO && y3_conv_wino44_preferred_impl(&d),
                        dt == NetDtype::F32_WINO && y3_conv_wino_eligible_impl(&d), split_planes(dt));
     return r;
 }
@@ -497,7 +485,7 @@ ConvRoute y3_route_train_fwd(const y3_net& net, int i, int n, int h, int w) {
 ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w) {
     const Layer& l = net.layers[i];
     const y3_conv_desc d = net.desc(i, n, h, w, true);
-    const y3_conv_desc g = {n, d.h, d.w, l.bn ? l.cout : ((3 * (5 + net.class_num) + 31) / 32) * 32, 0, l.cin, l.k, l.stride, 0};
+    const y3_conv_desc g = {n, d.h, d.w, net.dz_stride(i), 0, l.cin, l.k, l.stride, 0};
     const bool wino = net.dtype == NetDtype::F32_WINO && l.up < 0 && l.k == 3 && l.stride == 1 && y3_conv_wino_eligible_impl(&g);
     const int planes = (l.cin != 3 && l.stride == 1 && l.cin % 4 == 0 && g.cin % 32 == 0) ? split_planes(net.dtype) : 0;
     ConvRoute r = fp32_route(g, wino && y3_conv_wino44_preferred_impl(&g), wino, planes);
@@ -522,6 +510,137 @@ ConvRoute y3_route_wgrad(const y3_net& net, int i, int n, int h, int w) {
     return r;
 }
 
+// ---- packings: what a route reads its kernel in, and how that packing is written
+ConvPack y3_conv_pack(const y3_net& net, int i, const ConvRoute& r, bool dgrad) {
+    const Layer& l = net.layers[i];
+    ConvPack p;
+    p.planes = r.planes; p.dgrad = dgrad;
+    p.k = l.k; p.cin = l.cin; p.cout = dgrad ? net.dz_stride(i) : l.cout;
+    switch (r.kind) {
+    case RouteKind::Wino44: p.kind = Packing::Wino44; break;
+    case RouteKind::Wino: p.kind = Packing::Wino; break;
+    case RouteKind::Split: p.kind = Packing::Split; break;
+    case RouteKind::Bf16: case RouteKind::StemS2Bf16: case RouteKind::ResBlock64Bf16: p.kind = Packing::Bf16; break;
+    case RouteKind::InNext: p.kind = net.dtype == NetDtype::BF16 ? Packing::Bf16 : Packing::Direct; break;
+    case RouteKind::Direct: case RouteKind::StemS2F32: p.kind = dgrad ? Packing::Hwio : Packing::Direct; break;
+    }
+    if (l.cin == 3 && !dgrad) p.kind = Packing::Hwio;      // the stem reads its HWIO kernel in every dtype
+    return p;
+}
+
+size_t ConvPack::bytes() const {
+    const size_t taps = (size_t)k * k * cin * cout;
+    switch (kind) {
+    case Packing::Direct: return taps * 4;
+    case Packing::Bf16: return taps * 2;
+    case Packing::Split: return taps * 2 * planes;
+    case Packing::Wino: return (size_t)16 * cin * cout * 4;
+    case Packing::Wino44: return (size_t)36 * cin * cout * 4;
+    default: return 0;
+    }
+}
+
+int ConvPack::launch(y3_ctx* ctx, const float* w, void* out) const {
+    float* o = static_cast<float*>(out);
+    switch (kind) {
+    case Packing::Direct: return y3_pack_conv_weights(ctx, w, k, cin, cout, o);
+    case Packing::Bf16: return y3_pack_conv_weights_bf16(ctx, w, k, cin, cout, out);
+    case Packing::Split:
+        return dgrad ? y3_pack_conv_weights_split_dgrad(ctx, w, k, cin, cout, planes, out)
+                     : y3_pack_conv_weights_split(ctx, w, k, cin, cout, planes, out);
+    case Packing::Wino: return dgrad ? y3_pack_conv_weights_wino_dgrad(ctx, w, cin, cout, o) : y3_pack_conv_weights_wino(ctx, w, cin, cout, o);
+    case Packing::Wino44:
+        return dgrad ? y3_pack_conv_weights_wino44_dgrad(ctx, w, cin, cout, o) : y3_pack_conv_weights_wino44(ctx, w, cin, cout, o);
+    default: return Y3_OK;
+    }
+}
+
+// The parameter buffer of y3_net_set_params: per layer, the folded scale and shift, then the kernel in every packing
+// y3_route_infer may read it in at some legal input size (the stem's HWIO kernel copied), each region 256-byte aligned.
+// A route depends on the size only through the kernels' predicates, and those refuse a map with a 1-pixel side (the /32 map
+// of a 32-pixel input) or take it at every larger size; y3_conv_wino44_preferred is a subset of y3_conv_wino44_candidate,
+// whose packing goes in beside the others.  So the routes at 32 x 32 and 64 x 64, plus that one, cover every size.
+struct LayerParams {
+    size_t scale, shift;
+    std::vector<ConvPack> packs;
+    std::vector<size_t> at;      // offset of packs[j]
+};
+static size_t params_layout(const y3_net& net, std::vector<LayerParams>* out) {
+    Arena A;
+    A.reset(nullptr, 0, true);
+    std::vector<LayerParams> lp(net.layers.size());
+    for (size_t i = 0; i < net.layers.size(); ++i) {
+        const Layer& l = net.layers[i];
+        LayerParams& p = lp[i];
+        p.scale = A.alloc((size_t)l.cout * 4).off;
+        p.shift = A.alloc((size_t)l.cout * 4).off;
+        ConvRoute w44;
+        w44.kind = RouteKind::Wino44;
+        const y3_conv_desc d = net.desc((int)i, 1, 64, 64);
+        std::vector<ConvRoute> rs = {y3_route_infer(net, (int)i, 1, 32, 32), y3_route_infer(net, (int)i, 1, 64, 64)};
+        if (net.dtype == NetDtype::F32_WINO && y3_conv_wino44_candidate_impl(&d)) rs.push_back(w44);
+        for (const ConvRoute& r : rs) {
+            const ConvPack k = y3_conv_pack(net, (int)i, r);
+            if (std::any_of(p.packs.begin(), p.packs.end(), [&](const ConvPack& q) { return q.kind == k.kind; })) continue;
+            p.packs.push_back(k);
+            p.at.push_back(A.alloc(k.kind == Packing::Hwio ? (size_t)l.k * l.k * l.cin * l.cout * 4 : k.bytes()).off);
+        }
+    }
+    if (out) out->swap(lp);
+    return A.top;
+}
+
+extern "C" size_t y3_net_params_bytes(const y3_net* net) { return net ? params_layout(*net, nullptr) : 0; }
+
+extern "C" int y3_net_set_params(y3_net* net, const y3_train_var* vars, void* params, size_t params_bytes) {
+    Y3_CHECK_ARG(net && params, "y3_net_set_params: null argument");
+    std::vector<LayerParams> lp;
+    const size_t need = params_layout(*net, &lp);
+    Y3_CHECK_ARG(params_bytes >= need, "y3_net_set_params: buffer too small (%zu < %zu)", params_bytes, need);
+    Y3_CHECK_ARG(((uintptr_t)params & 255) == 0, "y3_net_set_params: the buffer must be 256-byte aligned");
+    char* base = static_cast<char*>(params);
+    if (vars) {
+        if (!net->ctx) {
+            y3_set_error("y3_net_set_params: the net was created without a context");
+            return Y3_ESTATE;
+        }
+        for (size_t i = 0; i < net->layers.size(); ++i) {
+            const y3_train_var& v = vars[i];
+            Y3_CHECK_ARG(v.weights && (net->layers[i].bn ? v.gamma && v.beta && v.moving_mean && v.moving_variance : v.biases != nullptr),
+                         "y3_net_set_params: layer %zu: a variable is missing", i);
+        }
+        y3_ctx* ctx = net->ctx;
+        for (size_t i = 0; i < net->layers.size(); ++i) {
+            const Layer& l = net->layers[i];
+            const y3_train_var& v = vars[i];
+            float* scale = reinterpret_cast<float*>(base + lp[i].scale);
+            float* shift = reinterpret_cast<float*>(base + lp[i].shift);
+            if (l.bn) {
+                if (int rc = y3_bn_fold(ctx, v.gamma, v.beta, v.moving_mean, v.moving_variance, 1e-5f, l.cout, scale, shift)) return rc;
+            } else {      // detection convs: linear, with a bias (model.py:55-57)
+                Y3_CHECK_HIP(hipMemsetD32Async(scale, 0x3f800000, l.cout, ctx->stream));      // 1.0f
+                Y3_CHECK_HIP(hipMemcpyAsync(shift, v.biases, (size_t)l.cout * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+            for (size_t j = 0; j < lp[i].packs.size(); ++j) {
+                const ConvPack& k = lp[i].packs[j];
+                if (k.kind == Packing::Hwio)
+                    Y3_CHECK_HIP(hipMemcpyAsync(base + lp[i].at[j], v.weights, (size_t)l.k * l.k * l.cin * l.cout * 4,
+                                                hipMemcpyDeviceToDevice, ctx->stream));
+                else if (int rc = k.launch(ctx, v.weights, base + lp[i].at[j]))
+                    return rc;
+            }
+        }
+    }
+    for (size_t i = 0; i < net->layers.size(); ++i) {
+        Layer& l = net->layers[i];
+        l.scale = reinterpret_cast<const float*>(base + lp[i].scale);
+        l.shift = reinterpret_cast<const float*>(base + lp[i].shift);
+        std::fill(std::begin(l.w), std::end(l.w), nullptr);
+        for (size_t j = 0; j < lp[i].packs.size(); ++j) l.w[(int)lp[i].packs[j].kind] = base + lp[i].at[j];
+    }
+    return Y3_OK;
+}
+
 // 0: layer i has its own launch; 1: it runs inside the NEXT layer's launch (its output tensor never exists; its profiled time
 // is 0); 2: its launch also runs the layer before it.
 extern "C" int y3_net_layer_fused(const y3_net* net, int i, int n, int h, int w) {
@@ -543,11 +662,15 @@ extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, 
     Y3_CHECK_ARG(workspace_bytes >= net->plan_bytes, "y3_net_forward: workspace too small (%zu < %zu)",
                  workspace_bytes, net->plan_bytes);
     Y3_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "y3_net_forward: workspace must be 256-byte aligned");
-    for (size_t i = 0; i < net->layers.size(); ++i)
-        if (!net->layers[i].w) {
-            y3_set_error("y3_net_forward: layer %zu has no parameters (call y3_net_set_layer)", i);
+    const size_t nl = net->layers.size();
+    std::vector<const float*> wk(nl);      // each layer's kernel in the packing its route reads
+    for (size_t i = 0; i < nl; ++i) {
+        wk[i] = static_cast<const float*>(net->layers[i].w[(int)y3_conv_pack(*net, (int)i, net->routes[i]).kind]);
+        if (!wk[i] || !net->layers[i].scale) {
+            y3_set_error("y3_net_forward: no parameters bound for this dtype (call y3_net_set_params)");
             return Y3_ESTATE;
         }
+    }
     float* ext[3] = {fm1, fm2, fm3};
     char* base = static_cast<char*>(workspace);
     auto ptr = [&](int id) -> float* {
@@ -558,7 +681,6 @@ extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, 
         return reinterpret_cast<float*>(base + net->offsets[id]);
     };
     hipStream_t st = net->ctx->stream;
-    const size_t nl = net->layers.size();
     hipEvent_t* ev = nullptr;
     if (net->profiling && net->sets_used < 256) {
         if (net->sets_used == net->event_sets.size()) {
@@ -582,25 +704,26 @@ extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, 
         o.flags = net->flags_bytes ? flag_base + i * y3_net::FLAG_WORDS : nullptr;
         o.wino44_form = r.two_pass;
         const Layer& p = net->layers[i ? i - 1 : 0];      // the fused kinds: the layer before, whose launch this is too
+        const float *pw = wk[i ? i - 1 : 0], *lw = wk[i];
         float *src = ptr(l.src), *up = ptr(l.up), *res = ptr(l.resid), *y = ptr(l.dst);
         int rc = Y3_OK;
         switch (r.kind) {
         case RouteKind::InNext: break;
         case RouteKind::StemS2F32:
-            rc = y3_launch_conv_f32_stem_s2(st, n, h, w, x, p.w, p.scale, p.shift, p.act, l.w, l.scale, l.shift, l.act, y); break;
+            rc = y3_launch_conv_f32_stem_s2(st, n, h, w, x, pw, p.scale, p.shift, p.act, lw, l.scale, l.shift, l.act, y); break;
         case RouteKind::StemS2Bf16:
-            rc = y3_launch_conv_bf16_stem_s2(st, n, h, w, x, p.w, p.scale, p.shift, p.act, l.w, l.scale, l.shift, l.act, y); break;
+            rc = y3_launch_conv_bf16_stem_s2(st, n, h, w, x, pw, p.scale, p.shift, p.act, lw, l.scale, l.shift, l.act, y); break;
         case RouteKind::ResBlock64Bf16:
-            rc = y3_launch_conv_bf16_resblock64(st, n, d.h, d.w, ptr(p.src), p.w, p.scale, p.shift, p.act, l.w, l.scale, l.shift,
+            rc = y3_launch_conv_bf16_resblock64(st, n, d.h, d.w, ptr(p.src), pw, p.scale, p.shift, p.act, lw, l.scale, l.shift,
                                                 l.act, y);
             break;
         case RouteKind::Bf16:
-            rc = y3_launch_conv_bf16(st, &d, src, up, l.w, l.scale, l.shift, res, y, net->tensors[l.dst].ext >= 0 ? 1 : 0); break;
-        case RouteKind::Wino44: rc = y3_launch_conv_wino44(st, &d, src, l.w_alt, l.scale, l.shift, res, y, scratch, sb, &o); break;
-        case RouteKind::Wino: rc = y3_launch_conv_wino(st, &d, src, l.w, l.scale, l.shift, res, y, scratch, sb, &o); break;
+            rc = y3_launch_conv_bf16(st, &d, src, up, lw, l.scale, l.shift, res, y, net->tensors[l.dst].ext >= 0 ? 1 : 0); break;
+        case RouteKind::Wino44: rc = y3_launch_conv_wino44(st, &d, src, lw, l.scale, l.shift, res, y, scratch, sb, &o); break;
+        case RouteKind::Wino: rc = y3_launch_conv_wino(st, &d, src, lw, l.scale, l.shift, res, y, scratch, sb, &o); break;
         case RouteKind::Split:
-            rc = y3_launch_conv_split(st, &d, r.planes, src, up, l.w, l.scale, l.shift, res, y, scratch, sb, &o); break;
-        case RouteKind::Direct: rc = y3_launch_conv(st, &d, src, up, l.w, l.scale, l.shift, res, y, scratch, sb, &o); break;
+            rc = y3_launch_conv_split(st, &d, r.planes, src, up, lw, l.scale, l.shift, res, y, scratch, sb, &o); break;
+        case RouteKind::Direct: rc = y3_launch_conv(st, &d, src, up, lw, l.scale, l.shift, res, y, scratch, sb, &o); break;
         }
         if (rc != Y3_OK) return rc;
         if (ev) Y3_CHECK_HIP(hipEventRecord(ev[i + 1], st));

@@ -734,8 +734,8 @@ int y3_conv_wino44_eligible_impl(const y3_conv_desc* d) {
            d->n > 0 && d->h > 1 && d->w > 1;
 }
 
-// The convs y3_net_forward (dtype 4) runs on this kernel instead of the F(2x2,3x3) one, given the alternative packing
-// (y3_net_set_layer_alt): where it measured faster inside the bs=32 416x416 forward (tools/layer_profile.py,
+// The convs y3_net_forward (dtype 4) runs on this kernel instead of the F(2x2,3x3) one (y3_net_set_params packs both for a
+// candidate): where it measured faster inside the bs=32 416x416 forward (tools/layer_profile.py,
 // profiles/r04_wino44.txt; ms per layer, F(2x2) | F(4x4) one-kernel form):
 //   64->128 @104: 0.280 | 0.260     128->256 @52: 0.244 | 0.186     256->512 @26: 0.222 | 0.205     512->1024 @13: 0.240 | 0.198
 //   32->64 @208: 0.361 | 0.372 - four K-steps per block, the block prologue and store tail dominate: stays on F(2x2) at bs=32.

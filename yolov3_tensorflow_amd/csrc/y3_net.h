@@ -25,6 +25,75 @@ ConvRoute y3_route_train_fwd(const y3_net& net, int i, int n, int h, int w);
 ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w);
 ConvRoute y3_route_wgrad(const y3_net& net, int i, int n, int h, int w);
 
+// The layout a launch reads a conv kernel in, implied by its route (y3_conv_pack, y3_abi.hip).  Hwio: the variable as it is
+// (the Cin = 3 stem in every dtype; the direct data gradient, which reads the kernel as [k*k][cin][dz_stride]).
+enum class Packing { Hwio, Direct, Bf16, Split, Wino, Wino44, Count };
+struct ConvPack {
+    Packing kind = Packing::Hwio;
+    int planes = 0;                  // Split: 3 or 2
+    bool dgrad = false;              // the data gradient's packing: the kernel read as [k*k][cin][cout = dz_stride], axes swapped
+    int k = 0, cin = 0, cout = 0;
+    size_t bytes() const;            // of the packing (0 for Hwio: the launch reads the variable)
+    int launch(y3_ctx* ctx, const float* w, void* out) const;   // writes the packing of w (nothing for Hwio)
+};
+ConvPack y3_conv_pack(const y3_net& net, int i, const ConvRoute& r, bool dgrad = false);   // dgrad: r is y3_route_dgrad's
+
+struct Buf {
+    size_t off = SIZE_MAX, bytes = 0;
+    bool ok() const { return off != SIZE_MAX; }
+};
+
+// Best-fit free list over one buffer: a released block merges with its neighbours, and a free block at the top goes back to
+// the bump pointer.  dry: hand out offsets, touch nothing (sizing).
+struct Arena {
+    char* base = nullptr;
+    size_t cap = 0, top = 0, peak = 0;
+    bool dry = false;
+    bool overflow = false;
+    struct Free { size_t off, size; };
+    std::vector<Free> fl;
+    static size_t round(size_t b) { return (b + 255) & ~(size_t)255; }
+    void reset(void* ws, size_t bytes, bool dry_) { base = static_cast<char*>(ws); cap = bytes; top = peak = 0; dry = dry_; overflow = false; fl.clear(); }
+    void rewind(size_t to) { top = to; fl.clear(); }
+    Buf alloc(size_t bytes) {
+        bytes = round(bytes ? bytes : 1);
+        size_t best = SIZE_MAX, best_size = SIZE_MAX;
+        for (size_t f = 0; f < fl.size(); ++f)
+            if (fl[f].size >= bytes && fl[f].size < best_size) { best = f; best_size = fl[f].size; }
+        Buf b;
+        b.bytes = bytes;
+        if (best != SIZE_MAX) {
+            b.off = fl[best].off;
+            fl[best].off += bytes;
+            fl[best].size -= bytes;
+            if (fl[best].size == 0) fl.erase(fl.begin() + best);
+        } else {
+            b.off = top;
+            top += bytes;
+            peak = std::max(peak, top);
+            if (!dry && top > cap) overflow = true;
+        }
+        return b;
+    }
+    void release(Buf& b) {
+        if (!b.ok()) return;
+        fl.push_back({b.off, b.bytes});
+        std::sort(fl.begin(), fl.end(), [](const Free& x, const Free& y) { return x.off < y.off; });
+        std::vector<Free> merged;
+        for (const Free& f : fl) {
+            if (!merged.empty() && merged.back().off + merged.back().size == f.off) merged.back().size += f.size;
+            else merged.push_back(f);
+        }
+        if (!merged.empty() && merged.back().off + merged.back().size == top) {
+            top = merged.back().off;
+            merged.pop_back();
+        }
+        fl.swap(merged);
+        b = Buf();
+    }
+    float* p(const Buf& b) const { return b.ok() ? reinterpret_cast<float*>(base + b.off) : nullptr; }
+};
+
 struct Tensor {
     int c;        // channels
     int sdiv;     // spatial divisor relative to the input (1,2,4,8,16,32)
@@ -36,8 +105,8 @@ struct Layer {
     int k, stride, cin, cout, bn, act;
     int src, up, resid, dst;  // tensor ids (-1 = none)
     int c_up;
-    const float *w, *scale, *shift;
-    const float* w_alt = nullptr;   // F32_WINO: the F(4x4,3x3) packing of a y3_conv_wino44_candidate layer (y3_net_set_layer_alt)
+    const float *scale, *shift;     // folded BN (detection convs: ones, bias), bound by y3_net_set_params
+    const void* w[(int)Packing::Count];     // the kernel in every packing the inference routes may read (y3_net_set_params)
 };
 
 struct y3_train_state;                       // y3_net_train.hip: what a training forward leaves for loss / backward
@@ -74,7 +143,8 @@ struct y3_net {
         l.src = src; l.up = up; l.resid = resid;
         l.c_up = up >= 0 ? tensors[up].c : 0;
         l.cin = tensors[src].c + l.c_up;
-        l.w = l.scale = l.shift = nullptr;
+        l.scale = l.shift = nullptr;
+        std::fill(std::begin(l.w), std::end(l.w), nullptr);
         Tensor t;
         t.c = cout; t.sdiv = tensors[src].sdiv * stride; t.last_use = -1; t.ext = -1;
         tensors.push_back(t);
@@ -142,6 +212,9 @@ struct y3_net {
         return {n, h / sd, w / sd, l.cin, train ? 0 : l.c_up, l.cout, l.k, l.stride, train ? 0 : l.act};
     }
 
+    // the channel stride of layer i's output gradient in the train step: Cout, the detection convs' padded to a multiple of 32
+    int dz_stride(int i) const { return layers[i].bn ? layers[i].cout : ((3 * (5 + class_num) + 31) / 32) * 32; }
+
     size_t tensor_bytes(int id, int n, int h, int w) const {
         const Tensor& t = tensors[id];
         const size_t esize = (dtype == NetDtype::BF16 && t.ext < 0 && id != 0) ? 2 : sizeof(float);
@@ -153,57 +226,19 @@ struct y3_net {
     // for the deeper layers.
     void plan(int n, int h, int w) {
         if (n == pn && h == ph && w == pw) return;
-        struct Free { size_t off, size; };
-        std::vector<Free> freelist;
-        std::vector<char> live(tensors.size(), 0);
-        size_t top = 0, peak = 0;
+        Arena A;
+        A.reset(nullptr, 0, true);
+        std::vector<Buf> live(tensors.size());
         offsets.assign(tensors.size(), SIZE_MAX);
-        auto rounded = [&](int id) { return (tensor_bytes(id, n, h, w) + 255) & ~(size_t)255; };
-        auto release = [&](size_t off, size_t size) {
-            freelist.push_back({off, size});
-            std::sort(freelist.begin(), freelist.end(),
-                      [](const Free& a, const Free& b) { return a.off < b.off; });
-            std::vector<Free> merged;
-            for (const Free& f : freelist) {
-                if (!merged.empty() && merged.back().off + merged.back().size == f.off)
-                    merged.back().size += f.size;
-                else
-                    merged.push_back(f);
-            }
-            if (!merged.empty() && merged.back().off + merged.back().size == top) {
-                top = merged.back().off;  // give the tail back to the bump pointer
-                merged.pop_back();
-            }
-            freelist.swap(merged);
-        };
         for (size_t li = 0; li < layers.size(); ++li) {
             const Layer& l = layers[li];
             for (size_t t = 1; t < tensors.size(); ++t)
-                if (live[t] && tensors[t].last_use < (int)li) {
-                    release(offsets[t], rounded((int)t));
-                    live[t] = 0;
-                }
+                if (live[t].ok() && tensors[t].last_use < (int)li) A.release(live[t]);
             if (tensors[l.dst].ext >= 0) continue;
-            const size_t need = rounded(l.dst);
-            size_t best = SIZE_MAX, best_size = SIZE_MAX;
-            for (size_t f = 0; f < freelist.size(); ++f)
-                if (freelist[f].size >= need && freelist[f].size < best_size) {
-                    best = f;
-                    best_size = freelist[f].size;
-                }
-            if (best != SIZE_MAX) {
-                offsets[l.dst] = freelist[best].off;
-                freelist[best].off += need;
-                freelist[best].size -= need;
-                if (freelist[best].size == 0) freelist.erase(freelist.begin() + best);
-            } else {
-                offsets[l.dst] = top;
-                top += need;
-            }
-            live[l.dst] = 1;
-            peak = std::max(peak, top);
+            live[l.dst] = A.alloc(tensor_bytes(l.dst, n, h, w));
+            offsets[l.dst] = live[l.dst].off;
         }
-        arena_bytes = (peak + 255) & ~(size_t)255;
+        arena_bytes = Arena::round(A.peak);
         scratch_bytes = 0;
         routes.clear();
         for (size_t li = 0; li < layers.size(); ++li) {

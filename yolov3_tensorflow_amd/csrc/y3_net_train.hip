@@ -20,60 +20,6 @@ namespace {
 constexpr float BN_EPS = 1e-5f;      // model.py:37
 constexpr int MAXC = 1024;           // widest channel count of the graph (ones / zeros vectors, per-channel scratch)
 
-struct Buf {
-    size_t off = SIZE_MAX, bytes = 0;
-    bool ok() const { return off != SIZE_MAX; }
-};
-
-struct Arena {
-    char* base = nullptr;
-    size_t cap = 0, top = 0, peak = 0;
-    bool dry = false;                 // size query: hand out offsets, touch nothing
-    bool overflow = false;
-    struct Free { size_t off, size; };
-    std::vector<Free> fl;
-    static size_t round(size_t b) { return (b + 255) & ~(size_t)255; }
-    void reset(void* ws, size_t bytes, bool dry_) { base = static_cast<char*>(ws); cap = bytes; top = peak = 0; dry = dry_; overflow = false; fl.clear(); }
-    void rewind(size_t to) { top = to; fl.clear(); }
-    Buf alloc(size_t bytes) {
-        bytes = round(bytes ? bytes : 1);
-        size_t best = SIZE_MAX, best_size = SIZE_MAX;
-        for (size_t f = 0; f < fl.size(); ++f)
-            if (fl[f].size >= bytes && fl[f].size < best_size) { best = f; best_size = fl[f].size; }
-        Buf b;
-        b.bytes = bytes;
-        if (best != SIZE_MAX) {
-            b.off = fl[best].off;
-            fl[best].off += bytes;
-            fl[best].size -= bytes;
-            if (fl[best].size == 0) fl.erase(fl.begin() + best);
-        } else {
-            b.off = top;
-            top += bytes;
-            peak = std::max(peak, top);
-            if (!dry && top > cap) overflow = true;
-        }
-        return b;
-    }
-    void release(Buf& b) {
-        if (!b.ok()) return;
-        fl.push_back({b.off, b.bytes});
-        std::sort(fl.begin(), fl.end(), [](const Free& x, const Free& y) { return x.off < y.off; });
-        std::vector<Free> merged;
-        for (const Free& f : fl) {
-            if (!merged.empty() && merged.back().off + merged.back().size == f.off) merged.back().size += f.size;
-            else merged.push_back(f);
-        }
-        if (!merged.empty() && merged.back().off + merged.back().size == top) {
-            top = merged.back().off;
-            merged.pop_back();
-        }
-        fl.swap(merged);
-        b = Buf();
-    }
-    float* p(const Buf& b) const { return b.ok() ? reinterpret_cast<float*>(base + b.off) : nullptr; }
-};
-
 __global__ void loss_total_kernel(const float* __restrict__ loss4, float* __restrict__ loss5) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         // model.py:364: total = xy + wh + conf + class, summed in this order
@@ -203,20 +149,12 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
             ? y3_conv_stats_blocks(&d, r.kind == RouteKind::Wino44 ? 2 : r.kind == RouteKind::Wino ? 1 : 0) : 0;
         Buf part = nblk ? A.alloc((size_t)nblk * 2 * cout * 4) : Buf();
         // the kernel in this step's packing (the variable changes every step)
-        const size_t kelems = (size_t)l.k * l.k * l.cin * cout;
-        Buf wp;
-        const float* wdev = v.weights;                      // Cin = 3 stem: HWIO as it is
-        if (l.cin != 3) {
-            wp = A.alloc(r.kind == RouteKind::Wino44 ? (size_t)36 * l.cin * cout * 4 : r.kind == RouteKind::Wino
-                         ? (size_t)16 * l.cin * cout * 4 : kelems * (r.kind == RouteKind::Split ? 2 * r.planes : 4));
-            float* p = A.p(wp);
-            switch (r.kind) {
-            case RouteKind::Wino44: Y3_TRY(y3_pack_conv_weights_wino44(ctx, v.weights, l.cin, cout, p)); break;
-            case RouteKind::Wino: Y3_TRY(y3_pack_conv_weights_wino(ctx, v.weights, l.cin, cout, p)); break;
-            case RouteKind::Split: Y3_TRY(y3_pack_conv_weights_split(ctx, v.weights, l.k, l.cin, cout, r.planes, p)); break;
-            default: Y3_TRY(y3_pack_conv_weights(ctx, v.weights, l.k, l.cin, cout, p));
-            }
-            wdev = p;
+        const ConvPack pk = y3_conv_pack(*net, (int)i, r);
+        Buf wp = pk.bytes() ? A.alloc(pk.bytes()) : Buf();
+        const float* wdev = v.weights;                      // (Hwio: the variable as it is)
+        if (wp.ok()) {
+            Y3_TRY(pk.launch(ctx, v.weights, A.p(wp)));
+            wdev = A.p(wp);
         }
         const float* ones = A.p(S.ones);
         const float* zeros = A.p(S.zeros);
@@ -476,17 +414,9 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
         const int src = l.src, up = l.up;
         const bool need_src = needs(src), need_up = up >= 0 && needs(up);
         if (need_src || need_up) {
-            Buf wk;                           // the kernel in the data gradient's packing
-            if (r.kind != RouteKind::Direct)
-                wk = A.alloc(r.kind == RouteKind::Wino44 ? (size_t)36 * cin * dz_stride * 4 : r.kind == RouteKind::Wino
-                             ? (size_t)16 * cin * dz_stride * 4 : (size_t)r.planes * l.k * l.k * cin * dz_stride * 2);
-            switch (r.kind) {
-            case RouteKind::Wino44: Y3_TRY(y3_pack_conv_weights_wino44_dgrad(ctx, w_d, cin, dz_stride, A.p(wk))); break;
-            case RouteKind::Wino: Y3_TRY(y3_pack_conv_weights_wino_dgrad(ctx, w_d, cin, dz_stride, A.p(wk))); break;
-            case RouteKind::Split:
-                Y3_TRY(y3_pack_conv_weights_split_dgrad(ctx, w_d, l.k, cin, dz_stride, r.planes, A.p(wk))); break;
-            default: break;                   // (the direct kernel reads w_d)
-            }
+            const ConvPack pk = y3_conv_pack(*net, i, r, true);
+            Buf wk = pk.bytes() ? A.alloc(pk.bytes()) : Buf();      // the kernel in the data gradient's packing
+            if (wk.ok()) Y3_TRY(pk.launch(ctx, w_d, A.p(wk)));       // (the direct kernel reads w_d)
             const y3_conv_desc g = {n, d.h, d.w, dz_stride, 0, cin, 3, 1, 0};    // Winograd: a stride-1 3x3 conv, dz_stride -> Cin
             y3_sk_opts so;
             so.err = dry ? nullptr : ctx->err_host;

@@ -12,78 +12,10 @@ BN_EPS = 1e-5  # model.py:37
 _param_cache = {}  # weights op_name -> (version key, w_dev, scale, shift)
 
 
-def prepare_conv_params_bf16(w_var, bn_vars=None, bias_var=None):
-    """As prepare_conv_params, with the kernel packed to bf16 (the 3->32 stem keeps its fp32 HWIO kernel)."""
-    w32, scale, shift = prepare_conv_params(w_var, bn_vars=bn_vars, bias_var=bias_var)
-    k, _, cin, cout = w_var.shape
-    if cin == 3:
-        return w32, scale, shift
-    key = w_var.op_name + '#bf16'
-    hit = _param_cache.get(key)
-    if hit is not None and hit[0] == w_var.version:
-        return hit[1], scale, shift
-    wb = torch.empty(k * k * cout * cin, dtype=torch.bfloat16, device=w_var.tensor.device)
-    _lib.check(_lib.lib().y3_pack_conv_weights_bf16(fw.context(), fw.ptr(w_var.tensor), k, cin, cout, fw.ptr(wb)))
-    _param_cache[key] = (w_var.version, wb)
-    return wb, scale, shift
-
-
-SPLIT_PLANES = {'f32_bf16x6': 3, 'f32_bf16x3': 2}
-
-
-def prepare_conv_params_split(w_var, bn_vars=None, bias_var=None, planes=3):
-    """As prepare_conv_params, with the kernel pre-split into `planes` bf16 planes for the fp32-on-bf16-MFMA
-    kernels (y3_conv_split.hip); the 3->32 stem keeps its fp32 HWIO kernel."""
-    w32, scale, shift = prepare_conv_params(w_var, bn_vars=bn_vars, bias_var=bias_var)
-    k, _, cin, cout = w_var.shape
-    if cin == 3:
-        return w32, scale, shift
-    key = w_var.op_name + '#split%d' % planes
-    hit = _param_cache.get(key)
-    if hit is not None and hit[0] == w_var.version:
-        return hit[1], scale, shift
-    ws = torch.empty(planes * k * k * cout * cin, dtype=torch.bfloat16, device=w_var.tensor.device)
-    _lib.check(_lib.lib().y3_pack_conv_weights_split(fw.context(), fw.ptr(w_var.tensor), k, cin, cout, planes,
-                                                     fw.ptr(ws)))
-    _param_cache[key] = (w_var.version, ws)
-    return ws, scale, shift
-
-
 def wino_eligible(k, stride, cin, cout, c_up=0):
     """True for the convs the Winograd kernel takes (the rule lives in the library: y3_conv_wino_eligible)."""
     d = _lib.ConvDesc(1, 8, 8, cin, c_up, cout, k, stride, 1)
     return _lib.lib().y3_conv_wino_eligible(ctypes.byref(d)) == 1
-
-
-def prepare_conv_params_wino(w_var, bn_vars=None, bias_var=None, stride=1):
-    """As prepare_conv_params, with the Winograd-transformed kernel for the eligible layers (the others keep the
-    direct kernel's packing)."""
-    w32, scale, shift = prepare_conv_params(w_var, bn_vars=bn_vars, bias_var=bias_var)
-    k, _, cin, cout = w_var.shape
-    if not wino_eligible(k, stride, cin, cout):
-        return w32, scale, shift
-    key = w_var.op_name + '#wino'
-    hit = _param_cache.get(key)
-    if hit is not None and hit[0] == w_var.version:
-        return hit[1], scale, shift
-    wu = pack_wino(w_var.tensor)
-    _param_cache[key] = (w_var.version, wu)
-    return wu, scale, shift
-
-
-def prepare_conv_alt_wino44(w_var, stride=1):
-    """The F(4x4,3x3) packing of a layer y3_conv_wino44_candidate names (None for the others): y3_net_forward runs such a
-    layer on that kernel when the launch is large enough (y3_net_set_layer_alt)."""
-    k, _, cin, cout = w_var.shape
-    if not wino44_candidate(k, stride, cin, cout):
-        return None
-    key = w_var.op_name + '#wino44'
-    hit = _param_cache.get(key)
-    if hit is not None and hit[0] == w_var.version:
-        return hit[1]
-    wu = pack_wino44(w_var.tensor)
-    _param_cache[key] = (w_var.version, wu)
-    return wu
 
 
 def prepare_conv_params(w_var, bn_vars=None, bias_var=None):
@@ -205,12 +137,6 @@ def wino44_eligible(k, stride, cin, cout, c_up=0):
     """True for the convs the F(4x4,3x3) inference kernel takes (y3_conv_wino44_eligible)."""
     d = _lib.ConvDesc(1, 8, 8, cin, c_up, cout, k, stride, 0)
     return _lib.lib().y3_conv_wino44_eligible(ctypes.byref(d)) == 1
-
-
-def wino44_candidate(k, stride, cin, cout, c_up=0):
-    """True for the conv shapes worth an F(4x4,3x3) packing beside the F(2x2,3x3) one (y3_conv_wino44_candidate)."""
-    d = _lib.ConvDesc(1, 8, 8, cin, c_up, cout, k, stride, 0)
-    return _lib.lib().y3_conv_wino44_candidate(ctypes.byref(d)) == 1
 
 
 def wino44_preferred(n, h, w, k, stride, cin, cout, c_up=0):

@@ -37,7 +37,8 @@ class yolov3(object):
         self.use_focal_loss = use_focal_loss
         self.weight_decay = weight_decay
         self.use_static_shape = use_static_shape
-        self._nets = {}   # (ctx key, scope, dtype) -> dict(handle, version, keepalive, workspace)
+        self._nets = {}   # (ctx key, scope, dtype) -> dict(handle, table, variables, bound parameters, workspace)
+        self._params = {}  # (device, scope, dtype) -> dict(buf, bytes, versions): the packed parameters (_get_net)
         self.inference_streams = 1    # > 1: inference forwards split the batch over that many HIP streams (opt-in)
         self.img_size = None
         # 'f32' (the reference's precision), 'f32_bf16x6' / 'f32_bf16x3' (fp32 tensors, products on the bf16
@@ -81,8 +82,6 @@ class yolov3(object):
     def _get_net(self, device):
         if self.compute_dtype not in NET_DTYPES:
             raise ValueError("compute_dtype must be one of %s" % (sorted(NET_DTYPES),))
-        bf16 = self.compute_dtype == 'bf16'
-        planes = engine.SPLIT_PLANES.get(self.compute_dtype, 0)
         ctx = fw.context(device)
         scope = fw.current_scope_name()
         key = (ctx.value, scope, self.compute_dtype)
@@ -94,28 +93,30 @@ class yolov3(object):
             if NET_DTYPES[self.compute_dtype]:
                 _lib.check(L.y3_net_set_dtype(h, NET_DTYPES[self.compute_dtype]))
             table = self._layer_table(h)
-            ent = dict(handle=h, table=table, version=-1, keep=None, ws=None, ws_bytes=0,
+            ent = dict(handle=h, table=table, params=None, ws=None, ws_bytes=0,
                        layers=self._ensure_variables(scope, table))
             self._nets[key] = ent
-        if ent['version'] != fw.global_version():
-            keep = []
-            for i, (w, bnv, bias) in enumerate(ent['layers']):
-                if self.compute_dtype == 'f32_wino':
-                    wp, sc, sh = engine.prepare_conv_params_wino(w, bn_vars=bnv, bias_var=bias,
-                                                                 stride=ent['table'][i][1])
-                elif planes:
-                    wp, sc, sh = engine.prepare_conv_params_split(w, bn_vars=bnv, bias_var=bias, planes=planes)
-                else:
-                    prep = engine.prepare_conv_params_bf16 if bf16 else engine.prepare_conv_params
-                    wp, sc, sh = prep(w, bn_vars=bnv, bias_var=bias)
-                _lib.check(L.y3_net_set_layer(ent['handle'], i, fw.ptr(wp), fw.ptr(sc), fw.ptr(sh)))
-                alt = None
-                if self.compute_dtype == 'f32_wino':       # the F(4x4,3x3) packing beside it, where the library wants one
-                    alt = engine.prepare_conv_alt_wino44(w, stride=ent['table'][i][1])
-                    _lib.check(L.y3_net_set_layer_alt(ent['handle'], i, fw.ptr(alt)))
-                keep.append((wp, sc, sh, alt))
-            ent['keep'] = keep   # the library holds raw pointers: keep the tensors alive
-            ent['version'] = fw.global_version()
+        # the library packs the parameters (y3_net_set_params): one buffer per (device, scope, dtype), repacked when a variable
+        # of this net changes, and bound by the nets of the other streams (their forwards wait for this stream)
+        pkey = (str(device), scope, self.compute_dtype)
+        p = self._params.get(pkey)
+        if p is None or p['checked'] != fw.global_version():
+            versions = tuple(v.version for layer in ent['layers'] for v in
+                             ((layer[0],) + tuple(layer[1] or ()) + ((layer[2],) if layer[2] is not None else ())))
+            if p is None or p['versions'] != versions:
+                if p is None:
+                    nbytes = L.y3_net_params_bytes(ent['handle'])
+                    p = dict(buf=torch.empty(nbytes, dtype=torch.uint8, device=device), bytes=nbytes)
+                    self._params[pkey] = p
+                from . import training
+                table, _ = training._var_table(ent['layers'])
+                _lib.check(L.y3_net_set_params(ent['handle'], table, fw.ptr(p['buf']), ctypes.c_size_t(p['bytes'])))
+                ent['params'] = p['buf']
+                p['versions'] = versions
+            p['checked'] = fw.global_version()
+        if ent['params'] is not p['buf']:
+            _lib.check(L.y3_net_set_params(ent['handle'], None, fw.ptr(p['buf']), ctypes.c_size_t(p['bytes'])))
+            ent['params'] = p['buf']
         return ent
 
     # ------------------------------------------------------------------------------------------
