@@ -388,6 +388,37 @@ int y3_conv2d_dgrad_wino(y3_ctx* ctx, const y3_conv_desc* fwd, const float* dz, 
 size_t y3_conv_wgrad_scratch_bytes(const y3_conv_desc* fwd);
 int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* fwd, const float* x, const float* dz, int dz_stride,
                   float* dw_hwio, void* scratch, size_t scratch_bytes);
+/* The kernels of the bf16 train step (net dtype 1; numerics contract: the train-step block below).  bf16 tensors are
+ * 16-bit words (round to nearest even); `fwd` describes the FORWARD layer as for y3_conv2d_dgrad (c_up = 0, act ignored).
+ * pack_bf16_train: the kernel as those convs read it: dgrad_stride 0 -> the forward's ([k*k*cin*cout] bf16), else the data
+ *        gradient's: flipped, channel axes swapped, its reduction zero-extended to dgrad_stride ([k*k*dgrad_stride*cin]).
+ * train_fwd_bf16: z [n,ho,wo,cout] bf16 = conv(x bf16, w) with no scale / shift / activation, and stats
+ *        [y3_conv_train_stats_blocks_bf16(fwd)][2][cout] = per row block (sum z, sum z^2) of z AS STORED
+ *        (y3_bn_train_stats_partials finalises them).  cin % 32 == 0, cout % 4 == 0.
+ * dgrad_bf16: dx [n,h,w,cin] fp32 (+)= data gradient of dz [n,ho,wo,dz_stride] bf16 (stride 1 or the stride-2 3x3).
+ * wgrad_bf16: dw_hwio [k][k][cin][cout] fp32 from x [n,h,w,cin] bf16 and dz bf16 (row stride dz_stride >= cout);
+ *        scratch: y3_conv_wgrad_bf16_scratch_bytes(fwd) (0: none needed).  Fixed summation order.
+ * bn_apply_fwd_bf16: y bf16 = leaky(z*scale + shift) (+ residual bf16); z bf16, or fp32 when z_f32.
+ * bn_train_bwd_bf16: y3_bn_train_bwd with z bf16 and dz bf16 (dy, dgamma, dbeta fp32); scratch y3_bn_bwd_scratch_bytes(c).
+ * upsample_concat_bf16: out [n,h,w,cu+cx] = concat(upsample2x(up [n,h/2,w/2,cu]), x [n,h,w,cx]), bf16.
+ * f32_to_bf16: count (a multiple of 4) values rounded to nearest even. */
+int y3_pack_conv_weights_bf16_train(y3_ctx* ctx, const float* w_hwio, int k, int cin, int cout, int dgrad_stride,
+                                    void* w_packed);
+int y3_conv_train_stats_blocks_bf16(const y3_conv_desc* fwd);
+int y3_conv2d_train_fwd_bf16(y3_ctx* ctx, const y3_conv_desc* fwd, const void* x, const void* w_packed, void* z,
+                             float* stats);
+int y3_conv2d_dgrad_bf16(y3_ctx* ctx, const y3_conv_desc* fwd, const void* dz, int dz_stride, const void* w_packed_d,
+                         int accumulate, float* dx);
+size_t y3_conv_wgrad_bf16_scratch_bytes(const y3_conv_desc* fwd);
+int y3_conv_wgrad_bf16(y3_ctx* ctx, const y3_conv_desc* fwd, const void* x, const void* dz, int dz_stride, float* dw_hwio,
+                       void* scratch, size_t scratch_bytes);
+int y3_bn_apply_fwd_bf16(y3_ctx* ctx, const void* z, int z_f32, const float* scale, const float* shift, const void* residual,
+                         long long rows, int c, void* y);
+int y3_bn_train_bwd_bf16(y3_ctx* ctx, const void* z, const float* dy, const float* gamma, const float* scale, const float* shift,
+                         const float* mean, const float* inv_std, long long rows, int c, float* dgamma, float* dbeta, void* dz,
+                         float* scratch);
+int y3_upsample_concat_bf16(y3_ctx* ctx, const void* up, int cu, const void* x, int cx, int n, int h, int w, void* out);
+int y3_f32_to_bf16(y3_ctx* ctx, const float* src, long long count, void* dst);
 /* The weight gradient of a stride-1 3x3 conv in Winograd F(2x2,3x3) form (Cin %% 64 == 0, Cout %% 64 == 0, at least
  * 8 / ceil(w/2) + 1 rows of 2x2 tiles per image — y3_conv_wgrad_wino_eligible says):
  *   dw = G^T [ sum over 2x2 output tiles of (B^T d B) .* (A dY A^T) ] G,
@@ -433,7 +464,15 @@ int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float* y_true, in
  *                          Re-runnable from the same forward / loss state.
  *   y3_net_train_step      forward + loss + backward in one call.
  * The net's dtype picks the kernels: 0 direct fp32, 4 Winograd forms of the stride-1 3x3 convs (forward, data AND weight
- * gradient), 2 / 3 products on the bf16 matrix pipe; 1 (bf16 storage) is rejected.  Variables are plain device pointers
+ * gradient), 2 / 3 products on the bf16 matrix pipe (all four fp32-accurate), 1 mixed precision on the bf16 matrix pipe.
+ * dtype 1: rounded once (nearest even) to bf16 where stored: every saved raw conv output z, every activation and the
+ * materialised upsample+concat inputs, the packed weights, and dz (the conv-gradient operand the BN backward writes).  fp32:
+ * every MFMA accumulation, the BN batch and moving statistics (those of z AS STORED, summed in fp32), the feature maps, the
+ * loss and d loss / d fm, every activation gradient dy (accumulated across a tensor's consumers), the weight / gamma / beta /
+ * bias gradients, the variables and the optimizer.  No loss scaling (bf16 has fp32's exponent range).  The Cin = 3 stem
+ * keeps the fp32 conv, z, statistics, BN backward and weight gradient (only its output is bf16); the detection convs write
+ * fp32 feature maps with their bias, and their dz is d loss / d fm rounded once to bf16 (the bias gradient reads it in fp32).
+ * y3_net_train_saved_type tells the element type of a layer's saved z.  Variables are plain device pointers
  * in layer order (y3_net_layer_info): HWIO kernel, BN gamma / beta / moving mean / moving variance or the bias.
  * workspace: y3_net_train_workspace_bytes(net, vars, n, h, w) bytes (it depends on which variables are trainable),
  * 256-byte aligned, untouched by the caller between forward and backward.  Deterministic (fixed reduction orders). */
@@ -477,6 +516,8 @@ int y3_net_train_set_wgrad_stream(y3_net* net, void* stream);
 /* test hook: byte offsets inside the last forward's workspace of layer i's raw conv output z and of its [4][cout]
  * mean / inv_std / folded scale / folded shift (the tensors that fix the LeakyReLU branches); SIZE_MAX for non-BN layers */
 int y3_net_train_saved(const y3_net* net, int layer, size_t* z_offset, size_t* stats_offset);
+/* the element type of that z: 1 bf16 (net dtype 1, every BN layer but the Cin = 3 stem), 0 fp32 */
+int y3_net_train_saved_type(const y3_net* net, int layer);
 
 /* ---- next row 8(f)#1: target assignment on the device (utils/data_utils.py:51-115 `process_box`) ------------
  * boxes [n][kmax][5] = (x_min,y_min,x_max,y_max,mix_weight) in resized-image pixels, labels [n][kmax] int32,

@@ -41,7 +41,8 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--optimizer', default='sgd')
     ap.add_argument('--head-only', action='store_true')
-    ap.add_argument('--precision', default='f32', help='f32 | f32_bf16x6 (forward + stride-1 dgrad on the bf16 pipe)')
+    ap.add_argument('--precision', default='f32', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'],
+                    help='the train mode (training._TRAIN_DTYPES): bf16 = mixed precision on the bf16 matrix pipe')
     a = ap.parse_args()
     import torch
     import yolov3_tensorflow_amd as y3

@@ -104,6 +104,8 @@ def build_parser():
     p.add_argument('--eval_threshold', type=float, default=0.5)
     p.add_argument('--use_voc_07_metric', type=_bool, default=False)
     p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--compute_dtype', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'], default='f32',
+                   help='train-step mode: fp32-accurate modes, or bf16 = mixed precision on the bf16 matrix pipe')
     return p
 
 
@@ -198,6 +200,7 @@ def main(argv=None):
     y3.set_init_seed(args.seed)
     yolo_model = y3.yolov3(args.class_num, args.anchors, args.use_label_smooth, args.use_focal_loss,
                            args.batch_norm_decay, args.weight_decay, use_static_shape=False)
+    yolo_model.compute_dtype = args.compute_dtype
     with y3.variable_scope('yolov3'):
         yolo_model.forward(torch.zeros((1, 64, 64, 3)), False)                 # create the variables
     variables = y3.global_variables(scope='yolov3')

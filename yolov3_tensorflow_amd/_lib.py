@@ -93,6 +93,18 @@ PROTOTYPES = {
                                   POINTER(TrainOpts), c_void_p, c_void_p, c_size_t, c_void_p, GradReadyFn, c_void_p]),
     "y3_net_train_set_wgrad_stream": (c_int, [c_void_p, c_void_p]),
     "y3_net_train_saved": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "y3_net_train_saved_type": (c_int, [c_void_p, c_int]),
+    "y3_pack_conv_weights_bf16_train": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "y3_conv_train_stats_blocks_bf16": (c_int, [POINTER(ConvDesc)]),
+    "y3_conv2d_train_fwd_bf16": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y3_conv2d_dgrad_bf16": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "y3_conv_wgrad_bf16_scratch_bytes": (c_size_t, [POINTER(ConvDesc)]),
+    "y3_conv_wgrad_bf16": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
+    "y3_bn_apply_fwd_bf16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p]),
+    "y3_bn_train_bwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y3_upsample_concat_bf16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "y3_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
     "y3_net_set_dtype": (c_int, [c_void_p, c_int]),
     "y3_upsample_nearest": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "y3_concat_channels": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_longlong, c_void_p]),

@@ -32,6 +32,7 @@ SOURCES = [
     ("y3_ops.hip", ["-ffp-contract=off"]),
     ("y3_train.hip", ["-ffp-contract=off"]),
     ("y3_wgrad.hip", []),
+    ("y3_wgrad_bf16.hip", []),
     ("y3_wgrad_wino.hip", []),
     ("y3_feed_gpu.hip", ["-ffp-contract=off"]),
 ]

@@ -470,9 +470,17 @@ ConvRoute y3_route_infer(const y3_net& net, int i, int n, int h, int w) {
     return r;
 }
 
+// The bf16 train step (dtype 1) runs every conv but the Cin = 3 stem (fp32 image in: today's fp32 route) on Bf16Train
+static bool bf16_train(const y3_net& net, int i) { return net.dtype == NetDtype::BF16 && net.layers[i].cin != 3; }
+
 ConvRoute y3_route_train_fwd(const y3_net& net, int i, int n, int h, int w) {
     const Layer& l = net.layers[i];
     const y3_conv_desc d = net.desc(i, n, h, w, true);
+    if (bf16_train(net, i)) {
+        ConvRoute r;
+        r.kind = RouteKind::Bf16Train;
+        return r;
+    }
     const bool wino = net.dtype == NetDtype::F32_WINO && y3_conv_wino_eligible_impl(&d);
     // F(4x4,3x3) where it fills the chip (y3_conv_wino44_preferred); the Cin = 3 stem reads its HWIO kernel as it is
     return fp32_route(d, wino && l.bn && y3_conv_wino44_preferred_impl(&d), wino, l.cin == 3 ? 0 : split_planes(net.dtype));
@@ -484,6 +492,11 @@ ConvRoute y3_route_train_fwd(const y3_net& net, int i, int n, int h, int w) {
 // The data gradient: a conv over dz [n, ho, wo, dz_stride] (Cout; the detection convs' padded to det_pad), channel axes swapped.
 ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w) {
     const Layer& l = net.layers[i];
+    if (net.dtype == NetDtype::BF16) {      // (the stem's data gradient never runs: nothing is below it)
+        ConvRoute r;
+        r.kind = RouteKind::Bf16Train;
+        return r;
+    }
     const y3_conv_desc d = net.desc(i, n, h, w, true);
     const y3_conv_desc g = {n, d.h, d.w, net.dz_stride(i), 0, l.cin, l.k, l.stride, 0};
     const bool wino = net.dtype == NetDtype::F32_WINO && l.up < 0 && l.k == 3 && l.stride == 1 && y3_conv_wino_eligible_impl(&g);
@@ -503,6 +516,15 @@ ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w) {
 ConvRoute y3_route_wgrad(const y3_net& net, int i, int n, int h, int w) {
     ConvRoute r;
     const y3_conv_desc d = net.desc(i, n, h, w, true);
+    if (bf16_train(net, i)) {
+        r.kind = RouteKind::Bf16Train;
+        r.scratch = y3_conv_wgrad_bf16_scratch_bytes(&d);
+        return r;
+    }
+    if (net.dtype == NetDtype::BF16) {      // the stem: the fp32 kernel over the fp32 image and dz
+        r.scratch = y3_conv_wgrad_scratch_bytes(&d);
+        return r;
+    }
     const bool wino = net.dtype == NetDtype::F32_WINO && y3_conv_wgrad_wino_eligible_impl(&d);
     r.kind = wino ? RouteKind::Wino : RouteKind::Direct;
     // (the Winograd kernel's scratch is reserved in every dtype: the workspace size the train step has always asked for)
@@ -516,6 +538,7 @@ ConvPack y3_conv_pack(const y3_net& net, int i, const ConvRoute& r, bool dgrad) 
     ConvPack p;
     p.planes = r.planes; p.dgrad = dgrad;
     p.k = l.k; p.cin = l.cin; p.cout = dgrad ? net.dz_stride(i) : l.cout;
+    p.wcout = l.cout;
     switch (r.kind) {
     case RouteKind::Wino44: p.kind = Packing::Wino44; break;
     case RouteKind::Wino: p.kind = Packing::Wino; break;
@@ -523,6 +546,7 @@ ConvPack y3_conv_pack(const y3_net& net, int i, const ConvRoute& r, bool dgrad) 
     case RouteKind::Bf16: case RouteKind::StemS2Bf16: case RouteKind::ResBlock64Bf16: p.kind = Packing::Bf16; break;
     case RouteKind::InNext: p.kind = net.dtype == NetDtype::BF16 ? Packing::Bf16 : Packing::Direct; break;
     case RouteKind::Direct: case RouteKind::StemS2F32: p.kind = dgrad ? Packing::Hwio : Packing::Direct; break;
+    case RouteKind::Bf16Train: p.kind = Packing::Bf16Reg; break;
     }
     if (l.cin == 3 && !dgrad) p.kind = Packing::Hwio;      // the stem reads its HWIO kernel in every dtype
     return p;
@@ -532,7 +556,7 @@ size_t ConvPack::bytes() const {
     const size_t taps = (size_t)k * k * cin * cout;
     switch (kind) {
     case Packing::Direct: return taps * 4;
-    case Packing::Bf16: return taps * 2;
+    case Packing::Bf16: case Packing::Bf16Reg: return taps * 2;
     case Packing::Split: return taps * 2 * planes;
     case Packing::Wino: return (size_t)16 * cin * cout * 4;
     case Packing::Wino44: return (size_t)36 * cin * cout * 4;
@@ -545,6 +569,9 @@ int ConvPack::launch(y3_ctx* ctx, const float* w, void* out) const {
     switch (kind) {
     case Packing::Direct: return y3_pack_conv_weights(ctx, w, k, cin, cout, o);
     case Packing::Bf16: return y3_pack_conv_weights_bf16(ctx, w, k, cin, cout, out);
+    case Packing::Bf16Reg:     // (the data gradient's: `cout` is dz_stride, the variable's Cout is the layer's)
+        return dgrad ? y3_pack_conv_weights_bf16_reg(ctx, w, k, cin, wcout, cout, out)
+                     : y3_pack_conv_weights_bf16_reg(ctx, w, k, cin, cout, 0, out);
     case Packing::Split:
         return dgrad ? y3_pack_conv_weights_split_dgrad(ctx, w, k, cin, cout, planes, out)
                      : y3_pack_conv_weights_split(ctx, w, k, cin, cout, planes, out);
@@ -724,6 +751,7 @@ extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, 
         case RouteKind::Split:
             rc = y3_launch_conv_split(st, &d, r.planes, src, up, lw, l.scale, l.shift, res, y, scratch, sb, &o); break;
         case RouteKind::Direct: rc = y3_launch_conv(st, &d, src, up, lw, l.scale, l.shift, res, y, scratch, sb, &o); break;
+        case RouteKind::Bf16Train: y3_set_error("y3_net_forward: layer %d has a train-step route", i); return Y3_EINVAL;
         }
         if (rc != Y3_OK) return rc;
         if (ev) Y3_CHECK_HIP(hipEventRecord(ev[i + 1], st));

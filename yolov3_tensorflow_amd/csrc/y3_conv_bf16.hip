@@ -14,7 +14,9 @@
 //   * epilogue in fp32 (scale/shift, LeakyReLU, residual), ONE rounding to bf16 (round-to-nearest-even) at the
 //     store; the detection convs (linear, 3*(5+C) channels) write fp32 so that decode/NMS are unchanged.
 // Data-parallel schedule with XCD-contiguous tile ids (no stream-K: the kernel is not matrix-pipe bound).
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include "y3_internal.h"
 
@@ -38,6 +40,29 @@ struct ConvArgsB {
     int stride, pad, act, out_f32;
     int M;
 };
+
+// The training forms of the kernel (compile time, so that the inference instantiations carry none of their state):
+//   EPI 1 (forward): the raw conv output z in bf16 (no scale, shift or activation), and per M-block column partials
+//         [nbm][2][Cout] = (sum z, sum z^2) of the values AS STORED, the rows y3_bn_train_stats_partials finalises;
+//   EPI 2 (data gradient): fp32 output, written or (acc) added to, no activation;
+//   TMODE (EPI 2): the data gradient of a stride-2 3x3 conv, ONE output parity class (cy, cx) per launch - a dense conv over
+//         the N*Ho*Wo rows of dz with 1, 2, 2 or 4 taps, written to pixel (2y'+cy, 2x'+cx) of dx (y3_conv.hip's TMODE).
+struct ConvArgsT : ConvArgsB {
+    float* stats;        // EPI 1
+    int acc;             // EPI 2
+    int cy, cx, ntaps;   // TMODE
+};
+
+// the training fields of an argument block (the inference instantiations read ConvArgsB: none)
+struct TrainFields {
+    float* stats = nullptr;
+    int acc = 0, cy = 0, cx = 0, ntaps = 0;
+};
+__device__ __forceinline__ TrainFields train_fields(const ConvArgsT& p) {
+    TrainFields f;
+    f.stats = p.stats; f.acc = p.acc; f.cy = p.cy; f.cx = p.cx; f.ntaps = p.ntaps;
+    return f;
+}
 
 constexpr int BKB = 32;            // K elements per step
 constexpr int LDB = 64;            // LDS row stride in bytes (unpadded; 16-byte slots swizzled, see lds_off)
@@ -323,6 +348,257 @@ __global__ void __launch_bounds__(256, 3) conv_mfma_bf16_kernel(const ConvArgsB 
     }
 }
 
+// the body of conv_mfma_bf16_kernel with the training forms (a copy: the inference kernel keeps its code and registers)
+template <int BM, int BN, int WGM, int WGN, int KS, int EPI, bool TMODE>
+__device__ __forceinline__ void conv_train_body(const ConvArgsT& p) {
+    static_assert(EPI == 1 || EPI == 2, "the training forms");
+    static_assert(!TMODE || (EPI == 2 && KS == 3), "the transposed gather is the stride-2 3x3 data gradient");
+    constexpr int WTM = BM / WGM, WTN = BN / WGN;
+    constexpr int MI = WTM / 32, NI = WTN / 32;
+    static_assert(WGM * WGN == 4 && MI >= 1 && NI >= 1, "bad wave layout");
+    constexpr int ACH = BM * 4 / 256;                 // 16-byte chunks of A each thread stages (2)
+    constexpr int BCH = (BN * 4 + 255) / 256;         // of B (2, 1, 1)
+    constexpr int LDC = BN + 4;                       // fp32 epilogue staging stride (floats), 64 rows at a time
+    const TrainFields tf = train_fields(p);
+    // (the launcher allocates max(2 * TILE_BYTES, 64 * LDC * 4): the epilogue stages 64 fp32 rows at a time)
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* As = smem;                        // [2][BM][80 B]
+    unsigned char* Bs = smem + 2 * BM * LDB;         // [2][BN][80 B]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WGN, wn = wave % WGN;
+    const int nbm = (p.M + BM - 1) / BM;
+    const int kchunks = p.Cin / BKB;
+    int taps = KS * KS;
+    if constexpr (TMODE) taps = tf.ntaps;
+    const int S = taps * kchunks;
+
+    // XCD-contiguous, column-major tile id (see y3_conv.hip)
+    const int nt = gridDim.x;
+    const int q8 = nt >> 3, r8 = nt & 7, xcd = blockIdx.x & 7, kk8 = blockIdx.x >> 3;
+    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + kk8;
+    const int bn = tile / nbm, bm = tile - bn * nbm;
+    const int m0 = bm * BM, n0 = bn * BN;
+
+    const int ch = tid & 3;          // 16-byte chunk inside the 64-byte row
+    const int r0 = tid >> 2;         // rows r0 + 64*j
+    const int c8 = ch * 8;           // element offset of the chunk
+
+    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16_t*>(p.x), 0, (unsigned)((size_t)p.N * p.H * p.W * p.Cx * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16_t*>(p.w), 0, (unsigned)((size_t)KS * KS * p.Cout * p.Cin * 2), 0x00020000);
+
+    int a_base[ACH], a_msk[ACH];
+    unsigned b_voff[BCH];
+    int ld_tap = 0, ld_cc = 0;
+    {
+        const int HoWo = p.Ho * p.Wo;
+#pragma unroll
+        for (int j = 0; j < ACH; ++j) {
+            const int m = m0 + r0 + 64 * j;
+            int mk = 0, base = 0;
+            if (m < p.M) {
+                const int n = m / HoWo;
+                const int rem = m - n * HoWo;
+                const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
+                const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+#pragma unroll
+                for (int t = 0; t < KS; ++t) {
+                    if ((unsigned)(iy0 + t) < (unsigned)p.H) mk |= 1 << t;
+                    if ((unsigned)(ix0 + t) < (unsigned)p.W) mk |= 1 << (4 + t);
+                }
+                base = ((n * p.H + iy0) * p.W + ix0) * p.Cx;
+            }
+            a_msk[j] = mk; a_base[j] = base;
+        }
+#pragma unroll
+        for (int j = 0; j < BCH; ++j) {
+            const int co = n0 + r0 + 64 * j;
+            const bool ok = co < p.Cout && (BN >= 64 || r0 < BN) && (r0 + 64 * j) < BN;
+            b_voff[j] = ok ? (unsigned)(co * BKB + c8) * 2u : OOB;
+        }
+    }
+    u32x4 ra[2][ACH], rb[2][BCH];
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+
+    // fetch the prepared K-step into register set s and step the loader; branch-free (past the last K-step the
+    // loads read in-bounds-or-zero addresses and are never consumed)
+    auto issue = [&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        int ky = (KS == 1) ? 0 : ld_tap / KS;
+        int kx = (KS == 1) ? 0 : ld_tap - ky * KS;
+        int wtap = ld_tap;
+        if constexpr (TMODE) {
+            // tap (ky, kx) of the flipped kernel (the dgrad packing) reads dz at (y' + ky', x' + kx'); past the last tap
+            // (the loader runs two K-steps ahead) the plane is clamped: those loads are never consumed
+            const int nkx = tf.cx ? 2 : 1;
+            const int ty = ld_tap / nkx, tx = ld_tap - ty * nkx;
+            const int fy = tf.cy ? 2 * ty : 1, fx = tf.cx ? 2 * tx : 1;
+            wtap = min(fy * KS + fx, KS * KS - 1);
+            ky = (tf.cy + fy - 1) >> 1;
+            kx = (tf.cx + fx - 1) >> 1;
+        }
+        const int tap_off = (ky * p.W + kx) * p.Cx + c8;
+        const unsigned soff = (unsigned)(ld_cc * BKB) * 2u;
+#pragma unroll
+        for (int j = 0; j < ACH; ++j) {
+            const bool ok = ((a_msk[j] >> ky) & (a_msk[j] >> (4 + kx)) & 1) != 0;
+            const unsigned voff = ok ? (unsigned)(a_base[j] + tap_off) * 2u : OOB;
+            ra[s][j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, voff, soff, 0);
+        }
+        // weights: [tap][Cin/32][Cout][32] — the B tile of a K-step is contiguous
+        const unsigned wsoff = (unsigned)((wtap * kchunks + ld_cc) * p.Cout) * (BKB * 2u);
+#pragma unroll
+        for (int j = 0; j < BCH; ++j) rb[s][j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, b_voff[j], wsoff, 0);
+        const bool wrap = ++ld_cc == kchunks;
+        ld_cc = wrap ? 0 : ld_cc;
+        ld_tap += wrap ? 1 : 0;
+    };
+    auto store = [&](auto sc) {
+        constexpr int s = decltype(sc)::value;      // register set s -> LDS buffer s
+        unsigned char* as = As + s * BM * LDB;
+        unsigned char* bs = Bs + s * BN * LDB;
+#pragma unroll
+        for (int j = 0; j < ACH; ++j) *reinterpret_cast<u32x4*>(as + lds_off(r0 + 64 * j, ch)) = ra[s][j];
+#pragma unroll
+        for (int j = 0; j < BCH; ++j)
+            if ((r0 + 64 * j) < BN) *reinterpret_cast<u32x4*>(bs + lds_off(r0 + 64 * j, ch)) = rb[s][j];
+    };
+
+    f32x16 acc[MI][NI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+
+    // lane l feeds row l&31 of each 32x32 MFMA tile with the 8 k-values of slot 2*kk + (l>>5); tile row bases are
+    // multiples of 32, so the swizzle term depends on the lane only
+    const int frag_row = lane & 31, frag_half = lane >> 5;
+    auto compute = [&](int buf) {
+        const unsigned char* as = As + buf * BM * LDB + wm * WTM * LDB;
+        const unsigned char* bs = Bs + buf * BN * LDB + wn * WTN * LDB;
+#pragma unroll
+        for (int kk = 0; kk < BKB / 16; ++kk) {
+            const int off = lds_off(frag_row, 2 * kk + frag_half);
+            bf16x8 a[MI], b[NI];
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+                a[mi] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(as + mi * 32 * LDB + off));
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni)
+                b[ni] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bs + ni * 32 * LDB + off));
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < NI; ++ni)
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+        }
+    };
+
+    // K-step g uses LDS buffer / register set g&1; its loads were issued two K-steps earlier
+    I0 i0;
+    I1 i1;
+    issue(i0);
+    issue(i1);
+    store(i0);
+    __syncthreads();
+    for (int g = 0; g < S; g += 2) {
+        issue(i0);                     // K-step g+2
+        compute(0);
+        store(i1);                     // K-step g+1
+        __syncthreads();
+        issue(i1);                     // K-step g+3
+        if (g + 1 < S) compute(1);
+        store(i0);                     // K-step g+2
+        __syncthreads();
+    }
+
+    // ---- epilogue --------------------------------------------------------------------------------------
+    const int col_l = lane & 31, row_l = 4 * (lane >> 5);
+    float* cs = reinterpret_cast<float*>(smem);
+    constexpr int C4 = BN / 4, RPP = 256 / C4, PASSES = 64 / RPP;
+    const int tc = (tid % C4) * 4, tr = tid / C4;
+    const int col = n0 + tc;
+    const bool cok = col < p.Cout;
+    f32x4 st_s = {0.f, 0.f, 0.f, 0.f}, st_q = {0.f, 0.f, 0.f, 0.f};    // EPI 1: this thread's column sums
+#pragma unroll
+    for (int half = 0; half < BM / 64; ++half) {
+        // the waves whose rows fall in [64*half, 64*half+64) stage their accumulators (fp32)
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+            const int rbase = wm * WTM + mi * 32;
+            if (rbase / 64 == half) {
+#pragma unroll
+                for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        cs[(rbase - 64 * half + row_l + (r & 3) + 8 * (r >> 2)) * LDC + wn * WTN + ni * 32 + col_l] =
+                            acc[mi][ni][r];
+            }
+        }
+        __syncthreads();
+        if (cok) {
+#pragma unroll
+            for (int i = 0; i < PASSES; ++i) {
+                const int rr = tr + i * RPP;
+                const int row = m0 + 64 * half + rr;
+                if (EPI == 1 && row < p.M) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(cs + rr * LDC + tc);
+                    u32x2 pk;
+                    pk[0] = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
+                    pk[1] = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
+                    *reinterpret_cast<u32x2*>(static_cast<bf16_t*>(p.y) + (size_t)row * p.Cout + col) = pk;
+                    const f32x4 r = {__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xFFFF0000u),
+                                     __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xFFFF0000u)};
+                    st_s += r;
+                    st_q += r * r;
+                } else if (EPI == 2 && row < p.M) {
+                    f32x4 v = *reinterpret_cast<const f32x4*>(cs + rr * LDC + tc);
+                    size_t o = (size_t)row * p.Cout + col;
+                    if constexpr (TMODE) {
+                        // row (n, y', x') of the parity class -> pixel (2y'+cy, 2x'+cx) of dx [N][2Ho][2Wo][Cout]
+                        const int HoWo = p.Ho * p.Wo;
+                        const int n = row / HoWo, rem = row - n * HoWo;
+                        const int yy = rem / p.Wo, xx = rem - yy * p.Wo;
+                        o = ((size_t)(n * 2 * p.Ho + 2 * yy + tf.cy) * (2 * p.Wo) + 2 * xx + tf.cx) * p.Cout + col;
+                    }
+                    float* yp = static_cast<float*>(p.y) + o;
+                    if (tf.acc) v += *reinterpret_cast<const f32x4*>(yp);
+                    *reinterpret_cast<f32x4*>(yp) = v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if constexpr (EPI == 1) {
+        // the RPP threads of a column quad combine their sums in a fixed order; row bm of the partials
+        f32x4* red = reinterpret_cast<f32x4*>(smem);      // [RPP][2][C4]
+        red[(tr * 2 + 0) * C4 + tc / 4] = st_s;
+        red[(tr * 2 + 1) * C4 + tc / 4] = st_q;
+        __syncthreads();
+        if (tr == 0 && cok) {
+#pragma unroll
+            for (int k = 1; k < RPP; ++k) {
+                st_s += red[(k * 2 + 0) * C4 + tc / 4];
+                st_q += red[(k * 2 + 1) * C4 + tc / 4];
+            }
+            float* ps = tf.stats + (size_t)bm * 2 * p.Cout + col;
+            *reinterpret_cast<f32x4*>(ps) = st_s;
+            *reinterpret_cast<f32x4*>(ps + p.Cout) = st_q;
+        }
+    }
+}
+
+template <int BM, int BN, int WGM, int WGN, int KS, int EPI, bool TMODE>
+__global__ void __launch_bounds__(256, 3) conv_train_bf16_kernel(const ConvArgsT p) {
+    conv_train_body<BM, BN, WGM, WGN, KS, EPI, TMODE>(p);
+}
+
 // stem: fp32 image [N,H,W,3] -> bf16 [N,H,W,32]; fp32 arithmetic, HWIO fp32 weights (same as the fp32 stem)
 __global__ void __launch_bounds__(256) conv_stem_bf16_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ scale,
@@ -438,7 +714,133 @@ int dispatch_b(hipStream_t stream, const ConvArgsB& a) {
     return launch_b<128, 128, 2, 2, KS, UPCAT>(stream, a);
 }
 
+// The training forms (RouteKind::Bf16Train): the register-staged kernel at every shape, M tiles of 128 rows
+template <int BN, int WGM, int WGN, int KS, int EPI, bool TMODE>
+int launch_t(hipStream_t stream, const ConvArgsT& a) {
+    constexpr int BM = 128;
+    auto kern = conv_train_bf16_kernel<BM, BN, WGM, WGN, KS, EPI, TMODE>;
+    constexpr size_t tiles = (size_t)2 * (BM + BN) * LDB, stage = (size_t)64 * (BN + 4) * 4;
+    constexpr size_t lds = tiles > stage ? tiles : stage;
+    const int nbm = (a.M + BM - 1) / BM, nbn = (a.Cout + BN - 1) / BN;
+    hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(256), lds, stream, a);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
+template <int KS, int EPI, bool TMODE>
+int dispatch_t(hipStream_t stream, const ConvArgsT& a) {
+    if (a.Cout <= 32) return launch_t<32, 4, 1, KS, EPI, TMODE>(stream, a);
+    if (a.Cout <= 64) return launch_t<64, 4, 1, KS, EPI, TMODE>(stream, a);
+    return launch_t<128, 2, 2, KS, EPI, TMODE>(stream, a);
+}
+
+ConvArgsT args_t(const void* x, const void* w, void* y, int n, int h, int w_, int cin, int cout, int k, int stride, int pad,
+                 int ho, int wo, long long m) {
+    ConvArgsT a;
+    std::memset(&a, 0, sizeof(a));
+    a.x = static_cast<const bf16_t*>(x); a.w = static_cast<const bf16_t*>(w); a.y = y;
+    a.N = n; a.H = h; a.W = w_; a.Cin = cin; a.Cu = 0; a.Cx = cin;
+    a.Ho = ho; a.Wo = wo; a.Cout = cout; a.stride = stride; a.pad = pad;
+    a.M = (int)m;
+    (void)k;
+    return a;
+}
+
+// [tap'][Cin'/32][Cout'][32] of the data gradient's conv: Cin' = dz_stride (the reduction, zero past Cout), Cout' = Cin, the
+// kernel flipped (tap' = k*k-1 - tap)
+__global__ void pack_weights_bf16_dgrad_kernel(const float* __restrict__ w_hwio, bf16_t* __restrict__ w_packed, int taps,
+                                               int cin, int cout, int dzs) {
+    const size_t total = (size_t)taps * dzs * cin;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % BKB);
+        size_t r = i / BKB;
+        const int co = (int)(r % cin);
+        r /= cin;
+        const int cc = (int)(r % (dzs / BKB));
+        const int t = (int)(r / (dzs / BKB));
+        const int g = cc * BKB + c;            // channel of dz
+        w_packed[i] = g < cout ? f32_to_bf16(w_hwio[((size_t)(taps - 1 - t) * cin + co) * cout + g]) : (bf16_t)0;
+    }
+}
+
 }  // namespace
+
+int y3_conv_bf16_train_stats_blocks(const y3_conv_desc* d) {
+    const long long m = (long long)d->n * (d->h / d->stride) * (d->w / d->stride);
+    return (int)((m + 127) / 128);
+}
+
+// cin / cout: the channels the launch reads / writes (dgrad: it reads dz [n*ho*wo][cin], writes dx [n*h*w][cout])
+static int check_train(const char* who, const y3_conv_desc* d, int cin, int cout, bool dgrad = false) {
+    Y3_CHECK_ARG(d->k == 1 || (d->k == 3 && (d->stride == 1 || d->stride == 2)), "%s: kernel 1x1 or 3x3 (stride 1 or 2)", who);
+    Y3_CHECK_ARG(d->k == 3 || d->stride == 1, "%s: 1x1 conv must have stride 1", who);
+    Y3_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->c_up == 0 && (d->stride == 1 || (d->h % 2 == 0 && d->w % 2 == 0)),
+                 "%s: bad dimension", who);
+    Y3_CHECK_ARG(cin % BKB == 0 && cout % 4 == 0, "%s: the reduction needs a multiple of %d channels, the output of 4", who, BKB);
+    const long long px = (long long)d->n * d->h * d->w, px_out = px / (d->stride * d->stride);
+    Y3_CHECK_ARG((dgrad ? px_out : px) * cin < (1LL << 30) && (dgrad ? px : px_out) * cout < (1LL << 30),
+                 "%s: tensor exceeds 2^30 elements (32-bit byte offsets)", who);
+    return Y3_OK;
+}
+
+int y3_launch_conv_bf16_train(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* w, void* z, float* stats) {
+    Y3_CHECK_ARG(d && x && w && z && stats, "y3_launch_conv_bf16_train: null argument");
+    if (int rc = check_train("y3_launch_conv_bf16_train", d, d->cin, d->cout)) return rc;
+    const int ho = d->h / d->stride, wo = d->w / d->stride;
+    ConvArgsT a = args_t(x, w, z, d->n, d->h, d->w, d->cin, d->cout, d->k, d->stride, d->k / 2, ho, wo, (long long)d->n * ho * wo);
+    a.stats = stats;
+    return d->k == 1 ? dispatch_t<1, 1, false>(stream, a) : dispatch_t<3, 1, false>(stream, a);
+}
+
+int y3_launch_conv_bf16_reg(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* w, const float* scale,
+                            const float* shift, void* y, int out_f32) {
+    Y3_CHECK_ARG(d && x && w && scale && shift && y, "y3_launch_conv_bf16_reg: null argument");
+    if (int rc = check_train("y3_launch_conv_bf16_reg", d, d->cin, 4)) return rc;
+    const int ho = d->h / d->stride, wo = d->w / d->stride;
+    ConvArgsB a = args_t(x, w, y, d->n, d->h, d->w, d->cin, d->cout, d->k, d->stride, d->k / 2, ho, wo, (long long)d->n * ho * wo);
+    a.scale = scale; a.shift = shift; a.act = d->act; a.out_f32 = out_f32;
+    return d->k == 1 ? dispatch_b<1, false>(stream, a) : dispatch_b<3, false>(stream, a);
+}
+
+int y3_launch_conv_bf16_dgrad(hipStream_t stream, const y3_conv_desc* fwd, const void* dz, int dz_stride, const void* w_d,
+                              int accumulate, float* dx) {
+    Y3_CHECK_ARG(fwd && dz && w_d && dx, "y3_launch_conv_bf16_dgrad: null argument");
+    Y3_CHECK_ARG(dz_stride >= fwd->cout, "y3_launch_conv_bf16_dgrad: dz stride below Cout");
+    if (int rc = check_train("y3_launch_conv_bf16_dgrad", fwd, dz_stride, fwd->cin, true)) return rc;
+    const int ho = fwd->h / fwd->stride, wo = fwd->w / fwd->stride;
+    if (fwd->stride == 1) {
+        ConvArgsT a = args_t(dz, w_d, dx, fwd->n, ho, wo, dz_stride, fwd->cin, fwd->k, 1, fwd->k / 2, fwd->h, fwd->w,
+                             (long long)fwd->n * fwd->h * fwd->w);
+        a.acc = accumulate;
+        return fwd->k == 1 ? dispatch_t<1, 2, false>(stream, a) : dispatch_t<3, 2, false>(stream, a);
+    }
+    // four output parity classes, each a dense conv over the N*Ho*Wo rows of dz with 1 / 2 / 2 / 4 taps
+    for (int cls = 0; cls < 4; ++cls) {
+        ConvArgsT a = args_t(dz, w_d, dx, fwd->n, ho, wo, dz_stride, fwd->cin, 3, 1, 0, ho, wo, (long long)fwd->n * ho * wo);
+        a.acc = accumulate;
+        a.cy = cls >> 1; a.cx = cls & 1;
+        a.ntaps = (a.cy ? 2 : 1) * (a.cx ? 2 : 1);
+        if (int rc = dispatch_t<3, 2, true>(stream, a)) return rc;
+    }
+    return Y3_OK;
+}
+
+int y3_pack_conv_weights_bf16_reg(y3_ctx* ctx, const float* w_hwio, int k, int cin, int cout, int dgrad_stride, void* w_packed) {
+    Y3_CHECK_ARG(ctx && w_hwio && w_packed, "y3_pack_conv_weights_bf16_reg: null argument");
+    const int red = dgrad_stride ? dgrad_stride : cin;
+    Y3_CHECK_ARG(k > 0 && cin > 0 && cout > 0 && red % BKB == 0 && (!dgrad_stride || dgrad_stride >= cout),
+                 "y3_pack_conv_weights_bf16_reg: the reduction must be a positive multiple of %d", BKB);
+    const size_t total = (size_t)k * k * red * (dgrad_stride ? cin : cout);
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    if (dgrad_stride)
+        hipLaunchKernelGGL(pack_weights_bf16_dgrad_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w_hwio,
+                           static_cast<bf16_t*>(w_packed), k * k, cin, cout, dgrad_stride);
+    else
+        hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w_hwio,
+                           static_cast<bf16_t*>(w_packed), k * k, cin, cout);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
 
 int y3_launch_conv_bf16(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* x_up, const void* w,
                         const float* scale, const float* shift, const void* residual, void* y, int out_f32) {
@@ -506,4 +908,23 @@ extern "C" int y3_conv2d_fwd_bf16(y3_ctx* ctx, const y3_conv_desc* d, const void
                                   const float* scale, const float* shift, const void* residual, void* y, int out_f32) {
     Y3_CHECK_ARG(ctx, "y3_conv2d_fwd_bf16: null context");
     return y3_launch_conv_bf16(ctx->stream, d, x, x_up, w, scale, shift, residual, y, out_f32);
+}
+
+extern "C" int y3_pack_conv_weights_bf16_train(y3_ctx* ctx, const float* w_hwio, int k, int cin, int cout, int dgrad_stride,
+                                               void* w_packed) {
+    return y3_pack_conv_weights_bf16_reg(ctx, w_hwio, k, cin, cout, dgrad_stride, w_packed);
+}
+
+extern "C" int y3_conv_train_stats_blocks_bf16(const y3_conv_desc* fwd) { return fwd ? y3_conv_bf16_train_stats_blocks(fwd) : 0; }
+
+extern "C" int y3_conv2d_train_fwd_bf16(y3_ctx* ctx, const y3_conv_desc* fwd, const void* x, const void* w_packed, void* z,
+                                        float* stats) {
+    Y3_CHECK_ARG(ctx, "y3_conv2d_train_fwd_bf16: null context");
+    return y3_launch_conv_bf16_train(ctx->stream, fwd, x, w_packed, z, stats);
+}
+
+extern "C" int y3_conv2d_dgrad_bf16(y3_ctx* ctx, const y3_conv_desc* fwd, const void* dz, int dz_stride, const void* w_packed_d,
+                                    int accumulate, float* dx) {
+    Y3_CHECK_ARG(ctx, "y3_conv2d_dgrad_bf16: null context");
+    return y3_launch_conv_bf16_dgrad(ctx->stream, fwd, dz, dz_stride, w_packed_d, accumulate, dx);
 }

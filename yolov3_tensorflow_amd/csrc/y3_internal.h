@@ -108,6 +108,19 @@ int y3_launch_conv_dgrad(hipStream_t stream, const y3_conv_desc* fwd, const floa
                          void* workspace, size_t workspace_bytes, const y3_sk_opts* sk = nullptr);
 int y3_launch_conv_bf16(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* x_up, const void* w,
                         const float* scale, const float* shift, const void* residual, void* y, int out_f32);
+// bf16 train step (net dtype 1, RouteKind::Bf16Train): the register-staged bf16 kernel's training forms (y3_conv_bf16.hip),
+// its packings (dgrad_stride 0: the forward's [tap][Cin/32][Cout][32]; else the data gradient's, flipped, Cin' = dgrad_stride)
+// and the bf16 weight gradient (y3_wgrad_bf16.hip)
+int y3_conv_bf16_train_stats_blocks(const y3_conv_desc* d);
+int y3_launch_conv_bf16_train(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* w, void* z, float* stats);
+int y3_launch_conv_bf16_reg(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* w, const float* scale,
+                            const float* shift, void* y, int out_f32);
+int y3_launch_conv_bf16_dgrad(hipStream_t stream, const y3_conv_desc* fwd, const void* dz, int dz_stride, const void* w_d,
+                              int accumulate, float* dx);
+int y3_pack_conv_weights_bf16_reg(y3_ctx* ctx, const float* w_hwio, int k, int cin, int cout, int dgrad_stride, void* w_packed);
+int y3_launch_conv_wgrad_bf16(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* dz, int dz_stride, float* dw,
+                              void* scratch, size_t scratch_bytes);
+// (the bf16 BN / concat / conversion passes and the C-ABI forms of the above: include/yolo355.h)
 int y3_conv_bf16x_takes(int k, int cin);
 int y3_launch_pack_bf16x(hipStream_t stream, const float* w_hwio, int k, int cin, int cout, void* w_packed);
 int y3_launch_conv_bf16x(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* x_up, const void* w,

@@ -8,9 +8,10 @@
 // y3_net_set_dtype: exact fp32 MFMA | bf16 storage | fp32 from 3 / 2 bf16 planes (y3_conv_split.hip) | fp32 + Winograd kernels
 enum class NetDtype { F32 = 0, BF16 = 1, F32_BF16X6 = 2, F32_BF16X3 = 3, F32_WINO = 4 };
 
-// How a conv layer runs in one role, decided only by y3_route_* (y3_abi.hip).  InNext: inside the next layer's launch; the last
-// three: this launch also runs the layer before it.
-enum class RouteKind { Direct, Split, Wino, Wino44, Bf16, InNext, StemS2F32, StemS2Bf16, ResBlock64Bf16 };
+// How a conv layer runs in one role, decided only by y3_route_* (y3_abi.hip).  InNext: inside the next layer's launch; the
+// three after it: this launch also runs the layer before it.  Bf16Train: the bf16 train step's kernels (net dtype 1: the
+// register-staged bf16 kernel's training forms, y3_conv_bf16.hip; the weight gradient of y3_wgrad_bf16.hip).
+enum class RouteKind { Direct, Split, Wino, Wino44, Bf16, InNext, StemS2F32, StemS2Bf16, ResBlock64Bf16, Bf16Train };
 struct ConvRoute {
     RouteKind kind = RouteKind::Direct;
     int planes = 0;          // Split: 3 or 2
@@ -26,13 +27,16 @@ ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w);
 ConvRoute y3_route_wgrad(const y3_net& net, int i, int n, int h, int w);
 
 // The layout a launch reads a conv kernel in, implied by its route (y3_conv_pack, y3_abi.hip).  Hwio: the variable as it is
-// (the Cin = 3 stem in every dtype; the direct data gradient, which reads the kernel as [k*k][cin][dz_stride]).
-enum class Packing { Hwio, Direct, Bf16, Split, Wino, Wino44, Count };
+// (the Cin = 3 stem in every dtype; the direct data gradient, which reads the kernel as [k*k][cin][dz_stride]).  Bf16Reg: the
+// register-staged bf16 kernel's [tap][Cin/32][Cout][32] at every shape (Bf16Train; as the data gradient's: flipped, the channel
+// axes swapped, Cin' = dz_stride zero-extended).
+enum class Packing { Hwio, Direct, Bf16, Split, Wino, Wino44, Bf16Reg, Count };
 struct ConvPack {
     Packing kind = Packing::Hwio;
     int planes = 0;                  // Split: 3 or 2
     bool dgrad = false;              // the data gradient's packing: the kernel read as [k*k][cin][cout = dz_stride], axes swapped
     int k = 0, cin = 0, cout = 0;
+    int wcout = 0;                   // the variable's Cout (a data gradient's packing zero-extends it to cout)
     size_t bytes() const;            // of the packing (0 for Hwio: the launch reads the variable)
     int launch(y3_ctx* ctx, const float* w, void* out) const;   // writes the packing of w (nothing for Hwio)
 };

@@ -134,7 +134,13 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
         Y3_TRY(ctx_pending_error(ctx));     // (the conv launches below go to the launchers: refuse after a stream-K time-out)
         const long long in_rows = (long long)n * d.h * d.w;
         const float* xin = tptr(l.src);
-        if (l.up >= 0) {      // training materialises concat([upsample(up), route]) (model.py:61-62,71-72)
+        const bool b16 = r.kind == RouteKind::Bf16Train;     // (dtype 1: every layer but the stem; bf16 activations in all)
+        if (l.up >= 0 && net->dtype == NetDtype::BF16) {
+            const int cu = net->tensors[l.up].c, cx = net->tensors[l.src].c;
+            S.xin[i] = A.alloc((size_t)in_rows * (cu + cx) * 2);
+            Y3_TRY(y3_upsample_concat_bf16(ctx, tptr(l.up), cu, xin, cx, n, d.h, d.w, A.p(S.xin[i])));
+            xin = A.p(S.xin[i]);
+        } else if (l.up >= 0) {      // training materialises concat([upsample(up), route]) (model.py:61-62,71-72)
             const int cu = net->tensors[l.up].c, cx = net->tensors[l.src].c;
             Buf upt = A.alloc((size_t)in_rows * cu * 4);
             S.xin[i] = A.alloc((size_t)in_rows * (cu + cx) * 4);
@@ -145,8 +151,9 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
         }
         const int cout = l.cout, ho = d.h / l.stride, wo = d.w / l.stride;
         const long long rows = (long long)n * ho * wo;
-        const int nblk = (l.bn && r.kind != RouteKind::Split)
-            ? y3_conv_stats_blocks(&d, r.kind == RouteKind::Wino44 ? 2 : r.kind == RouteKind::Wino ? 1 : 0) : 0;
+        const int nblk = !l.bn || r.kind == RouteKind::Split ? 0
+                         : b16 ? y3_conv_bf16_train_stats_blocks(&d)
+                               : y3_conv_stats_blocks(&d, r.kind == RouteKind::Wino44 ? 2 : r.kind == RouteKind::Wino ? 1 : 0);
         Buf part = nblk ? A.alloc((size_t)nblk * 2 * cout * 4) : Buf();
         // the kernel in this step's packing (the variable changes every step)
         const ConvPack pk = y3_conv_pack(*net, (int)i, r);
@@ -161,7 +168,7 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
         // BN layers: the raw conv output z (with its column sums where the kernel has them); detection convs: bias, linear
         // (model.py:55-57)
         Buf& out = l.bn ? S.z[i] : S.tens[l.dst];
-        out = A.alloc((size_t)rows * cout * 4);
+        out = A.alloc((size_t)rows * cout * (b16 && l.bn ? 2 : 4));      // (dtype 1: z in bf16; the feature maps fp32)
         float* y = A.p(out);
         const float* shift = l.bn ? zeros : v.biases;
         y3_sk_opts so;
@@ -170,6 +177,10 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
         so.wino44_form = r.two_pass;
         hipStream_t s = dry ? nullptr : ctx->stream;
         switch (r.kind) {
+        case RouteKind::Bf16Train:
+            if (l.bn) Y3_TRY(y3_launch_conv_bf16_train(s, &d, xin, wdev, y, A.p(part)));
+            else Y3_TRY(y3_launch_conv_bf16_reg(s, &d, xin, wdev, ones, shift, y, 1));
+            break;
         case RouteKind::Wino44: Y3_TRY(y3_launch_conv_wino44(s, &d, xin, wdev, ones, shift, nullptr, y, skp, skb, &so)); break;
         case RouteKind::Wino: Y3_TRY(y3_launch_conv_wino(s, &d, xin, wdev, ones, shift, nullptr, y, skp, skb, &so)); break;
         case RouteKind::Split:
@@ -187,9 +198,15 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
                 Y3_TRY(y3_bn_train_stats(ctx, y, rows, cout, v.gamma, v.beta, BN_EPS, o->bn_decay, st, st + cout, st + 2 * cout,
                                          st + 3 * cout, v.moving_mean, v.moving_variance, A.p(S.reduce_sc)));
             A.release(part);
-            S.tens[l.dst] = A.alloc((size_t)rows * cout * 4);
-            Y3_TRY(y3_bn_apply_fwd(ctx, y, st + 2 * cout, st + 3 * cout, l.resid >= 0 ? tptr(l.resid) : nullptr, rows, cout, 1,
-                                   A.p(S.tens[l.dst])));
+            if (net->dtype == NetDtype::BF16) {      // (the stem's z is fp32)
+                S.tens[l.dst] = A.alloc((size_t)rows * cout * 2);
+                Y3_TRY(y3_bn_apply_fwd_bf16(ctx, y, !b16, st + 2 * cout, st + 3 * cout, l.resid >= 0 ? tptr(l.resid) : nullptr,
+                                            rows, cout, A.p(S.tens[l.dst])));
+            } else {
+                S.tens[l.dst] = A.alloc((size_t)rows * cout * 4);
+                Y3_TRY(y3_bn_apply_fwd(ctx, y, st + 2 * cout, st + 3 * cout, l.resid >= 0 ? tptr(l.resid) : nullptr, rows, cout, 1,
+                                       A.p(S.tens[l.dst])));
+            }
         }
         const int e = net->tensors[l.dst].ext;
         if (e >= 0) S.fm_tensor[e] = l.dst;
@@ -341,7 +358,30 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
         const float* w_d = v.weights;    // the kernel as the data gradient reads it: [k*k][cin][dz_stride]
         Buf w_d_buf;
         long long rows;
-        if (l.bn) {
+        // dtype 1 (all but the stem): dz in bf16, rounded once from the fp32 BN backward (or loss gradient); dy stays fp32
+        const bool b16 = S.routes[i].wgrad.kind == RouteKind::Bf16Train;
+        if (l.bn && b16) {
+            rows = (long long)n * (d.h / l.stride) * (d.w / l.stride);
+            if (l.resid >= 0 && needs(l.resid)) {
+                if (have[l.resid]) {
+                    if (int rc = accumulate_into(l.resid, A.p(dy), cout, 0, rows, cout)) return rc;
+                } else {
+                    grads[l.resid] = dy;
+                    own[l.resid] = own[dst];
+                    have[l.resid] = 1;
+                    dy_given_away = true;
+                }
+            }
+            dz_buf = A.alloc((size_t)rows * cout * 2);
+            Buf tmp;
+            float *dgam = gptr(v.g_gamma), *dbet = gptr(v.g_beta);
+            if (!trainable(v.g_gamma) || !trainable(v.g_beta)) tmp = A.alloc((size_t)2 * cout * 4);
+            const float* st = A.p(S.stats[i]);
+            Y3_TRY(y3_bn_train_bwd_bf16(ctx, A.p(S.z[i]), A.p(dy), v.gamma, st + 2 * cout, st + 3 * cout, st, st + cout, rows, cout,
+                                        dgam ? dgam : A.p(tmp), dbet ? dbet : A.p(tmp) + cout, A.p(dz_buf), A.p(S.bnbwd_sc)));
+            A.release(tmp);
+            dz_stride = cout;
+        } else if (l.bn) {
             rows = (long long)n * (d.h / l.stride) * (d.w / l.stride);
             dz_buf = dy;                 // BN backward runs in place ...
             if (l.resid >= 0 && needs(l.resid)) {
@@ -381,11 +421,16 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
                 Y3_TRY(y3_bias_grad(ctx, A.p(dy), rows, dz_stride, tmp, A.p(S.bias_sc)));
                 if (!dry) Y3_CHECK_HIP(hipMemcpyAsync(gptr(v.g_biases), tmp, (size_t)cout * 4, hipMemcpyDeviceToDevice, ctx->stream));
             }
-            dz_buf = dy;
-            // the data gradient reads the kernel as [k*k][cin][dz_stride]: zero-extend its last axis
-            w_d_buf = A.alloc((size_t)l.k * l.k * cin * dz_stride * 4);
-            Y3_TRY(y3_pad_channels(ctx, v.weights, cout, (long long)l.k * l.k * cin, dz_stride, A.p(w_d_buf)));
-            w_d = A.p(w_d_buf);
+            if (b16) {           // d loss / d fm, rounded once to bf16 (the bias gradient above read it in fp32)
+                dz_buf = A.alloc((size_t)rows * dz_stride * 2);
+                Y3_TRY(y3_f32_to_bf16(ctx, A.p(dy), rows * dz_stride, A.p(dz_buf)));
+            } else {
+                dz_buf = dy;
+                // the data gradient reads the kernel as [k*k][cin][dz_stride]: zero-extend its last axis
+                w_d_buf = A.alloc((size_t)l.k * l.k * cin * dz_stride * 4);
+                Y3_TRY(y3_pad_channels(ctx, v.weights, cout, (long long)l.k * l.k * cin, dz_stride, A.p(w_d_buf)));
+                w_d = A.p(w_d_buf);
+            }
         }
         const float* dz = A.p(dz_buf);
         const bool on_side = two && trainable(v.g_weights);
@@ -395,7 +440,10 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
                 Y3_CHECK_HIP(hipStreamWaitEvent(sctx->stream, S.ev_dz[flip], 0));
             }
             y3_ctx* wctx = on_side ? sctx : ctx;
-            if (S.routes[i].wgrad.kind == RouteKind::Wino)
+            if (b16)
+                Y3_TRY(y3_launch_conv_wgrad_bf16(wctx->stream, &d, xin, dz, dz_stride, gptr(v.g_weights), A.p(S.wgrad_sc),
+                                                 S.wgrad_sc.bytes));
+            else if (S.routes[i].wgrad.kind == RouteKind::Wino)
                 Y3_TRY(y3_conv_wgrad_wino(wctx, &d, xin, dz, dz_stride, gptr(v.g_weights), A.p(S.wgrad_sc), S.wgrad_sc.bytes));
             else
                 Y3_TRY(y3_conv_wgrad(wctx, &d, xin, dz, dz_stride, gptr(v.g_weights), A.p(S.wgrad_sc), S.wgrad_sc.bytes));
@@ -424,6 +472,7 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
             hipStream_t s = dry ? nullptr : ctx->stream;
             auto dgrad = [&](int acc, float* dx) -> int {     // (acc: the Winograd forms read dx as the residual, same thread)
                 switch (r.kind) {
+                case RouteKind::Bf16Train: Y3_TRY(y3_launch_conv_bf16_dgrad(s, &d, dz, dz_stride, A.p(wk), acc, dx)); break;
                 case RouteKind::Wino44:
                     Y3_TRY(y3_launch_conv_wino44(s, &g, dz, A.p(wk), ones, zeros, acc ? dx : nullptr, dx, skp, skb, &so)); break;
                 case RouteKind::Wino:
@@ -494,7 +543,6 @@ int check_common(const char* who, y3_net* net, int n, int h, int w) {
     Y3_CHECK_ARG(net, "%s: null net", who);
     Y3_CHECK_ARG(n > 0 && h > 0 && w > 0 && h % 32 == 0 && w % 32 == 0,
                  "%s: the batch must be positive and the input size a positive multiple of 32 (got %d x %dx%d)", who, n, h, w);
-    Y3_CHECK_ARG(net->dtype != NetDtype::BF16, "%s: the train step is fp32 (net dtype 0, 2, 3 or 4)", who);
     return Y3_OK;
 }
 
@@ -619,4 +667,11 @@ extern "C" int y3_net_train_saved(const y3_net* net, int layer, size_t* z_offset
     if (z_offset) *z_offset = S.z[layer].off;
     if (stats_offset) *stats_offset = S.stats[layer].off;
     return Y3_OK;
+}
+
+// 1: layer i's saved z (y3_net_train_saved) is bf16 (net dtype 1, every BN layer but the stem); 0: fp32
+extern "C" int y3_net_train_saved_type(const y3_net* net, int layer) {
+    if (!net || layer < 0 || layer >= (int)net->layers.size()) return 0;
+    const Layer& l = net->layers[layer];
+    return net->dtype == NetDtype::BF16 && l.bn && l.cin != 3 ? 1 : 0;
 }

@@ -233,6 +233,139 @@ __global__ void __launch_bounds__(256) bn_apply_bwd_kernel(const float* __restri
     }
 }
 
+// ---- the bf16 train step (net dtype 1): bf16 z / activations / dz, fp32 statistics and arithmetic ----------------
+__device__ __forceinline__ f32x4 ld_bf16x4(const unsigned short* p) {
+    const uint2 v = *reinterpret_cast<const uint2*>(p);
+    return f32x4{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u), __uint_as_float(v.y << 16),
+                 __uint_as_float(v.y & 0xFFFF0000u)};
+}
+__device__ __forceinline__ unsigned rne_bf16(float f) {   // round to nearest even (finite inputs)
+    unsigned u = __float_as_uint(f);
+    u += 0x7FFFu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+__device__ __forceinline__ void st_bf16x4(unsigned short* p, f32x4 v) {
+    *reinterpret_cast<uint2*>(p) = uint2{rne_bf16(v[0]) | (rne_bf16(v[1]) << 16), rne_bf16(v[2]) | (rne_bf16(v[3]) << 16)};
+}
+
+// y = leaky(z*scale + shift) (+ residual), rounded once to bf16; z bf16 (or fp32: the stem), residual bf16
+template <bool ZF32>
+__global__ void __launch_bounds__(256) bn_apply_fwd_bf16_kernel(const void* __restrict__ z, const float* __restrict__ scale,
+                                                                const float* __restrict__ shift,
+                                                                const unsigned short* __restrict__ resid, long long total4,
+                                                                int C4, int act, unsigned short* __restrict__ y) {
+    const f32x4* sc4 = reinterpret_cast<const f32x4*>(scale);
+    const f32x4* sh4 = reinterpret_cast<const f32x4*>(shift);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C4);
+        f32x4 v = ZF32 ? reinterpret_cast<const f32x4*>(z)[i] : ld_bf16x4(static_cast<const unsigned short*>(z) + 4 * i);
+        v = v * sc4[c] + sh4[c];
+        if (act) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = v[q] > 0.f ? v[q] : 0.1f * v[q];
+        }
+        if (resid) v += ld_bf16x4(resid + 4 * i);
+        st_bf16x4(y + 4 * i, v);
+    }
+}
+
+// col_reduce_kernel<1> over a bf16 z: (sum g', sum g'*zhat) partial rows [grid][2][C]
+__global__ void __launch_bounds__(256) bn_bwd_reduce_bf16_kernel(const unsigned short* __restrict__ z, const float* __restrict__ dy,
+                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                 const float* __restrict__ mean, const float* __restrict__ inv_std,
+                                                                 long long M, int C, float* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float red[];  // [rows_per_pass][2][C]
+    const int C4 = C >> 2;
+    const int lanes_per_row = C4 < 256 ? C4 : 256;
+    const int rows_per_pass = 256 / lanes_per_row;
+    const int cols_per_thread = (C4 + 255) / 256;
+    const int tl = threadIdx.x % lanes_per_row, tr = threadIdx.x / lanes_per_row;
+    for (int cc = 0; cc < cols_per_thread; ++cc) {
+        const int c4 = tl + cc * 256;
+        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+        if (c4 < C4 && tr < rows_per_pass) {
+            const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * c4);
+            const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + 4 * c4);
+            const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + 4 * c4);
+            const f32x4 is = *reinterpret_cast<const f32x4*>(inv_std + 4 * c4);
+            for (long long r = (long long)blockIdx.x * rows_per_pass + tr; r < M; r += (long long)gridDim.x * rows_per_pass) {
+                const f32x4 v = ld_bf16x4(z + r * C + 4 * c4);
+                f32x4 g = *reinterpret_cast<const f32x4*>(dy + r * C + 4 * c4);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float u = v[q] * sc[q] + sh[q];
+                    g[q] = u > 0.f ? g[q] : 0.1f * g[q];
+                }
+                s0 += g;
+                s1 += g * ((v - mu) * is);
+            }
+        }
+        __syncthreads();
+        if (c4 < C4 && tr < rows_per_pass) {
+            *reinterpret_cast<f32x4*>(red + ((size_t)tr * 2 + 0) * C + 4 * c4) = s0;
+            *reinterpret_cast<f32x4*>(red + ((size_t)tr * 2 + 1) * C + 4 * c4) = s1;
+        }
+        __syncthreads();
+        if (c4 < C4 && tr == 0) {
+            for (int k = 1; k < rows_per_pass; ++k) {
+                s0 += *reinterpret_cast<const f32x4*>(red + ((size_t)k * 2 + 0) * C + 4 * c4);
+                s1 += *reinterpret_cast<const f32x4*>(red + ((size_t)k * 2 + 1) * C + 4 * c4);
+            }
+            *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * C + 4 * c4) = s0;
+            *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * C + 4 * c4) = s1;
+        }
+    }
+}
+
+// bn_apply_bwd_kernel with a bf16 z and a bf16 dz (rounded once)
+__global__ void __launch_bounds__(256) bn_apply_bwd_bf16_kernel(const unsigned short* __restrict__ z, const float* __restrict__ dy,
+                                                                const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                const float* __restrict__ mean, const float* __restrict__ inv_std,
+                                                                const float* __restrict__ coef, long long total4, int C4,
+                                                                unsigned short* __restrict__ dz) {
+    const int C = C4 * 4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C4) * 4;
+        const f32x4 v = ld_bf16x4(z + 4 * i);
+        const f32x4 g = reinterpret_cast<const f32x4*>(dy)[i];
+        f32x4 out;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float u = v[q] * scale[c + q] + shift[c + q];
+            const float gp = u > 0.f ? g[q] : 0.1f * g[q];
+            const float zh = (v[q] - mean[c + q]) * inv_std[c + q];
+            out[q] = coef[c + q] * (gp - coef[C + c + q] - zh * coef[2 * C + c + q]);
+        }
+        st_bf16x4(dz + 4 * i, out);
+    }
+}
+
+// out [n,h,w,cu+cx] = concat(upsample2x(up [n,h/2,w/2,cu]), x [n,h,w,cx]), all bf16 (exact copies), 8 bytes per thread
+__global__ void __launch_bounds__(256) upsample_concat_bf16_kernel(const unsigned short* __restrict__ up, int cu,
+                                                                   const unsigned short* __restrict__ x, int cx, int h, int w,
+                                                                   long long total4, unsigned short* __restrict__ out) {
+    const int c4 = (cu + cx) / 4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const long long pix = i / c4;
+        const int c = (int)(i - pix * c4) * 4;
+        uint2 v;
+        if (c < cu) {
+            const int xx = (int)(pix % w), yy = (int)((pix / w) % h);
+            const long long n = pix / ((long long)w * h);
+            v = *reinterpret_cast<const uint2*>(up + ((n * (h / 2) + yy / 2) * (w / 2) + xx / 2) * cu + c);
+        } else {
+            v = *reinterpret_cast<const uint2*>(x + pix * cx + (c - cu));
+        }
+        *reinterpret_cast<uint2*>(out + 4 * i) = v;
+    }
+}
+
+__global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restrict__ src, long long total4,
+                                                          unsigned short* __restrict__ dst) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256)
+        st_bf16x4(dst + 4 * i, reinterpret_cast<const f32x4*>(src)[i]);
+}
+
 // ---- backward routing ----------------------------------------------------------------------------------
 // dx[n,y,x,c] (+)= sum over the 2x2 block of g[n,2y+dy,2x+dx, c]   (g has row stride gC channels)
 __global__ void __launch_bounds__(256) upsample2x_bwd_kernel(const float* __restrict__ g, int gC, int n, int h,
@@ -1034,6 +1167,69 @@ extern "C" int y3_process_box(y3_ctx* ctx, const float* boxes, const int32_t* la
         Y3_CHECK_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(target_assign_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, a);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
+// ---- the bf16 train step's passes (y3_internal.h) ---------------------------------------------------------------------
+extern "C" int y3_bn_apply_fwd_bf16(y3_ctx* ctx, const void* z, int z_f32, const float* scale, const float* shift, const void* residual,
+                         long long rows, int c, void* y) {
+    Y3_CHECK_ARG(ctx && z && scale && shift && y, "y3_bn_apply_fwd_bf16: null argument");
+    Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_apply_fwd_bf16: bad shape");
+    const long long total4 = rows * (c / 4);
+    auto r = static_cast<const unsigned short*>(residual);
+    auto o = static_cast<unsigned short*>(y);
+    if (z_f32)
+        hipLaunchKernelGGL(bn_apply_fwd_bf16_kernel<true>, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, z, scale, shift, r,
+                           total4, c / 4, 1, o);
+    else
+        hipLaunchKernelGGL(bn_apply_fwd_bf16_kernel<false>, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, z, scale, shift, r,
+                           total4, c / 4, 1, o);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
+extern "C" int y3_bn_train_bwd_bf16(y3_ctx* ctx, const void* z, const float* dy, const float* gamma, const float* scale, const float* shift,
+                         const float* mean, const float* inv_std, long long rows, int c, float* dgamma, float* dbeta, void* dz,
+                         float* scratch) {
+    Y3_CHECK_ARG(ctx && z && dy && gamma && scale && shift && mean && inv_std && dz && scratch, "y3_bn_train_bwd_bf16: null argument");
+    Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_train_bwd_bf16: bad shape");
+    auto zb = static_cast<const unsigned short*>(z);
+    const int C4 = c / 4;
+    const int lanes_per_row = C4 < 256 ? C4 : 256;
+    const int rows_per_pass = 256 / lanes_per_row;
+    long long nb = (rows + rows_per_pass - 1) / rows_per_pass;
+    nb = nb > RED_BLOCKS ? RED_BLOCKS : nb < 1 ? 1 : nb;
+    hipLaunchKernelGGL(bn_bwd_reduce_bf16_kernel, dim3((int)nb), dim3(256), (size_t)rows_per_pass * 2 * c * sizeof(float),
+                       ctx->stream, zb, dy, scale, shift, mean, inv_std, rows, c, scratch);
+    Y3_CHECK_HIP(hipGetLastError());
+    float* coef = scratch + (size_t)RED_BLOCKS * 2 * c;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, scratch, (int)nb, c, (double)rows, gamma, inv_std,
+                       dbeta, dgamma, coef);
+    Y3_CHECK_HIP(hipGetLastError());
+    const long long total4 = rows * C4;
+    hipLaunchKernelGGL(bn_apply_bwd_bf16_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, zb, dy, scale, shift, mean,
+                       inv_std, coef, total4, C4, static_cast<unsigned short*>(dz));
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
+extern "C" int y3_upsample_concat_bf16(y3_ctx* ctx, const void* up, int cu, const void* x, int cx, int n, int h, int w, void* out) {
+    Y3_CHECK_ARG(ctx && up && x && out, "y3_upsample_concat_bf16: null argument");
+    Y3_CHECK_ARG(n > 0 && h % 2 == 0 && w % 2 == 0 && cu % 4 == 0 && cx % 4 == 0, "y3_upsample_concat_bf16: bad shape");
+    const long long total4 = (long long)n * h * w * ((cu + cx) / 4);
+    hipLaunchKernelGGL(upsample_concat_bf16_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream,
+                       static_cast<const unsigned short*>(up), cu, static_cast<const unsigned short*>(x), cx, h, w, total4,
+                       static_cast<unsigned short*>(out));
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
+extern "C" int y3_f32_to_bf16(y3_ctx* ctx, const float* src, long long count, void* dst) {
+    Y3_CHECK_ARG(ctx && src && dst && count > 0 && count % 4 == 0, "y3_f32_to_bf16: bad argument");
+    const long long total4 = count / 4;
+    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, src, total4,
+                       static_cast<unsigned short*>(dst));
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }

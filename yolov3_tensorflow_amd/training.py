@@ -96,8 +96,9 @@ def _train_state(model):
     return st
 
 
-# y3_net dtype codes of the compute modes the train step accepts (model.NET_DTYPES without bf16 storage)
-_TRAIN_DTYPES = {'f32': 0, 'f32_bf16x6': 2, 'f32_bf16x3': 3, 'f32_wino': 4}
+# y3_net dtype codes of the compute modes the train step accepts (bf16: mixed precision, bf16 tensors and products with fp32
+# statistics, gradients, variables and optimizer; include/yolo355.h, train-step block)
+_TRAIN_DTYPES = {'f32': 0, 'bf16': 1, 'f32_bf16x6': 2, 'f32_bf16x3': 3, 'f32_wino': 4}
 
 
 def _train_net(model, ctx, dev=None):
@@ -406,7 +407,8 @@ class Trainer(object):
                 continue
             sd = topo.tensors[l['dst']]['sdiv']
             cout = l['cout']
-            z = ws[zo.value:zo.value + n * (h // sd) * (w // sd) * cout * 4].view(torch.float32).view(n, h // sd, w // sd, cout)
+            zt, ze = (torch.bfloat16, 2) if L.y3_net_train_saved_type(st['net'], i) == 1 else (torch.float32, 4)
+            z = ws[zo.value:zo.value + n * (h // sd) * (w // sd) * cout * ze].view(zt).view(n, h // sd, w // sd, cout)
             stats = ws[so.value:so.value + 4 * cout * 4].view(torch.float32).view(4, cout)
             self.capture.append(dict(layer=i, z=z, stats=stats))
 
