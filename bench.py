@@ -1,12 +1,17 @@
 #!/usr/bin/env python
 """bench.py — the YOLOv3 hot path on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|c5|feeder] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|c5|feeder] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` with N > 1 and no launcher environment re-executes itself under torch.distributed.run
 (one rank per GPU, rendezvous on 127.0.0.1).
+
+A plain run does only what its headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, and the result line
+(`value`, `ms_per_step` and the `roofline` computed from the per-layer events of the timed steps).  Everything that takes
+runs of its own - ms_per_image_p50, fast_path / direct_path, box_delta_vs_oracle, cpu_baseline, the secondary objects
+detect / c5 / c4 / feeder of the c2 line, and c4's `fed` - runs only with --full.
 
 Workloads
   c2 (default; BASELINE.json configs[1], the metric): Darknet-53 + 3-scale head forward (75 fused conv launches) on a
@@ -16,8 +21,8 @@ Workloads
      of the elapsed time.
   c4 (configs[3]): one TRAIN step — forward(is_training) -> compute_loss -> backward -> bucketed RCCL all-reduce of the
      gradients (overlapped with backward) -> clip -> SGD update of the whole model — at 416x416, bs=64 per GPU.  `value` is
-     measured on resident synthetic tensors; `fed` repeats the steps with the batches coming from the feeder (JPEG decode,
-     the reference's augmentation chain, resize, upload, target assignment under the steps).
+     measured on resident synthetic tensors; `fed` (--full) repeats the steps with the batches coming from the feeder (JPEG
+     decode, the reference's augmentation chain, resize, upload, target assignment under the steps).
   c5 (configs[4]): the c2 forward with bf16 storage at 608x608, bs=16 per GPU.
   feeder: the host side of c4 alone - one feeder per rank (10 worker threads, prefetch 5: the reference's defaults) decoding
      synthetic JPEGs, augmenting, resizing to 416x416 and uploading bs=64 batches that nothing consumes (run_feeder).
@@ -39,6 +44,8 @@ measured with hipEvents recorded on the launch stream inside the timed region; `
 needs 2.25x / 4x fewer multiplies).  `whole_forward_frac` = sum over the 75 layers of max(bytes / 8 TB/s, issued FLOPs /
 157.3 TF/s), divided by the measured ms_per_step.  `traffic`: fabric-side bytes per launch from a committed rocprofv3
 --pmc pass, reported only when that pass was taken on the kernel sources of this build.
+With --full:
+ms_per_image_p50: after the timed region, the median of up to 10 single forwards, each synchronised, per image.
 fast_path / direct_path: after the timed region the same steps are repeated with other compute_dtypes and reported next
 to `value` with the max deviation between the feature maps.  Never `value`.
 cpu_baseline: the CPU oracle's torch-fp32 restatement of the same graph ("port"; the literal TF-CPU reference cannot run
@@ -407,13 +414,17 @@ def parse_args(argv):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--warmup', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help="after the timed steps also measure and check what the headline figure does not need: "
+                         "ms_per_image_p50, fast_path / direct_path, box_delta_vs_oracle, cpu_baseline and the secondary "
+                         "objects detect / c5 / c4 / feeder (c2), the steps on batches from the feeder (c4: `fed`)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help="with --full: skip cpu_baseline")
     ap.add_argument('--streams', type=int, default=2,
                     help="HIP streams per GPU for the inference workloads (c2, c5, detect): the batch runs as that many equal "
                          "parts, one per stream (model.inference_streams; forwards with per-layer events on stay on one stream)")
     ap.add_argument('--no-secondary', action='store_true',
-                    help="c2 only: skip the secondary objects (fast_path / direct_path, detect, c5, c4, feeder) measured after the "
-                         "timed region of `value`")
+                    help="c2 with --full: skip the secondary objects (fast_path / direct_path, detect, c5, c4, feeder) "
+                         "measured after the timed region of `value`")
     ap.add_argument('--workload', choices=['c2', 'c4', 'c5', 'feeder'], default='c2',
                     help="c2 (default, the BASELINE metric): fp32 forward 416x416 bs=32; c4: train step 416x416 bs=64 "
                          "per GPU, SGD, RCCL gradient all-reduce; c5: bf16-storage forward 608x608 bs=16; feeder: the "
@@ -427,7 +438,8 @@ def parse_args(argv):
     ap.add_argument('--batch', type=int, default=None, help="per-GPU batch (default: the workload's BASELINE value)")
     ap.add_argument('--wgrad-stream', type=int, choices=[0, 1], default=None,
                     help="c4: backward's weight gradients on a second stream (1) or on the main one (0); default: the package's")
-    ap.add_argument('--no-fed', action='store_true', help="c4: skip the repetition of the steps on batches from the feeder")
+    ap.add_argument('--no-fed', action='store_true', help="c4 with --full: skip the repetition of the steps on batches from "
+                                                          "the feeder")
     ap.add_argument('--head-only', action='store_true', help="c4: update only yolov3/yolov3_head (the reference's "
                                                              "default update_part) instead of the whole model")
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -504,7 +516,7 @@ def main(argv=None):
         out = run_feeder(args, y3, torch, dist, rank, world, distributed, barrier, max_over_ranks)
     else:
         out = run_forward(args, y3, torch, dist, rank, world, distributed, barrier, max_over_ranks)
-    if args.workload == 'c2' and not args.no_secondary and args.batch is None:
+    if args.workload == 'c2' and args.full and not args.no_secondary and args.batch is None:
         # The other BASELINE configurations, measured by the same (driver-run) command AFTER the timed region of `value`
         # and never part of it: detect = forward + decode + gpu_nms (what test_single_image.py / eval.py run), c5 =
         # configs[4] (608x608 bf16 bs=16), c4 = configs[3] (train step, bs=64 per GPU, RCCL all-reduce when N > 1).
@@ -779,9 +791,9 @@ def run_train(args, y3, torch, dist, rank, world, distributed, barrier, max_over
         loss0 = float(loss[0])
         assert np.isfinite(loss0), "non-finite loss"
         # the same steps with the batches coming from the feeder (decode + augmentation + resize + upload + target assignment
-        # under the steps): never `value`, reported beside it
+        # under the steps): never `value`, reported beside it (--full)
         fed = None
-        if not args.no_fed:
+        if args.full and not args.no_fed:
             try:
                 fed = fed_train_steps(args, trainer, torch, rank, barrier, max_over_ranks)
             except Exception as e:      # the fed repetition must never cost the resident measurement
@@ -942,19 +954,20 @@ def run_forward(args, y3, torch, dist, rank, world, distributed, barrier, max_ov
         layer_ms, table = model.read_layer_ms()
         is_sk = model.layer_is_streamk(BATCH, SIZE, SIZE)
         model.set_layer_profiling(False)
-        # p50 of single-step latency (separate short loop; each step synchronised)
+        # p50 of single-step latency (--full: separate short loop; each step synchronised)
         lat = []
-        for _ in range(min(args.steps, 10)):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            model.forward(x, False)
-            torch.cuda.synchronize()
-            lat.append(time.perf_counter() - t1)
+        if args.full:
+            for _ in range(min(args.steps, 10)):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                model.forward(x, False)
+                torch.cuda.synchronize()
+                lat.append(time.perf_counter() - t1)
     assert all(torch.isfinite(f).all().item() for f in fms), "non-finite feature maps"
 
-    # Secondary measurements (c2, default precision only; outside the timed region above and never `value`)
+    # Secondary measurements (--full, c2, default precision only; outside the timed region above and never `value`)
     fast, direct = None, None
-    if not bf16 and not split and not args.no_secondary:
+    if args.full and not bf16 and not split and not args.no_secondary:
         primary = model.compute_dtype
         for key, dtype in (('fast', 'f32_bf16x6'), ('direct', 'f32')):
             if dtype == primary:
@@ -1025,7 +1038,7 @@ def run_forward(args, y3, torch, dist, rank, world, distributed, barrier, max_ov
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4),
-        "ms_per_image_p50": round(float(np.median(lat)) * 1e3 / BATCH, 4),
+        **({"ms_per_image_p50": round(float(np.median(lat)) * 1e3 / BATCH, 4)} if lat else {}),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1074,12 +1087,12 @@ def run_forward(args, y3, torch, dist, rank, world, distributed, barrier, max_ov
     out["per_rank_ms_per_step"] = rank_ms          # every rank's own timed region (value uses the slowest)
     if dump is not None:
         out["dump_outputs"] = dump
-    if world == 1 and not bf16 and not getattr(args, 'secondary', False):      # checker work: N = 1 only
+    if args.full and world == 1 and not bf16 and not getattr(args, 'secondary', False):      # checker work: N = 1 only
         try:
             out["box_delta_vs_oracle"] = box_delta_vs_oracle(model, y3, x, fms)
         except Exception as e:      # a checker must never cost the line
             out["box_delta_vs_oracle"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if world == 1 and not args.no_cpu_baseline and not bf16:
+    if args.full and world == 1 and not args.no_cpu_baseline and not bf16:
         out["cpu_baseline"] = cpu_baseline(y3.global_variables(scope='yolov3'))
     return out
 

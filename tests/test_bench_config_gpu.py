@@ -148,3 +148,30 @@ def test_hip_conv_agrees_with_miopen(k, stride, cin, cout):
         got = engine.conv2d_fwd_wino(x, engine.pack_wino(wt), scale, shift, cout, True).cpu().numpy()
         err = np.abs(got - want)
         assert (err <= 1e-4 * (1 + np.abs(want))).all(), 'Winograd kernel vs MIOpen: max err %.3e' % err.max()
+
+
+def test_plain_bench_run_reports_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the timed steps, the dump and one result line with the
+    headline fields and the `roofline` of the timed steps' own events - and nothing that takes runs of its own (the p50
+    loop, the other precisions, the oracle check, the CPU baseline, the secondary workloads: those are --full's)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                          '--dump-outputs', str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-3000:]
+    line = json.loads(out.stdout.decode().strip().splitlines()[-1])
+    assert line['unit'] == 'images/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert line['steps'] == 2 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+    assert line['roofline']['achieved'] > 0 and 'library' in line
+    for key in ('ms_per_image_p50', 'fast_path', 'direct_path', 'box_delta_vs_oracle', 'cpu_baseline',
+                'detect', 'c5', 'c4', 'feeder'):
+        assert key not in line, key
+    assert sorted(line['dump_outputs']['files']) == sorted(os.listdir(tmp_path)) == \
+        ['feature_map_%d.npy' % k for k in (1, 2, 3)]

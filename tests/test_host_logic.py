@@ -336,3 +336,20 @@ def test_bench_reports_traffic_only_from_a_profile_of_this_build(tmp_path, monke
     val, src = bench.traffic_from_profile(['old.json'])
     assert val is None and 'old.json' in src
     assert bench.traffic_from_profile(['does_not_exist.json']) == (None, None)
+
+
+def test_bench_measures_beyond_the_headline_only_with_full():
+    """A plain bench.py run does only what its headline figure needs; --full (off by default) adds the rest and leaves
+    --steps / --warmup alone.  The skips of the extras (--no-secondary, --no-cpu-baseline, --no-fed) still parse."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '3'])
+    assert not plain.full and (plain.steps, plain.warmup) == (7, 3)
+    full = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '3', '--full'])
+    assert full.full and (full.steps, full.warmup) == (7, 3)
+    c4 = bench.parse_args(['--workload', 'c4', '--full', '--no-fed', '--no-secondary', '--no-cpu-baseline'])
+    assert c4.full and c4.no_fed and (c4.steps, c4.warmup) == (5, 2)
+    assert not bench.parse_args(['--workload', 'c4']).full

@@ -43,7 +43,7 @@ def main():
         "algorithmic_bytes_per_launch": int(float(algo)),
         "dispatches_counted": len(fv),
         "note": "fabric-side (L2 miss) traffic; Infinity-Cache hits are included, so this is an upper bound on HBM "
-                "bytes.  Collected in separate --pmc passes (FETCH_SIZE, then WRITE_SIZE) over `bench.py --steps 3 "
+                "bytes.  Collected in separate --pmc passes (FETCH_SIZE, then WRITE_SIZE) over `bench.py --full --steps 3 "
                 "--warmup 1 --no-cpu-baseline`, mean over the full-size dispatches.",
         "all_kernels": {c: {k: {"dispatches": len(v), "mean_kb": round(sum(v) / len(v), 1)} for k, v in d.items()}
                         for c, d in (("FETCH_SIZE", fetch), ("WRITE_SIZE", write))},

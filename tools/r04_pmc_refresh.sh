@@ -10,6 +10,6 @@ python tools/pmc_traffic_layers.py $O/pmc_layers.json conv_wino $O/pmc_traffic_w
 python tools/pmc_layers_summary.py $O/pmc_layers_c5.json $O/pmc_mem_c5/p_counter_collection.csv > $O/pmc_layers_c5.txt 2>&1
 python tools/pmc_traffic_layers.py $O/pmc_layers_c5.json conv_bf16x,conv_bf16p $O/pmc_traffic_bf16.json
 cp $O/pmc_traffic_wino.json profiles/r04_pmc_traffic_wino.json; cp $O/pmc_traffic_bf16.json profiles/r04_pmc_traffic_bf16.json
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 rm -rf $O/pmc_mem $O/pmc_sq $O/pmc_mem_c5
 python -c "import json; d=json.load(open('$O/bench_n1.json')); print(d['value'], d['roofline']['traffic'], d['roofline']['traffic_source'][:80])"
