@@ -539,6 +539,17 @@ struct y3f_djob;
 int y3_feed_run(y3_ctx* ctx, const void* blob_dev, const struct y3f_djob* jobs_host, int n, const void* tables_dev,
                 void* scratch_dev, size_t scratch_bytes, float* out, int out_h, int out_w);
 
+/* The device half of the feeder's JPEG decoder (include/yolo355_jpeg.h).  liby3feed.so's y3f_jpeg_plan wrote n files into
+ * one blob; the caller uploads it and passes its device address and size, the host copy of the n y3j_rec records at its
+ * start, a scratch of >= the plan's scratch bytes and an output of >= its output bytes.  Every record's extents are checked
+ * against the three sizes before anything is launched.  Each image is written as packed uint8 RGB HWC at its record's
+ * out_off: the bytes Pillow's Image.open(f).convert('RGB') gives.  status_dev: n x 2 int32, per image a status (0: good;
+ * else bits: 1 invalid Huffman code, 2 data overrun, 4 wrong block count, 8 no synchronisation) and the number of
+ * synchronisation rounds the entropy decoder took.  Asynchronous on the context's stream. */
+struct y3j_rec;
+int y3_jpeg_decode(y3_ctx* ctx, const void* blob_dev, size_t blob_bytes, const struct y3j_rec* recs_host, int n,
+                   void* scratch_dev, size_t scratch_bytes, void* out_dev, size_t out_bytes, int* status_dev);
+
 /* box_iou (model.py:307-345): pred_boxes [num_pred][4], true_boxes [num_true][4], both (cx,cy,w,h);
  * iou [num_pred][num_true] = inter / (area_p + area_t - inter + 1e-10). */
 int y3_box_iou(y3_ctx* ctx, const float* pred_boxes, long long num_pred, const float* true_boxes, int num_true,

@@ -35,6 +35,7 @@ SOURCES = [
     ("y3_wgrad_bf16.hip", []),
     ("y3_wgrad_wino.hip", []),
     ("y3_feed_gpu.hip", ["-ffp-contract=off"]),
+    ("y3_jpeg.hip", []),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -42,17 +43,19 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 # liby3feed.so: host code (include/yolo355_feed.h).  No FMA contraction and no fast-math: it reproduces numpy's float32
 # loops and Pillow's C arithmetic bit for bit.  Baseline x86-64 only (the file is built here and runs on the GPU box).
 FEED_SRC = os.path.join(CSRC, "y3_feed.cpp")
+JPEG_SRC = os.path.join(CSRC, "y3_jpeg.cpp")          # the JPEG decoder's host half (include/yolo355_jpeg.h)
 FEED_LIB = os.path.join(CSRC, "liby3feed.so")
 FEED_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-Wall",
               "-Wno-format-truncation"]
 
 
 def build_feed(force=False, verbose=True):
-    deps = [FEED_SRC, os.path.join(HERE, "..", "include", "yolo355_feed.h")]
+    deps = [FEED_SRC, JPEG_SRC, os.path.join(HERE, "..", "include", "yolo355_feed.h"),
+            os.path.join(HERE, "..", "include", "yolo355_jpeg.h")]
     if not force and os.path.exists(FEED_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(FEED_LIB) for d in deps):
         return FEED_LIB
     tmp = FEED_LIB + ".%d.tmp" % os.getpid()         # (several feeder workers may get here at once: rename is atomic)
-    cmd = [os.environ.get("CXX", "g++")] + FEED_FLAGS + [FEED_SRC, "-o", tmp]
+    cmd = [os.environ.get("CXX", "g++")] + FEED_FLAGS + [FEED_SRC, JPEG_SRC, "-o", tmp]
     if verbose:
         print(" ".join(cmd), flush=True)
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
@@ -90,6 +93,8 @@ def needs_build():
         os.path.join(CSRC, "y3_conv_common.h"),
         os.path.join(CSRC, "y3_net.h"),
         os.path.join(CSRC, "y3_feed_px.h"),
+        os.path.join(CSRC, "y3_jpeg_px.h"),
+        os.path.join(HERE, "..", "include", "yolo355_jpeg.h"),
         os.path.join(HERE, "..", "include", "yolo355_feed.h"),
         os.path.join(HERE, "..", "include", "yolo355.h"),
         os.path.abspath(__file__),

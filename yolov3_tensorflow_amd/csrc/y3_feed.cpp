@@ -764,6 +764,15 @@ void parallel_jobs(int n, int threads, F work) {
 
 }  // namespace
 
+// the y3f_last_error channel for the library's other translation unit (y3_jpeg.cpp)
+__attribute__((visibility("hidden"))) int y3f_fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof(g_error), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
 extern "C" {
 
 int y3f_plan_batch(const y3f_job* jobs, int n, uint8_t* blob, size_t capacity, size_t* blob_bytes, size_t* scratch_bytes,
