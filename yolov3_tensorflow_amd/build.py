@@ -91,6 +91,7 @@ def needs_build():
     deps = [os.path.join(CSRC, s) for s, _ in SOURCES] + [
         os.path.join(CSRC, "y3_internal.h"),
         os.path.join(CSRC, "y3_conv_common.h"),
+        os.path.join(CSRC, "y3_bf16.h"),
         os.path.join(CSRC, "y3_net.h"),
         os.path.join(CSRC, "y3_feed_px.h"),
         os.path.join(CSRC, "y3_jpeg_px.h"),

@@ -18,11 +18,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
-#include "y3_internal.h"
+#include "y3_bf16.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -72,12 +71,6 @@ constexpr unsigned OOB = 0x80000000u;
 // flipped by (row/4)%4 and 16 consecutive rows of one logical slot land on 16 different bank groups.
 __device__ __forceinline__ int lds_off(int row, int slot) { return row * LDB + ((slot ^ ((row >> 2) & 3)) << 4); }
 
-__device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ bf16_t f32_to_bf16(float f) {   // round to nearest even (finite inputs)
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
 
 template <int BM, int BN, int WGM, int WGN, int KS, bool UPCAT>
 __global__ void __launch_bounds__(256, 3) conv_mfma_bf16_kernel(const ConvArgsB p) {

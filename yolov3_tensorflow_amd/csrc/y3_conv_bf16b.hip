@@ -19,14 +19,11 @@
 //            the pixels of phase 2; the shortcut is read from the patch (the tile's own pixels) BEFORE the patch buffer is
 //            reused to stage the output, so that an output pixel's 128 bytes leave as eight 16-byte pieces of one line.
 #include <cstdlib>
-#include "y3_internal.h"
+#include "y3_bf16.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -63,11 +60,6 @@ constexpr int LDS_BYTES = 2 * A_BYTES + M_BYTES + W3_BYTES + CONST_BYTES;
 constexpr int NTHR = 512, NW = 8;
 constexpr int DPW = (NDMA + NW - 1) / NW;       // DMA instructions per wave and tile (6; the last ones of some waves are dead)
 constexpr int OPITCH = 144;                     // staged output row: 128 bytes + 16 (bank spread)
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-    return __builtin_bit_cast(unsigned, v);
-}
 
 __global__ void __launch_bounds__(NTHR) conv_resblock64_bf16_kernel(const ResBlockArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -167,7 +159,7 @@ __global__ void __launch_bounds__(NTHR) conv_resblock64_bf16_kernel(const ResBlo
                     const float t = acc[4 * g + e] * sc2[g][e] + sh2[g][e];
                     o[e] = p.act2 ? fmaxf(t, 0.1f * t) : t;
                 }
-                const unsigned lo = pack_bf16(o[0], o[1]), hi = pack_bf16(o[2], o[3]);
+                const unsigned lo = cvt_pack_bf16(o[0], o[1]), hi = cvt_pack_bf16(o[2], o[3]);
                 if (pix < NPIX)
                     *reinterpret_cast<u32x2*>(dst + ((g ^ msw) << 4)) = u32x2{inside ? lo : 0u, inside ? hi : 0u};
             }
@@ -236,7 +228,8 @@ __global__ void __launch_bounds__(NTHR) conv_resblock64_bf16_kernel(const ResBlo
                 o[1] += __uint_as_float(res[rt][g][0] & 0xFFFF0000u);
                 o[2] += __uint_as_float(res[rt][g][1] << 16);
                 o[3] += __uint_as_float(res[rt][g][1] & 0xFFFF0000u);
-                *reinterpret_cast<u32x2*>(out + l32 * OPITCH + ch * 2) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+                *reinterpret_cast<u32x2*>(out + l32 * OPITCH + ch * 2) =
+                    u32x2{cvt_pack_bf16(o[0], o[1]), cvt_pack_bf16(o[2], o[3])};
             }
         // (one wave: its LDS operations execute in order)
 #pragma unroll

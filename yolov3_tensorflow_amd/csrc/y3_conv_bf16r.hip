@@ -25,11 +25,10 @@
 //     The epilogue ends with ONE `vmcnt(0)` (its own loads and stores share the counter with the DMAs; nothing here relies
 //     on loads and stores retiring in order relative to each other).
 #include <cstdlib>
-#include "y3_internal.h"
+#include "y3_bf16.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -54,12 +53,6 @@ struct ConvArgsR {
 };
 
 constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ bf16_t f32_to_bf16(float f) {   // round to nearest even (finite inputs)
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
 
 // slot of a 128-byte row that holds logical 16-byte chunk c: c ^ swz(row)
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }

@@ -28,14 +28,11 @@
 //            4 consecutive output channels of one output pixel per quad: scale / shift / LeakyReLU, bf16, staged through the
 //            (now idle) stem-pixel LDS so that an output pixel's 128 bytes leave as eight 16-byte pieces of one line.
 #include <cstdlib>
-#include "y3_internal.h"
+#include "y3_bf16.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -67,14 +64,10 @@ constexpr int NTHR = 512;
 constexpr int NPRE = (PP * PP + NTHR - 1) / NTHR;          // image pixels each thread prefetches per tile (3)
 constexpr int OPITCH = 144;                          // staged output row: 128 bytes + 16 (bank spread)
 
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-    return __builtin_bit_cast(unsigned, v);
-}
 // (a, b) -> packed bf16 pair `hi` (round to nearest even) and the packed bf16 pair `lo` of what is left: a = a_hi + a_lo to 2^-16
 __device__ __forceinline__ void split_bf16(float a, float b, unsigned& hi, unsigned& lo) {
-    hi = pack_bf16(a, b);
-    lo = pack_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xFFFF0000u));
+    hi = cvt_pack_bf16(a, b);
+    lo = cvt_pack_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xFFFF0000u));
 }
 
 __global__ void __launch_bounds__(NTHR) conv_stem_s2_bf16_kernel(const StemS2Args p) {
@@ -206,7 +199,7 @@ __global__ void __launch_bounds__(NTHR) conv_stem_s2_bf16_kernel(const StemS2Arg
                     const float t = acc[4 * g + e] * sc0[g][e] + sh0[g][e];
                     o[e] = p.act0 ? fmaxf(t, 0.1f * t) : t;
                 }
-                const unsigned lo = pack_bf16(o[0], o[1]), hi = pack_bf16(o[2], o[3]);
+                const unsigned lo = cvt_pack_bf16(o[0], o[1]), hi = cvt_pack_bf16(o[2], o[3]);
                 if (pix < SP * SP)
                     *reinterpret_cast<u32x2*>(dst + ((g ^ sw) << 4)) = u32x2{inside ? lo : 0u, inside ? hi : 0u};
             }
@@ -262,7 +255,8 @@ __global__ void __launch_bounds__(NTHR) conv_stem_s2_bf16_kernel(const StemS2Arg
                     const float t = acc3[rt][4 * g + e] * sc[e] + sh[e];
                     o[e] = p.act1 ? fmaxf(t, 0.1f * t) : t;
                 }
-                *reinterpret_cast<u32x2*>(out + l32 * OPITCH + ch * 2) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+                *reinterpret_cast<u32x2*>(out + l32 * OPITCH + ch * 2) =
+                    u32x2{cvt_pack_bf16(o[0], o[1]), cvt_pack_bf16(o[2], o[3])};
             }
         // (one wave: its LDS operations execute in order)
 #pragma unroll

@@ -18,11 +18,10 @@
 //     the other buffer | 4 x (fragment reads, MFMAs) of stage g.
 #include <cstdlib>
 #include <type_traits>
-#include "y3_internal.h"
+#include "y3_bf16.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -52,12 +51,6 @@ struct ConvArgsX {
 };
 
 constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ bf16_t f32_to_bf16(float f) {   // round to nearest even (finite inputs)
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
 
 template <int BK>
 struct Swz {

@@ -134,18 +134,18 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
         Y3_TRY(ctx_pending_error(ctx));     // (the conv launches below go to the launchers: refuse after a stream-K time-out)
         const long long in_rows = (long long)n * d.h * d.w;
         const float* xin = tptr(l.src);
-        const bool b16 = r.kind == RouteKind::Bf16Train;     // (dtype 1: every layer but the stem; bf16 activations in all)
-        if (l.up >= 0 && net->dtype == NetDtype::BF16) {
+        const bool b16 = r.kind == RouteKind::Bf16Train;     // (dtype 1: every layer but the stem)
+        const bool half = net->dtype == NetDtype::BF16;      // (dtype 1: bf16 activations in all layers)
+        if (l.up >= 0) {      // training materialises concat([upsample(up), route]) (model.py:61-62,71-72)
             const int cu = net->tensors[l.up].c, cx = net->tensors[l.src].c;
-            S.xin[i] = A.alloc((size_t)in_rows * (cu + cx) * 2);
-            Y3_TRY(y3_upsample_concat_bf16(ctx, tptr(l.up), cu, xin, cx, n, d.h, d.w, A.p(S.xin[i])));
-            xin = A.p(S.xin[i]);
-        } else if (l.up >= 0) {      // training materialises concat([upsample(up), route]) (model.py:61-62,71-72)
-            const int cu = net->tensors[l.up].c, cx = net->tensors[l.src].c;
-            Buf upt = A.alloc((size_t)in_rows * cu * 4);
-            S.xin[i] = A.alloc((size_t)in_rows * (cu + cx) * 4);
-            Y3_TRY(y3_upsample_nearest(ctx, tptr(l.up), n, d.h / 2, d.w / 2, cu, d.h, d.w, A.p(upt)));
-            Y3_TRY(y3_concat_channels(ctx, A.p(upt), cu, xin, cx, in_rows, A.p(S.xin[i])));
+            Buf upt = half ? Buf() : A.alloc((size_t)in_rows * cu * 4);      // (bf16: one kernel upsamples and concatenates)
+            S.xin[i] = A.alloc((size_t)in_rows * (cu + cx) * (half ? 2 : 4));
+            if (half) {
+                Y3_TRY(y3_upsample_concat_bf16(ctx, tptr(l.up), cu, xin, cx, n, d.h, d.w, A.p(S.xin[i])));
+            } else {
+                Y3_TRY(y3_upsample_nearest(ctx, tptr(l.up), n, d.h / 2, d.w / 2, cu, d.h, d.w, A.p(upt)));
+                Y3_TRY(y3_concat_channels(ctx, A.p(upt), cu, xin, cx, in_rows, A.p(S.xin[i])));
+            }
             A.release(upt);
             xin = A.p(S.xin[i]);
         }
@@ -198,15 +198,12 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
                 Y3_TRY(y3_bn_train_stats(ctx, y, rows, cout, v.gamma, v.beta, BN_EPS, o->bn_decay, st, st + cout, st + 2 * cout,
                                          st + 3 * cout, v.moving_mean, v.moving_variance, A.p(S.reduce_sc)));
             A.release(part);
-            if (net->dtype == NetDtype::BF16) {      // (the stem's z is fp32)
-                S.tens[l.dst] = A.alloc((size_t)rows * cout * 2);
-                Y3_TRY(y3_bn_apply_fwd_bf16(ctx, y, !b16, st + 2 * cout, st + 3 * cout, l.resid >= 0 ? tptr(l.resid) : nullptr,
-                                            rows, cout, A.p(S.tens[l.dst])));
-            } else {
-                S.tens[l.dst] = A.alloc((size_t)rows * cout * 4);
-                Y3_TRY(y3_bn_apply_fwd(ctx, y, st + 2 * cout, st + 3 * cout, l.resid >= 0 ? tptr(l.resid) : nullptr, rows, cout, 1,
-                                       A.p(S.tens[l.dst])));
-            }
+            S.tens[l.dst] = A.alloc((size_t)rows * cout * (half ? 2 : 4));
+            const float* res = l.resid >= 0 ? tptr(l.resid) : nullptr;
+            if (half)      // (the stem's z is fp32)
+                Y3_TRY(y3_bn_apply_fwd_bf16(ctx, y, !b16, st + 2 * cout, st + 3 * cout, res, rows, cout, A.p(S.tens[l.dst])));
+            else
+                Y3_TRY(y3_bn_apply_fwd(ctx, y, st + 2 * cout, st + 3 * cout, res, rows, cout, 1, A.p(S.tens[l.dst])));
         }
         const int e = net->tensors[l.dst].ext;
         if (e >= 0) S.fm_tensor[e] = l.dst;
@@ -360,56 +357,39 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
         long long rows;
         // dtype 1 (all but the stem): dz in bf16, rounded once from the fp32 BN backward (or loss gradient); dy stays fp32
         const bool b16 = S.routes[i].wgrad.kind == RouteKind::Bf16Train;
-        if (l.bn && b16) {
+        if (l.bn) {
             rows = (long long)n * (d.h / l.stride) * (d.w / l.stride);
             if (l.resid >= 0 && needs(l.resid)) {
                 if (have[l.resid]) {
                     if (int rc = accumulate_into(l.resid, A.p(dy), cout, 0, rows, cout)) return rc;
                 } else {
+                    // dy is also the first contribution to the shortcut's gradient (res_block: net + shortcut,
+                    // utils/layer_utils.py:30): dy itself becomes that gradient (no copy)
                     grads[l.resid] = dy;
                     own[l.resid] = own[dst];
                     have[l.resid] = 1;
                     dy_given_away = true;
                 }
             }
-            dz_buf = A.alloc((size_t)rows * cout * 2);
+            // fp32: BN backward runs in place unless dy was given away; bf16: dz is always a buffer of its own, half the size
+            dz_buf = b16 ? A.alloc((size_t)rows * cout * 2) : dy_given_away ? A.alloc((size_t)rows * cout * 4) : dy;
             Buf tmp;
-            float *dgam = gptr(v.g_gamma), *dbet = gptr(v.g_beta);
-            if (!trainable(v.g_gamma) || !trainable(v.g_beta)) tmp = A.alloc((size_t)2 * cout * 4);
-            const float* st = A.p(S.stats[i]);
-            Y3_TRY(y3_bn_train_bwd_bf16(ctx, A.p(S.z[i]), A.p(dy), v.gamma, st + 2 * cout, st + 3 * cout, st, st + cout, rows, cout,
-                                        dgam ? dgam : A.p(tmp), dbet ? dbet : A.p(tmp) + cout, A.p(dz_buf), A.p(S.bnbwd_sc)));
-            A.release(tmp);
-            dz_stride = cout;
-        } else if (l.bn) {
-            rows = (long long)n * (d.h / l.stride) * (d.w / l.stride);
-            dz_buf = dy;                 // BN backward runs in place ...
-            if (l.resid >= 0 && needs(l.resid)) {
-                if (have[l.resid]) {
-                    if (int rc = accumulate_into(l.resid, A.p(dy), cout, 0, rows, cout)) return rc;
-                } else {
-                    // ... unless dy is also the first contribution to the shortcut's gradient (res_block: net + shortcut,
-                    // utils/layer_utils.py:30): then dy itself becomes that gradient (no copy), dz goes elsewhere
-                    grads[l.resid] = dy;
-                    own[l.resid] = own[dst];
-                    have[l.resid] = 1;
-                    dy_given_away = true;
-                    dz_buf = A.alloc((size_t)rows * cout * 4);
-                }
-            }
-            Buf tmp;
-            float *dgam = gptr(v.g_gamma), *dbet = gptr(v.g_beta);
             // (asked of the offsets, not the pointers: the dry run's flat_grad is null, and an offset of 0 must not look untrainable)
             if (!trainable(v.g_gamma) || !trainable(v.g_beta)) tmp = A.alloc((size_t)2 * cout * 4);
+            float* dgam = trainable(v.g_gamma) ? gptr(v.g_gamma) : A.p(tmp);
+            float* dbet = trainable(v.g_beta) ? gptr(v.g_beta) : A.p(tmp) + cout;
             const float* st = A.p(S.stats[i]);
-            if (fused_nb[i] > 0) {
-                Y3_TRY(y3_bn_train_bwd_partials(ctx, A.p(S.z[i]), A.p(dy), v.gamma, st + 2 * cout, st + 3 * cout, st, st + cout, rows,
-                                                cout, A.p(fused_part[i]), fused_nb[i], dgam ? dgam : A.p(tmp),
-                                                dbet ? dbet : A.p(tmp) + cout, A.p(dz_buf), A.p(S.bnbwd_sc)));
+            const float *sc = st + 2 * cout, *sh = st + 3 * cout, *mean = st, *istd = st + cout;
+            if (b16) {
+                Y3_TRY(y3_bn_train_bwd_bf16(ctx, A.p(S.z[i]), A.p(dy), v.gamma, sc, sh, mean, istd, rows, cout, dgam, dbet, A.p(dz_buf),
+                                            A.p(S.bnbwd_sc)));
+            } else if (fused_nb[i] > 0) {
+                Y3_TRY(y3_bn_train_bwd_partials(ctx, A.p(S.z[i]), A.p(dy), v.gamma, sc, sh, mean, istd, rows, cout, A.p(fused_part[i]),
+                                                fused_nb[i], dgam, dbet, A.p(dz_buf), A.p(S.bnbwd_sc)));
                 A.release(fused_part[i]);
             } else {
-                Y3_TRY(y3_bn_train_bwd(ctx, A.p(S.z[i]), A.p(dy), v.gamma, st + 2 * cout, st + 3 * cout, st, st + cout, rows, cout,
-                                       dgam ? dgam : A.p(tmp), dbet ? dbet : A.p(tmp) + cout, A.p(dz_buf), A.p(S.bnbwd_sc)));
+                Y3_TRY(y3_bn_train_bwd(ctx, A.p(S.z[i]), A.p(dy), v.gamma, sc, sh, mean, istd, rows, cout, dgam, dbet, A.p(dz_buf),
+                                       A.p(S.bnbwd_sc)));
             }
             A.release(tmp);
             dz_stride = cout;

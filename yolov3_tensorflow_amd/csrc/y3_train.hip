@@ -6,7 +6,7 @@
 // per-workgroup partial sums written to a scratch array and combined by a finalize kernel in a FIXED order
 // (fp64 accumulation) so that every statistic and gradient is run-to-run deterministic (no float atomics).
 #include <vector>
-#include "y3_internal.h"
+#include "y3_bf16.h"
 
 namespace {
 
@@ -19,12 +19,38 @@ inline int grid_for(long long work, int cap = 256 * 16) {
     return (int)b;
 }
 
+// ---- element access of the BN passes --------------------------------------------------------------------
+// The passes move four consecutive channels per lane; what differs between the fp32 and the bf16 train step is only how those
+// four are read and written.  ld / st take an ELEMENT pointer.  Three ways to read (which pass reads which way was measured,
+// profiles/r06_bn_nt_ab.txt, and is fixed where the kernels are instantiated), two to write (bf16: rounded once).
+template <bool STREAM>
+__device__ __forceinline__ f32x4 ld_f32x4(const float* p) {
+    const f32x4* p4 = reinterpret_cast<const f32x4*>(p);
+    return STREAM ? __builtin_nontemporal_load(p4) : *p4;
+}
+struct F32 {              // fp32, plain loads
+    typedef float T;
+    static constexpr bool STREAM = false;
+    static __device__ __forceinline__ f32x4 ld(const float* p) { return ld_f32x4<false>(p); }
+    static __device__ __forceinline__ void st(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+};
+struct F32Stream : F32 {  // fp32, streaming loads (a tensor that is not read again soon: the caches stay with the others)
+    static constexpr bool STREAM = true;
+    static __device__ __forceinline__ f32x4 ld(const float* p) { return ld_f32x4<true>(p); }
+};
+struct Bf16 {             // bf16 storage, fp32 arithmetic
+    typedef bf16_t T;
+    static constexpr bool STREAM = false;
+    static __device__ __forceinline__ f32x4 ld(const bf16_t* p) { return ld_bf16x4(p); }
+    static __device__ __forceinline__ void st(bf16_t* p, f32x4 v) { st_bf16x4(p, v); }
+};
+
 // ---- column reductions over an [M][C] matrix -----------------------------------------------------
 // MODE 0: (sum z, sum z^2)                                       -> BN forward statistics
 // MODE 1: (sum g', sum g'*zhat), g' = dy * leaky'(z*scale+shift) -> BN backward (d beta, d gamma)
 // Workgroup b handles rows b, b+gridDim, ...; thread t owns float4 column (t % C4) and row lane t / C4.
-template <int MODE>
-__global__ void __launch_bounds__(256) col_reduce_kernel(const float* __restrict__ z, const float* __restrict__ dy,
+template <int MODE, class Z>
+__global__ void __launch_bounds__(256) col_reduce_kernel(const typename Z::T* __restrict__ z, const float* __restrict__ dy,
                                                          const float* __restrict__ scale,
                                                          const float* __restrict__ shift,
                                                          const float* __restrict__ mean,
@@ -50,13 +76,13 @@ __global__ void __launch_bounds__(256) col_reduce_kernel(const float* __restrict
             for (long long r = (long long)blockIdx.x * rows_per_pass + tr; r < M;
                  r += (long long)gridDim.x * rows_per_pass) {
                 if (MODE == 0) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(z + r * C + 4 * c4);
+                    const f32x4 v = Z::ld(z + r * C + 4 * c4);
                     s0 += v;
                     s1 += v * v;
                 } else {
                     // (plain loads: bn_apply_bwd reads both tensors again right behind this kernel, and what the caches keep of
                     // them counts - streaming loads here cost 0.15-0.35 ms per bs=64 step, profiles/r06_bn_nt_ab.txt)
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(z + r * C + 4 * c4);
+                    const f32x4 v = Z::ld(z + r * C + 4 * c4);
                     f32x4 g = *reinterpret_cast<const f32x4*>(dy + r * C + 4 * c4);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -180,86 +206,42 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __res
     }
 }
 
-// y = leaky(z*scale + shift) (+ residual)
-__global__ void __launch_bounds__(256) bn_apply_fwd_kernel(const float* __restrict__ z,
+// y = leaky(z*scale + shift) (+ residual); the residual is stored as y is
+template <class Z, class Y>
+__global__ void __launch_bounds__(256) bn_apply_fwd_kernel(const typename Z::T* __restrict__ z,
                                                            const float* __restrict__ scale,
                                                            const float* __restrict__ shift,
-                                                           const float* __restrict__ resid, long long total4,
-                                                           int C4, int act, float* __restrict__ y) {
-    const f32x4* z4 = reinterpret_cast<const f32x4*>(z);
-    const f32x4* r4 = reinterpret_cast<const f32x4*>(resid);
+                                                           const typename Y::T* __restrict__ resid, long long total4,
+                                                           int C4, int act, typename Y::T* __restrict__ y) {
     const f32x4* sc4 = reinterpret_cast<const f32x4*>(scale);
     const f32x4* sh4 = reinterpret_cast<const f32x4*>(shift);
-    f32x4* y4 = reinterpret_cast<f32x4*>(y);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C4);
-        // (z is not read again before the backward pass: a streaming load leaves the caches to y, which the next conv reads;
+        // (fp32: z is not read again before the backward pass: a streaming load leaves the caches to y, which the next conv reads;
         // measured on the bs=64 step together with the two loads of bn_apply_bwd: 81.63 -> 81.22 ms, profiles/r06_bn_nt_ab.txt)
-        f32x4 v = __builtin_nontemporal_load(z4 + i) * sc4[c] + sh4[c];
+        f32x4 v = Z::ld(z + 4 * i) * sc4[c] + sh4[c];
         if (act) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = v[q] > 0.f ? v[q] : 0.1f * v[q];
         }
-        if (resid) v += __builtin_nontemporal_load(r4 + i);
-        y4[i] = v;
+        if (resid) v += Y::ld(resid + 4 * i);
+        Y::st(y + 4 * i, v);
     }
 }
 
-// dz = a * (g' - b - zhat * c),  g' = dy * leaky'(u), u = z*scale+shift, zhat = (z-mean)*inv_std
-__global__ void __launch_bounds__(256) bn_apply_bwd_kernel(const float* __restrict__ z, const float* __restrict__ dy,
-                                                           const float* __restrict__ scale,
-                                                           const float* __restrict__ shift,
-                                                           const float* __restrict__ mean,
-                                                           const float* __restrict__ inv_std,
-                                                           const float* __restrict__ coef, long long total4,
-                                                           int C4, float* __restrict__ dz) {
-    const f32x4* z4 = reinterpret_cast<const f32x4*>(z);
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(dy);
-    f32x4* o4 = reinterpret_cast<f32x4*>(dz);
-    const int C = C4 * 4;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % C4) * 4;
-        const f32x4 v = __builtin_nontemporal_load(z4 + i);      // (the last reader of z and of dy)
-        f32x4 g = __builtin_nontemporal_load(g4 + i);
-        f32x4 out;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float u = v[q] * scale[c + q] + shift[c + q];
-            const float gp = u > 0.f ? g[q] : 0.1f * g[q];
-            const float zh = (v[q] - mean[c + q]) * inv_std[c + q];
-            out[q] = coef[c + q] * (gp - coef[C + c + q] - zh * coef[2 * C + c + q]);
-        }
-        o4[i] = out;
-    }
-}
-
-// ---- the bf16 train step (net dtype 1): bf16 z / activations / dz, fp32 statistics and arithmetic ----------------
-__device__ __forceinline__ f32x4 ld_bf16x4(const unsigned short* p) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
-    return f32x4{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u), __uint_as_float(v.y << 16),
-                 __uint_as_float(v.y & 0xFFFF0000u)};
-}
-__device__ __forceinline__ unsigned rne_bf16(float f) {   // round to nearest even (finite inputs)
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ void st_bf16x4(unsigned short* p, f32x4 v) {
-    *reinterpret_cast<uint2*>(p) = uint2{rne_bf16(v[0]) | (rne_bf16(v[1]) << 16), rne_bf16(v[2]) | (rne_bf16(v[3]) << 16)};
-}
-
-// y = leaky(z*scale + shift) (+ residual), rounded once to bf16; z bf16 (or fp32: the stem), residual bf16
-template <bool ZF32>
-__global__ void __launch_bounds__(256) bn_apply_fwd_bf16_kernel(const void* __restrict__ z, const float* __restrict__ scale,
-                                                                const float* __restrict__ shift,
-                                                                const unsigned short* __restrict__ resid, long long total4,
-                                                                int C4, int act, unsigned short* __restrict__ y) {
+// The stem of the bf16 train step (fp32 z, plain loads; bf16 y and residual) keeps a body of its own: through the traits the
+// compiler orders its address arithmetic differently (same instructions, other registers and schedule), and that form has
+// not been timed; this one is the code the committed measurements were taken on (profiles/bn_merge_isa.txt).
+template <>
+__global__ void __launch_bounds__(256) bn_apply_fwd_kernel<F32, Bf16>(const float* __restrict__ z, const float* __restrict__ scale,
+                                                                      const float* __restrict__ shift,
+                                                                      const bf16_t* __restrict__ resid, long long total4, int C4,
+                                                                      int act, bf16_t* __restrict__ y) {
     const f32x4* sc4 = reinterpret_cast<const f32x4*>(scale);
     const f32x4* sh4 = reinterpret_cast<const f32x4*>(shift);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C4);
-        f32x4 v = ZF32 ? reinterpret_cast<const f32x4*>(z)[i] : ld_bf16x4(static_cast<const unsigned short*>(z) + 4 * i);
-        v = v * sc4[c] + sh4[c];
+        f32x4 v = reinterpret_cast<const f32x4*>(z)[i] * sc4[c] + sh4[c];
         if (act) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = v[q] > 0.f ? v[q] : 0.1f * v[q];
@@ -269,65 +251,20 @@ __global__ void __launch_bounds__(256) bn_apply_fwd_bf16_kernel(const void* __re
     }
 }
 
-// col_reduce_kernel<1> over a bf16 z: (sum g', sum g'*zhat) partial rows [grid][2][C]
-__global__ void __launch_bounds__(256) bn_bwd_reduce_bf16_kernel(const unsigned short* __restrict__ z, const float* __restrict__ dy,
-                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                 const float* __restrict__ mean, const float* __restrict__ inv_std,
-                                                                 long long M, int C, float* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float red[];  // [rows_per_pass][2][C]
-    const int C4 = C >> 2;
-    const int lanes_per_row = C4 < 256 ? C4 : 256;
-    const int rows_per_pass = 256 / lanes_per_row;
-    const int cols_per_thread = (C4 + 255) / 256;
-    const int tl = threadIdx.x % lanes_per_row, tr = threadIdx.x / lanes_per_row;
-    for (int cc = 0; cc < cols_per_thread; ++cc) {
-        const int c4 = tl + cc * 256;
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-        if (c4 < C4 && tr < rows_per_pass) {
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * c4);
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + 4 * c4);
-            const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + 4 * c4);
-            const f32x4 is = *reinterpret_cast<const f32x4*>(inv_std + 4 * c4);
-            for (long long r = (long long)blockIdx.x * rows_per_pass + tr; r < M; r += (long long)gridDim.x * rows_per_pass) {
-                const f32x4 v = ld_bf16x4(z + r * C + 4 * c4);
-                f32x4 g = *reinterpret_cast<const f32x4*>(dy + r * C + 4 * c4);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float u = v[q] * sc[q] + sh[q];
-                    g[q] = u > 0.f ? g[q] : 0.1f * g[q];
-                }
-                s0 += g;
-                s1 += g * ((v - mu) * is);
-            }
-        }
-        __syncthreads();
-        if (c4 < C4 && tr < rows_per_pass) {
-            *reinterpret_cast<f32x4*>(red + ((size_t)tr * 2 + 0) * C + 4 * c4) = s0;
-            *reinterpret_cast<f32x4*>(red + ((size_t)tr * 2 + 1) * C + 4 * c4) = s1;
-        }
-        __syncthreads();
-        if (c4 < C4 && tr == 0) {
-            for (int k = 1; k < rows_per_pass; ++k) {
-                s0 += *reinterpret_cast<const f32x4*>(red + ((size_t)k * 2 + 0) * C + 4 * c4);
-                s1 += *reinterpret_cast<const f32x4*>(red + ((size_t)k * 2 + 1) * C + 4 * c4);
-            }
-            *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * C + 4 * c4) = s0;
-            *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * C + 4 * c4) = s1;
-        }
-    }
-}
-
-// bn_apply_bwd_kernel with a bf16 z and a bf16 dz (rounded once)
-__global__ void __launch_bounds__(256) bn_apply_bwd_bf16_kernel(const unsigned short* __restrict__ z, const float* __restrict__ dy,
-                                                                const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                const float* __restrict__ mean, const float* __restrict__ inv_std,
-                                                                const float* __restrict__ coef, long long total4, int C4,
-                                                                unsigned short* __restrict__ dz) {
+// dz = a * (g' - b - zhat * c),  g' = dy * leaky'(u), u = z*scale+shift, zhat = (z-mean)*inv_std; dy is fp32, read the way z is
+template <class Z, class DZ>
+__global__ void __launch_bounds__(256) bn_apply_bwd_kernel(const typename Z::T* __restrict__ z, const float* __restrict__ dy,
+                                                           const float* __restrict__ scale,
+                                                           const float* __restrict__ shift,
+                                                           const float* __restrict__ mean,
+                                                           const float* __restrict__ inv_std,
+                                                           const float* __restrict__ coef, long long total4,
+                                                           int C4, typename DZ::T* __restrict__ dz) {
     const int C = C4 * 4;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C4) * 4;
-        const f32x4 v = ld_bf16x4(z + 4 * i);
-        const f32x4 g = reinterpret_cast<const f32x4*>(dy)[i];
+        const f32x4 v = Z::ld(z + 4 * i);                        // (the last reader of z and of dy)
+        const f32x4 g = ld_f32x4<Z::STREAM>(dy + 4 * i);
         f32x4 out;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -336,14 +273,15 @@ __global__ void __launch_bounds__(256) bn_apply_bwd_bf16_kernel(const unsigned s
             const float zh = (v[q] - mean[c + q]) * inv_std[c + q];
             out[q] = coef[c + q] * (gp - coef[C + c + q] - zh * coef[2 * C + c + q]);
         }
-        st_bf16x4(dz + 4 * i, out);
+        DZ::st(dz + 4 * i, out);
     }
 }
 
+// ---- the bf16 train step's own passes (net dtype 1) ---------------------------------------------------------------------
 // out [n,h,w,cu+cx] = concat(upsample2x(up [n,h/2,w/2,cu]), x [n,h,w,cx]), all bf16 (exact copies), 8 bytes per thread
-__global__ void __launch_bounds__(256) upsample_concat_bf16_kernel(const unsigned short* __restrict__ up, int cu,
-                                                                   const unsigned short* __restrict__ x, int cx, int h, int w,
-                                                                   long long total4, unsigned short* __restrict__ out) {
+__global__ void __launch_bounds__(256) upsample_concat_bf16_kernel(const bf16_t* __restrict__ up, int cu,
+                                                                   const bf16_t* __restrict__ x, int cx, int h, int w,
+                                                                   long long total4, bf16_t* __restrict__ out) {
     const int c4 = (cu + cx) / 4;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
         const long long pix = i / c4;
@@ -361,7 +299,7 @@ __global__ void __launch_bounds__(256) upsample_concat_bf16_kernel(const unsigne
 }
 
 __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restrict__ src, long long total4,
-                                                          unsigned short* __restrict__ dst) {
+                                                          bf16_t* __restrict__ dst) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256)
         st_bf16x4(dst + 4 * i, reinterpret_cast<const f32x4*>(src)[i]);
 }
@@ -860,9 +798,9 @@ __global__ void target_assign_kernel(const TargetArgs a) {
 // ------------------------------------------------------------------------------------------------------
 extern "C" size_t y3_reduce_scratch_bytes(int c) { return (size_t)RED_BLOCKS * 2 * (size_t)(c > 0 ? c : 0) * sizeof(float); }
 
-static int reduce_launch(y3_ctx* ctx, int mode, const float* z, const float* dy, const float* scale,
-                         const float* shift, const float* mean, const float* inv_std, long long rows, int c,
-                         float* scratch, int* nblocks_out) {
+template <int MODE, class Z>
+static int reduce_launch(y3_ctx* ctx, const typename Z::T* z, const float* dy, const float* scale, const float* shift,
+                         const float* mean, const float* inv_std, long long rows, int c, float* scratch, int* nblocks_out) {
     const int C4 = c / 4;
     const int lanes_per_row = C4 < 256 ? C4 : 256;
     const int rows_per_pass = 256 / lanes_per_row;
@@ -870,12 +808,8 @@ static int reduce_launch(y3_ctx* ctx, int mode, const float* z, const float* dy,
     if (nb > RED_BLOCKS) nb = RED_BLOCKS;
     if (nb < 1) nb = 1;
     const size_t lds = (size_t)rows_per_pass * 2 * c * sizeof(float);
-    if (mode == 0)
-        hipLaunchKernelGGL(col_reduce_kernel<0>, dim3((int)nb), dim3(256), lds, ctx->stream, z, dy, scale, shift,
-                           mean, inv_std, rows, c, scratch);
-    else
-        hipLaunchKernelGGL(col_reduce_kernel<1>, dim3((int)nb), dim3(256), lds, ctx->stream, z, dy, scale, shift,
-                           mean, inv_std, rows, c, scratch);
+    hipLaunchKernelGGL((col_reduce_kernel<MODE, Z>), dim3((int)nb), dim3(256), lds, ctx->stream, z, dy, scale, shift, mean,
+                       inv_std, rows, c, scratch);
     Y3_CHECK_HIP(hipGetLastError());
     *nblocks_out = (int)nb;
     return Y3_OK;
@@ -890,7 +824,7 @@ extern "C" int y3_bn_train_stats(y3_ctx* ctx, const float* z, long long rows, in
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_train_stats: bad shape rows=%lld c=%d", rows, c);
     Y3_CHECK_ARG((moving_mean == nullptr) == (moving_var == nullptr), "y3_bn_train_stats: moving stats must come in pairs");
     int nb = 0;
-    if (int rc = reduce_launch(ctx, 0, z, nullptr, nullptr, nullptr, nullptr, nullptr, rows, c, scratch, &nb)) return rc;
+    if (int rc = (reduce_launch<0, F32>(ctx, z, nullptr, nullptr, nullptr, nullptr, nullptr, rows, c, scratch, &nb))) return rc;
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, scratch, nb, c,
                        (double)rows, gamma, beta, eps, decay, mean, inv_std, scale, shift, moving_mean, moving_var);
     Y3_CHECK_HIP(hipGetLastError());
@@ -912,13 +846,49 @@ extern "C" int y3_bn_train_stats_partials(y3_ctx* ctx, const float* partial, int
     return Y3_OK;
 }
 
+// How the passes over a tensor stored as T read it (measured, profiles/r06_bn_nt_ab.txt): the fp32 reduction keeps z and dy in
+// the caches for the apply pass right behind it, the fp32 apply passes stream; the bf16 passes read plainly.
+template <class T> struct BnAccess;
+template <> struct BnAccess<float> { typedef F32 Reduce; typedef F32Stream Apply; };
+template <> struct BnAccess<bf16_t> { typedef Bf16 Reduce; typedef Bf16 Apply; };
+
+template <class Z, class Y>
+static int apply_fwd_launch(y3_ctx* ctx, const void* z, const float* scale, const float* shift, const void* residual, long long rows,
+                            int c, int act, void* y) {
+    const long long total4 = rows * (c / 4);
+    hipLaunchKernelGGL((bn_apply_fwd_kernel<Z, Y>), dim3(grid_for(total4)), dim3(256), 0, ctx->stream,
+                       static_cast<const typename Z::T*>(z), scale, shift, static_cast<const typename Y::T*>(residual), total4, c / 4,
+                       act, static_cast<typename Y::T*>(y));
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
 extern "C" int y3_bn_apply_fwd(y3_ctx* ctx, const float* z, const float* scale, const float* shift,
                                const float* residual, long long rows, int c, int act, float* y) {
     Y3_CHECK_ARG(ctx && z && scale && shift && y, "y3_bn_apply_fwd: null argument");
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_apply_fwd: bad shape");
+    return apply_fwd_launch<F32Stream, F32Stream>(ctx, z, scale, shift, residual, rows, c, act, y);
+}
+
+// BN backward of a tensor stored as T, dz stored alike: the reduction (unless the caller hands its partial sums in: `partial`,
+// [nblocks][2][c]), the finalize and the apply pass.  scratch: y3_bn_bwd_scratch_bytes - the partial rows, then [3][c] coefficients.
+template <class T>
+static int bn_bwd(y3_ctx* ctx, const T* z, const float* dy, const float* gamma, const float* scale, const float* shift,
+                  const float* mean, const float* inv_std, long long rows, int c, const float* partial, int nblocks, float* dgamma,
+                  float* dbeta, T* dz, float* scratch) {
+    typedef BnAccess<T> Acc;
+    if (!partial) {
+        if (int rc = (reduce_launch<1, typename Acc::Reduce>(ctx, z, dy, scale, shift, mean, inv_std, rows, c, scratch, &nblocks)))
+            return rc;
+        partial = scratch;
+    }
+    float* coef = scratch + (size_t)RED_BLOCKS * 2 * c;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, partial, nblocks, c,
+                       (double)rows, gamma, inv_std, dbeta, dgamma, coef);
+    Y3_CHECK_HIP(hipGetLastError());
     const long long total4 = rows * (c / 4);
-    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, z, scale, shift,
-                       residual, total4, c / 4, act, y);
+    hipLaunchKernelGGL((bn_apply_bwd_kernel<typename Acc::Apply, typename Acc::Apply>), dim3(grid_for(total4)), dim3(256), 0,
+                       ctx->stream, z, dy, scale, shift, mean, inv_std, coef, total4, c / 4, dz);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }
@@ -929,17 +899,7 @@ extern "C" int y3_bn_train_bwd(y3_ctx* ctx, const float* z, const float* dy, con
     Y3_CHECK_ARG(ctx && z && dy && gamma && scale && shift && mean && inv_std && dz && scratch,
                  "y3_bn_train_bwd: null argument");
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_train_bwd: bad shape");
-    int nb = 0;
-    if (int rc = reduce_launch(ctx, 1, z, dy, scale, shift, mean, inv_std, rows, c, scratch, &nb)) return rc;
-    float* coef = scratch + (size_t)RED_BLOCKS * 2 * c;   // scratch has room for 3*C more (see y3_bn_bwd_scratch_bytes)
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, scratch, nb, c,
-                       (double)rows, gamma, inv_std, dbeta, dgamma, coef);
-    Y3_CHECK_HIP(hipGetLastError());
-    const long long total4 = rows * (c / 4);
-    hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, z, dy, scale, shift,
-                       mean, inv_std, coef, total4, c / 4, dz);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return bn_bwd<float>(ctx, z, dy, gamma, scale, shift, mean, inv_std, rows, c, nullptr, 0, dgamma, dbeta, dz, scratch);
 }
 
 int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float* dy, const float* gamma, const float* scale, const float* shift,
@@ -948,15 +908,7 @@ int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float* dy, const
     Y3_CHECK_ARG(ctx && z && dy && gamma && scale && shift && mean && inv_std && dz && scratch && partial && nblocks > 0,
                  "y3_bn_train_bwd_partials: null argument");
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_train_bwd_partials: bad shape");
-    float* coef = scratch + (size_t)RED_BLOCKS * 2 * c;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, partial, nblocks, c,
-                       (double)rows, gamma, inv_std, dbeta, dgamma, coef);
-    Y3_CHECK_HIP(hipGetLastError());
-    const long long total4 = rows * (c / 4);
-    hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, z, dy, scale, shift,
-                       mean, inv_std, coef, total4, c / 4, dz);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return bn_bwd<float>(ctx, z, dy, gamma, scale, shift, mean, inv_std, rows, c, partial, nblocks, dgamma, dbeta, dz, scratch);
 }
 
 extern "C" size_t y3_bn_bwd_scratch_bytes(int c) { return y3_reduce_scratch_bytes(c) + (size_t)3 * (c > 0 ? c : 0) * sizeof(float); }
@@ -1176,17 +1128,8 @@ extern "C" int y3_bn_apply_fwd_bf16(y3_ctx* ctx, const void* z, int z_f32, const
                          long long rows, int c, void* y) {
     Y3_CHECK_ARG(ctx && z && scale && shift && y, "y3_bn_apply_fwd_bf16: null argument");
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_apply_fwd_bf16: bad shape");
-    const long long total4 = rows * (c / 4);
-    auto r = static_cast<const unsigned short*>(residual);
-    auto o = static_cast<unsigned short*>(y);
-    if (z_f32)
-        hipLaunchKernelGGL(bn_apply_fwd_bf16_kernel<true>, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, z, scale, shift, r,
-                           total4, c / 4, 1, o);
-    else
-        hipLaunchKernelGGL(bn_apply_fwd_bf16_kernel<false>, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, z, scale, shift, r,
-                           total4, c / 4, 1, o);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return z_f32 ? apply_fwd_launch<F32, Bf16>(ctx, z, scale, shift, residual, rows, c, 1, y)      // (the stem's z)
+                 : apply_fwd_launch<Bf16, Bf16>(ctx, z, scale, shift, residual, rows, c, 1, y);
 }
 
 extern "C" int y3_bn_train_bwd_bf16(y3_ctx* ctx, const void* z, const float* dy, const float* gamma, const float* scale, const float* shift,
@@ -1194,24 +1137,8 @@ extern "C" int y3_bn_train_bwd_bf16(y3_ctx* ctx, const void* z, const float* dy,
                          float* scratch) {
     Y3_CHECK_ARG(ctx && z && dy && gamma && scale && shift && mean && inv_std && dz && scratch, "y3_bn_train_bwd_bf16: null argument");
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_train_bwd_bf16: bad shape");
-    auto zb = static_cast<const unsigned short*>(z);
-    const int C4 = c / 4;
-    const int lanes_per_row = C4 < 256 ? C4 : 256;
-    const int rows_per_pass = 256 / lanes_per_row;
-    long long nb = (rows + rows_per_pass - 1) / rows_per_pass;
-    nb = nb > RED_BLOCKS ? RED_BLOCKS : nb < 1 ? 1 : nb;
-    hipLaunchKernelGGL(bn_bwd_reduce_bf16_kernel, dim3((int)nb), dim3(256), (size_t)rows_per_pass * 2 * c * sizeof(float),
-                       ctx->stream, zb, dy, scale, shift, mean, inv_std, rows, c, scratch);
-    Y3_CHECK_HIP(hipGetLastError());
-    float* coef = scratch + (size_t)RED_BLOCKS * 2 * c;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, scratch, (int)nb, c, (double)rows, gamma, inv_std,
-                       dbeta, dgamma, coef);
-    Y3_CHECK_HIP(hipGetLastError());
-    const long long total4 = rows * C4;
-    hipLaunchKernelGGL(bn_apply_bwd_bf16_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, zb, dy, scale, shift, mean,
-                       inv_std, coef, total4, C4, static_cast<unsigned short*>(dz));
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return bn_bwd<bf16_t>(ctx, static_cast<const bf16_t*>(z), dy, gamma, scale, shift, mean, inv_std, rows, c, nullptr, 0, dgamma,
+                          dbeta, static_cast<bf16_t*>(dz), scratch);
 }
 
 extern "C" int y3_upsample_concat_bf16(y3_ctx* ctx, const void* up, int cu, const void* x, int cx, int n, int h, int w, void* out) {
@@ -1219,8 +1146,8 @@ extern "C" int y3_upsample_concat_bf16(y3_ctx* ctx, const void* up, int cu, cons
     Y3_CHECK_ARG(n > 0 && h % 2 == 0 && w % 2 == 0 && cu % 4 == 0 && cx % 4 == 0, "y3_upsample_concat_bf16: bad shape");
     const long long total4 = (long long)n * h * w * ((cu + cx) / 4);
     hipLaunchKernelGGL(upsample_concat_bf16_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream,
-                       static_cast<const unsigned short*>(up), cu, static_cast<const unsigned short*>(x), cx, h, w, total4,
-                       static_cast<unsigned short*>(out));
+                       static_cast<const bf16_t*>(up), cu, static_cast<const bf16_t*>(x), cx, h, w, total4,
+                       static_cast<bf16_t*>(out));
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }
@@ -1229,7 +1156,7 @@ extern "C" int y3_f32_to_bf16(y3_ctx* ctx, const float* src, long long count, vo
     Y3_CHECK_ARG(ctx && src && dst && count > 0 && count % 4 == 0, "y3_f32_to_bf16: bad argument");
     const long long total4 = count / 4;
     hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(total4)), dim3(256), 0, ctx->stream, src, total4,
-                       static_cast<unsigned short*>(dst));
+                       static_cast<bf16_t*>(dst));
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }

@@ -13,11 +13,10 @@
 // Every Cin of the network is a multiple of 32, so a 16-byte chunk of a P row never crosses a tap: each thread stages one
 // fixed (tap, ci) column chunk, and the P gather is x's row of that tap (zero outside the image: buffer loads past the end).
 #include <algorithm>
-#include "y3_internal.h"
+#include "y3_bf16.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
