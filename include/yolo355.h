@@ -539,6 +539,18 @@ struct y3f_djob;
 int y3_feed_run(y3_ctx* ctx, const void* blob_dev, const struct y3f_djob* jobs_host, int n, const void* tables_dev,
                 void* scratch_dev, size_t scratch_bytes, float* out, int out_h, int out_w);
 
+/* y3_feed_run over a y3f_plan_batch_src plan (include/yolo355_feed.h): a source whose record says so is not in the blob but in
+ * the caller's device arena src_dev of src_bytes (whole 8-bit RGB images; NULL when no record refers to it), and is read where
+ * it lies.  This entry is given every size and checks every record before it launches anything: each blob offset plus extent
+ * (records, packed sources, jitter maps, tables by their ksize and counts) against blob_bytes, each arena rectangle
+ * (img_off + ((r_y0 + r_h - 1) * stride + r_x0 + r_w) * 3, stride >= r_x0 + r_w) against src_bytes, live inside win, the
+ * scratch extents; anything out of range is Y3_EINVAL naming the job.  The kernels read the records from the copy that was
+ * checked, uploaded behind the jobs' scratch: scratch_bytes >= the plan's scratch + 16 + n * sizeof(y3f_djob).  Same bytes
+ * as y3_feed_run gives for the packed plan of the same jobs (tests/test_feed_src_gpu.py). */
+int y3_feed_run_src(y3_ctx* ctx, const void* blob_dev, size_t blob_bytes, const struct y3f_djob* jobs_host, int n,
+                    const void* tables_dev, void* scratch_dev, size_t scratch_bytes, const void* src_dev, size_t src_bytes,
+                    float* out, int out_h, int out_w);
+
 /* The device half of the feeder's JPEG decoder (include/yolo355_jpeg.h).  liby3feed.so's y3f_jpeg_plan wrote n files into
  * one blob; the caller uploads it and passes its device address and size, the host copy of the n y3j_rec records at its
  * start, a scratch of >= the plan's scratch bytes and an output of >= its output bytes.  Every record's extents are checked

@@ -133,7 +133,8 @@ typedef struct y3f_djob {
     int32_t mode, horizontal, vertical, ksize_x, ksize_y;
     int32_t tmp_y0, tmp_rows;           /* the horizontal pass holds window rows [tmp_y0, tmp_y0 + tmp_rows) */
     int32_t res_w, res_h, out_w, out_h, pad_x, pad_y, pad_value, flip_x;
-    int32_t reserved[3];
+    int32_t reserved[3];                /* all 0 from y3f_plan_batch.  y3f_plan_batch_src: [0] = Y3F_SRC1_ARENA | Y3F_SRC2_ARENA
+                                           bits, [1] / [2] = row stride of source 1 / 2 in pixels (see below) */
 } y3f_djob;                             /* 208 bytes */
 
 /* Plans n jobs for the device.  Always sets *blob_bytes and *scratch_bytes to what the batch needs; when `blob` is not
@@ -142,6 +143,25 @@ typedef struct y3f_djob {
  * Every job must have the same out_w x out_h. */
 int y3f_plan_batch(const y3f_job* jobs, int n, uint8_t* blob, size_t capacity, size_t* blob_bytes, size_t* scratch_bytes,
                    int threads);
+
+/* The same plan with sources read BY REFERENCE: decoded images that the caller keeps in a device arena (8-bit RGB HWC, rows
+ * contiguous, w * 3 bytes per row) are not copied into the blob.  src1_off[i] / src2_off[i] is the byte offset in that arena of
+ * the WHOLE image img1 / img2 of job i, or Y3F_NOT_IN_ARENA; such a job's img1 / img2 pointer may be NULL (h and w are still
+ * read; a partner exists when img2 is not NULL or src2_off[i] is an offset).  In the record of a source in the arena
+ *     reserved[0] has Y3F_SRC1_ARENA / Y3F_SRC2_ARENA set,
+ *     reserved[1] / reserved[2] is the row stride of the image in PIXELS (= w1 / w2),
+ *     img1_off / img2_off is the arena offset of the whole image,
+ *     r*_x0, r*_y0, r*_w, r*_h stay the visible rectangle in image coordinates: pixel (x, y) of it is at
+ *     arena + img_off + (y * stride + x) * 3,
+ * and the blob holds no bytes for it.  Every other source is packed as y3f_plan_batch packs it; a batch may mix both kinds job
+ * by job and source by source.  src1_off / src2_off may be NULL (= nothing in the arena); with nothing in the arena the blob
+ * is byte-identical to y3f_plan_batch's.  Sizing and a too small capacity behave as there.  y3_feed_run_src (include/yolo355.h)
+ * runs such a plan. */
+#define Y3F_NOT_IN_ARENA UINT64_MAX
+#define Y3F_SRC1_ARENA 1
+#define Y3F_SRC2_ARENA 2
+int y3f_plan_batch_src(const y3f_job* jobs, const uint64_t* src1_off, const uint64_t* src2_off, int n, uint8_t* blob,
+                       size_t capacity, size_t* blob_bytes, size_t* scratch_bytes, int threads);
 
 /* The constant tables of the colour conversions and of the final / 255, in the layout the device kernels read
  * (y3f_dtables below); uploaded once per device.  Returns the byte count (dst may be NULL). */

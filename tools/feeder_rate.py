@@ -139,6 +139,26 @@ def concurrent_feeders(args, lines):
                      '; %.2f ms of CPU per image' % (1e3 * sum(cpu) / (n * args.batches * args.batch_size)) if cpu else ''), flush=True)
 
 
+def timed_epochs(f, args, label):
+    """Whole epochs over the same files, each timed on its own (epoch 0 after 3 warm-up batches)."""
+    import torch
+    for epoch in range(args.epochs):
+        it = f.epoch(epoch)
+        images = 0
+        if epoch == 0:
+            for _ in range(3):
+                next(it)
+        torch.cuda.synchronize()
+        t0, c0 = time.perf_counter(), time.process_time()
+        for b in it:
+            images += len(b.image_ids)
+        torch.cuda.synchronize()
+        dt, cpu = time.perf_counter() - t0, time.process_time() - c0
+        stats = (' cache %r' % (f.cache.stats(),)) if f.cache is not None else ''
+        print('%s epoch %d: %5d images %7.0f images/s, %.2f ms of this process\'s CPU per image%s' % (
+            label, epoch, images, images / dt, 1e3 * cpu / images, stats), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--host-only', action='store_true', help="with --feeders: the host half only (no upload, no device)")
@@ -149,6 +169,10 @@ def main():
     ap.add_argument('--pixels', default='host', help="host,gpu: where the pixel work runs (Feeder(pixels=...); thread backend, "
                                                      "native=1 for gpu); with --feeders the first entry is used")
     ap.add_argument('--batches', type=int, default=12)
+    ap.add_argument('--cache_gb', type=float, default=0, help="Feeder(cache_bytes=...): keep decoded sources on the device "
+                                                                "(pixels=gpu only)")
+    ap.add_argument('--epochs', type=int, default=1, help="time this many epochs over the SAME files (the first 3 batches of "
+                                                           "epoch 0 are warm-up): with --cache_gb, epochs 1.. are cached ones")
     ap.add_argument('--batch_size', type=int, default=64)
     ap.add_argument('--check', action='store_true', help="first compare the first batch of a process-backed feeder with a "
                                                          "thread-backed one (same seed): they must be equal")
@@ -156,7 +180,10 @@ def main():
     import torch
     from yolov3_tensorflow_amd.feeder import Feeder
     lines = write_set(pathlib.Path(tempfile.mkdtemp()), 256)
-    lines = (lines * ((args.batches + 9) * args.batch_size // len(lines) + 1))[:(args.batches + 9) * args.batch_size]
+    if args.epochs > 1:          # an epoch is the 256 files once (more, distinct, when --batches asks for more)
+        lines = write_set(pathlib.Path(tempfile.mkdtemp()), max(256, args.batches * args.batch_size))
+    else:
+        lines = (lines * ((args.batches + 9) * args.batch_size // len(lines) + 1))[:(args.batches + 9) * args.batch_size]
     print('host threads available: %d' % len(os.sched_getaffinity(0)), flush=True)
     if args.feeders > 0:
         concurrent_feeders(args, lines)
@@ -181,8 +208,14 @@ def main():
                 for pixels in args.pixels.split(','):
                     if pixels == 'gpu' and (backend != 'thread' or native != '1'):
                         continue
+                    cache = int(args.cache_gb * (1 << 30)) if pixels == 'gpu' else 0
                     f = Feeder(lines, args.batch_size, 80, [416, 416], ANCHORS, mode='train', use_mix_up=True,
-                               num_threads=workers, prefetch=5, seed=1, backend=backend, pixels=pixels)
+                               num_threads=workers, prefetch=5, seed=1, backend=backend, pixels=pixels, cache_bytes=cache)
+                    if args.epochs > 1:
+                        timed_epochs(f, args, 'native=%s backend=%-7s workers=%3d pixels=%-4s cache=%gGB' % (
+                            native, backend, workers, pixels, args.cache_gb if cache else 0))
+                        f.close()
+                        continue
                     it = f.epoch(0)
                     for _ in range(3):              # pool start-up, pinned buffers
                         next(it)

@@ -81,6 +81,10 @@ def build_parser():
     # tf.data parameters (args.py:33-34)
     p.add_argument('--num_threads', type=int, default=10, help='threads decoding / augmenting / resizing images')
     p.add_argument('--prefetech_buffer', type=int, default=5, help='batches prepared ahead of the train step')
+    p.add_argument('--cache_sources_gb', type=float, default=0,
+                   help='above 0: decode every training image once and keep its 8-bit pixels in this many GB of device '
+                        'memory; later epochs read them there (same batches; needs the thread backend, the default). The '
+                        'validation feeder gets a cache of the same size of its own')
     p.add_argument('--feeder_backend', choices=['thread', 'process'], default=None,
                    help='feeder workers: threads (default; about 1,000 images/s per GPU) or processes filling page-locked '
                         'shared memory (past one interpreter, e.g. 32 workers: 3,300 images/s)')
@@ -115,6 +119,10 @@ def variables_to_restore(variables, include, exclude):
     return get_variables_to_restore(variables, include, exclude)
 
 
+def _cache_bytes(args):
+    return int(float(getattr(args, 'cache_sources_gb', 0) or 0) * (1 << 30))
+
+
 def validate(model, y3, args, lines):
     """mAP / recall / precision / losses over the validation file (train.py:171-214), batched on the device."""
     from yolov3_tensorflow_amd.utils import eval_utils
@@ -123,9 +131,13 @@ def validate(model, y3, args, lines):
     from yolov3_tensorflow_amd.feeder import Feeder
     meters = [AverageMeter() for _ in range(5)]
     val_preds = []
-    feeder = Feeder(lines, args.batch_size, args.class_num, args.img_size, args.anchors, mode='val',
-                    letterbox_resize=args.letterbox_resize, num_threads=args.num_threads, prefetch=args.prefetech_buffer,
-                    backend=getattr(args, 'feeder_backend', None))
+    feeder = getattr(args, 'val_feeder', None)      # (kept over the evaluations when it holds a source cache)
+    if feeder is None:
+        feeder = Feeder(lines, args.batch_size, args.class_num, args.img_size, args.anchors, mode='val',
+                        letterbox_resize=args.letterbox_resize, num_threads=args.num_threads, prefetch=args.prefetech_buffer,
+                        backend=getattr(args, 'feeder_backend', None), cache_bytes=_cache_bytes(args))
+        if feeder.cache_bytes > 0:
+            args.val_feeder = feeder
     for batch in feeder.epoch(0):
         with y3.variable_scope('yolov3'):
             fms = model.forward(batch.images, False)
@@ -246,7 +258,7 @@ def main(argv=None):
                     mode='train' if args.augment else 'val', shuffle=True,
                     multi_scale=args.multi_scale_train, use_mix_up=args.use_mix_up, letterbox_resize=args.letterbox_resize,
                     num_threads=args.num_threads, prefetch=args.prefetech_buffer, seed=args.seed, rank=rank, world=world,
-                    backend=args.feeder_backend)
+                    backend=args.feeder_backend, cache_bytes=_cache_bytes(args))
     for epoch in range(args.total_epoches):
         meters = [AverageMeter() for _ in range(5)]
         for i, batch in enumerate(feeder.epoch(epoch)):

@@ -163,6 +163,8 @@ PROTOTYPES = {
     "y3_process_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                POINTER(c_float), c_void_p, c_void_p, c_void_p]),
     "y3_feed_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int]),
+    "y3_feed_run_src": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                c_void_p, c_int, c_int]),
     "y3_jpeg_decode": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                c_void_p]),
     "y3_box_iou": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_void_p]),

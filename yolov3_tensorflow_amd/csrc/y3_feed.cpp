@@ -451,9 +451,10 @@ const float* unit_table() {          // v / 255 in float32 for v = 0..255
     return table.t;
 }
 
-int check_job(const y3f_job& j) {
-    if (!j.img1 || j.h1 < 1 || j.w1 < 1) return fail(Y3F_EINVAL, "sample: img1 is empty");
-    if (j.img2 && (j.h2 < 1 || j.w2 < 1)) return fail(Y3F_EINVAL, "sample: img2 is empty");
+// `ref1` / `ref2`: the source is read by reference (y3f_plan_batch_src), its pointer is not needed
+int check_job(const y3f_job& j, bool ref1 = false, bool ref2 = false) {
+    if ((!j.img1 && !ref1) || j.h1 < 1 || j.w1 < 1) return fail(Y3F_EINVAL, "sample: img1 is empty");
+    if ((j.img2 || ref2) && (j.h2 < 1 || j.w2 < 1)) return fail(Y3F_EINVAL, "sample: img2 is empty");
     if (j.win_w < 1 || j.win_h < 1 || j.res_w < 1 || j.res_h < 1 || j.out_w < 1 || j.out_h < 1)
         return fail(Y3F_EINVAL, "sample: empty window (%dx%d), resize target (%dx%d) or output (%dx%d)", j.win_w, j.win_h,
                     j.res_w, j.res_h, j.out_w, j.out_h);
@@ -468,8 +469,8 @@ int check_job(const y3f_job& j) {
 }
 
 // the part of the window that is not black canvas, as run_job hands it to the resampling filters
-Rect live_rect(const y3f_job& j) {
-    const int mh = j.img2 ? std::max(j.h1, j.h2) : j.h1, mw = j.img2 ? std::max(j.w1, j.w2) : j.w1;
+Rect live_rect(const y3f_job& j, bool has2) {
+    const int mh = has2 ? std::max(j.h1, j.h2) : j.h1, mw = has2 ? std::max(j.w1, j.w2) : j.w1;
     const int x_lo = std::max(j.win_x, j.off_x), x_hi = std::min(j.win_x + j.win_w, j.off_x + mw);
     Rect live = {std::max(0, x_lo - j.win_x), std::max(0, std::max(j.win_y, j.off_y) - j.win_y), std::max(0, x_hi - j.win_x),
                  std::max(0, std::min(j.win_y + j.win_h, j.off_y + mh) - j.win_y)};
@@ -639,17 +640,19 @@ int kernel_window(int in_size, int out_size, double filter_support, int o, int* 
     return (int)std::ceil(support) * 2 + 1;
 }
 
-int plan_geometry(const y3f_job& j, y3f_djob& d, size_t& blob, size_t& scratch) {
-    const int bad = check_job(j);
+// src1 / src2: the arena offset of the whole image (y3f_plan_batch_src) or Y3F_NOT_IN_ARENA: the visible rectangle is packed
+int plan_geometry(const y3f_job& j, uint64_t src1, uint64_t src2, y3f_djob& d, size_t& blob, size_t& scratch) {
+    const bool ref1 = src1 != Y3F_NOT_IN_ARENA, ref2 = src2 != Y3F_NOT_IN_ARENA;
+    const int bad = check_job(j, ref1, ref2);
     if (bad != Y3F_OK) return bad;
     memset(&d, 0, sizeof(d));
     const int sw = j.win_w, sh = j.win_h, dw = j.res_w, dh = j.res_h;
-    const Rect live = live_rect(j);
+    d.has2 = j.img2 != nullptr || ref2;
+    const Rect live = live_rect(j, d.has2 != 0);
     d.live_x0 = live.x0, d.live_y0 = live.y0, d.live_x1 = live.x1, d.live_y1 = live.y1;
     d.win_w = sw, d.win_h = sh;
     d.img_dx = j.win_x - j.off_x, d.img_dy = j.win_y - j.off_y;
     d.lam1 = j.lam1, d.lam2 = j.lam2;
-    d.has2 = j.img2 != nullptr;
     d.colour_on = j.colour.enabled != 0;
     d.res_w = dw, d.res_h = dh, d.out_w = j.out_w, d.out_h = j.out_h, d.pad_x = j.pad_x, d.pad_y = j.pad_y;
     d.pad_value = clamp_u8(j.pad_value), d.flip_x = j.flip_x != 0;
@@ -696,8 +699,11 @@ int plan_geometry(const y3f_job& j, y3f_djob& d, size_t& blob, size_t& scratch) 
             d.tmp_rows = std::max(0, std::min(row_last, live.y1) - d.tmp_y0);
         }
     }
-    d.img1_off = blob, blob += align16((size_t)d.r1_w * d.r1_h * 3);
-    d.img2_off = blob, blob += align16((size_t)d.r2_w * d.r2_h * 3);
+    d.img1_off = blob, d.img2_off = blob;
+    if (ref1) d.img1_off = src1, d.reserved[0] |= Y3F_SRC1_ARENA, d.reserved[1] = j.w1;
+    else blob += align16((size_t)d.r1_w * d.r1_h * 3), d.img2_off = blob;
+    if (d.has2 && ref2) d.img2_off = src2, d.reserved[0] |= Y3F_SRC2_ARENA, d.reserved[2] = j.w2;
+    else blob += align16((size_t)d.r2_w * d.r2_h * 3);
     d.jitter_off = blob, blob += d.colour_on ? 1024 : 0;
     d.xtab_off = blob, blob += align16(xtab);
     d.ytab_off = blob, blob += align16(ytab);
@@ -711,8 +717,8 @@ void fill_job(const y3f_job& j, const y3f_djob& d, uint8_t* blob) {
         for (int y = 0; y < r[3]; ++y)
             memcpy(blob + off + (size_t)y * r[2] * 3, img + ((size_t)(r[1] + y) * w + r[0]) * 3, (size_t)r[2] * 3);
     };
-    pack(j.img1, j.w1, &d.r1_x0, d.img1_off);
-    if (d.has2) pack(j.img2, j.w2, &d.r2_x0, d.img2_off);
+    if (!(d.reserved[0] & Y3F_SRC1_ARENA)) pack(j.img1, j.w1, &d.r1_x0, d.img1_off);
+    if (d.has2 && !(d.reserved[0] & Y3F_SRC2_ARENA)) pack(j.img2, j.w2, &d.r2_x0, d.img2_off);
     if (d.colour_on) {
         const Jitter J(j.colour);
         uint8_t* t = blob + d.jitter_off;
@@ -777,6 +783,11 @@ extern "C" {
 
 int y3f_plan_batch(const y3f_job* jobs, int n, uint8_t* blob, size_t capacity, size_t* blob_bytes, size_t* scratch_bytes,
                    int threads) {
+    return y3f_plan_batch_src(jobs, nullptr, nullptr, n, blob, capacity, blob_bytes, scratch_bytes, threads);
+}
+
+int y3f_plan_batch_src(const y3f_job* jobs, const uint64_t* src1_off, const uint64_t* src2_off, int n, uint8_t* blob,
+                       size_t capacity, size_t* blob_bytes, size_t* scratch_bytes, int threads) {
     if (n < 0 || (n && !jobs) || !blob_bytes || !scratch_bytes) return fail(Y3F_EINVAL, "plan_batch: bad arguments");
     try {
         std::vector<y3f_djob> recs((size_t)n);
@@ -785,7 +796,8 @@ int y3f_plan_batch(const y3f_job* jobs, int n, uint8_t* blob, size_t capacity, s
             if (jobs[i].out_w != jobs[0].out_w || jobs[i].out_h != jobs[0].out_h)
                 return fail(Y3F_EINVAL, "plan_batch: job %d writes %dx%d, job 0 %dx%d", i, jobs[i].out_w, jobs[i].out_h,
                             jobs[0].out_w, jobs[0].out_h);
-            const int rc = plan_geometry(jobs[i], recs[i], need, scratch);
+            const int rc = plan_geometry(jobs[i], src1_off ? src1_off[i] : Y3F_NOT_IN_ARENA,
+                                         src2_off ? src2_off[i] : Y3F_NOT_IN_ARENA, recs[i], need, scratch);
             if (rc != Y3F_OK) {
                 char message[sizeof(g_error)];
                 snprintf(message, sizeof(message), "job %d: %s", i, g_error);

@@ -24,11 +24,16 @@ constexpr int kCoefBits = 32 - 8 - 2;      // Pillow's PRECISION_BITS
 
 // ---- 1. one live pixel of the window: blend (mix-up), jitter (random_color_distort after its draws) -------------------
 // (wx, wy) in window coordinates, inside the live rectangle.  y3_feed.cpp: run_job step 1 + colour_run.
-Y3F_HD void window_pixel(const y3f_djob& d, const uint8_t* blob, const y3f_dtables& T, int wx, int wy, uint8_t out[3]) {
+// kArena: a source whose record says so (y3f_plan_batch_src) is a whole image in `arena`, read where it lies with its own row
+// stride; without kArena every source is a packed rectangle of the blob and `arena` is not looked at.
+template <bool kArena>
+Y3F_HD void window_pixel(const y3f_djob& d, const uint8_t* blob, const uint8_t* arena, const y3f_dtables& T, int wx, int wy,
+                         uint8_t out[3]) {
     const int ix = wx + d.img_dx, iy = wy + d.img_dy;
     const int ax = ix - d.r1_x0, ay = iy - d.r1_y0;
     const bool in1 = ax >= 0 && ax < d.r1_w && ay >= 0 && ay < d.r1_h;
     const uint8_t* a = blob + d.img1_off + ((size_t)ay * d.r1_w + ax) * 3;
+    if (kArena && (d.reserved[0] & Y3F_SRC1_ARENA)) a = arena + d.img1_off + ((size_t)iy * d.reserved[1] + ix) * 3;
     int r, g, b;
     if (!d.has2) {
         r = a[0], g = a[1], b = a[2];          // (the live rectangle of a single image lies inside it)
@@ -36,6 +41,7 @@ Y3F_HD void window_pixel(const y3f_djob& d, const uint8_t* blob, const y3f_dtabl
         const int bx = ix - d.r2_x0, by = iy - d.r2_y0;
         const bool in2 = bx >= 0 && bx < d.r2_w && by >= 0 && by < d.r2_h;
         const uint8_t* p2 = blob + d.img2_off + ((size_t)by * d.r2_w + bx) * 3;
+        if (kArena && (d.reserved[0] & Y3F_SRC2_ARENA)) p2 = arena + d.img2_off + ((size_t)iy * d.reserved[2] + ix) * 3;
         int px[3];
         for (int c = 0; c < 3; ++c) {
             float acc = 0.f;
@@ -79,6 +85,10 @@ Y3F_HD void window_pixel(const y3f_djob& d, const uint8_t* blob, const y3f_dtabl
         case 4: out[0] = qt; out[1] = p; out[2] = u; break;
         default: out[0] = u; out[1] = p; out[2] = qt; break;
     }
+}
+
+Y3F_HD void window_pixel(const y3f_djob& d, const uint8_t* blob, const y3f_dtables& T, int wx, int wy, uint8_t out[3]) {
+    window_pixel<false>(d, blob, nullptr, T, wx, wy, out);
 }
 
 // the window as the resize sees it: black canvas outside the live rectangle.  `win` holds the live part, rows packed.
@@ -195,6 +205,65 @@ Y3F_HD void output_pixel(const y3f_djob& d, const uint8_t* blob, const uint8_t* 
     int px[3] = {d.pad_value, d.pad_value, d.pad_value};
     if (rx >= 0 && rx < d.res_w && ry >= 0 && ry < d.res_h) resized_pixel(d, blob, win, tmp, rx, ry, px);
     out[0] = T.unit255[px[0]], out[1] = T.unit255[px[1]], out[2] = T.unit255[px[2]];
+}
+
+// ---- 5. is a record safe to run?  (y3_feed_run_src checks every record of its own copy before it launches anything) ------
+// Every byte the functions above read or write for `d` through the record's own fields lies inside a blob of blob_bytes, an
+// arena of arena_bytes (0: there is none) and a scratch of scratch_bytes.  Returns what is wrong, or nullptr.
+inline const char* record_fault(const y3f_djob& d, size_t blob_bytes, size_t arena_bytes, size_t scratch_bytes) {
+    const int64_t big = 1 << 20;                                    // y3f_sample's own bound on sizes
+    auto fits = [](uint64_t off, uint64_t bytes, size_t size) { return off <= size && bytes <= size - off; };
+    if (d.mode < Y3F_MODE_NEAREST || d.mode > Y3F_MODE_RESAMPLE) return "unknown mode";
+    if (d.win_w < 1 || d.win_h < 1 || d.win_w > big || d.win_h > big || d.out_w < 1 || d.out_h < 1 || d.out_w > big || d.out_h > big)
+        return "window or output size out of range";
+    if (d.res_w < 1 || d.res_h < 1 || d.pad_x < 0 || d.pad_y < 0 || (int64_t)d.pad_x + d.res_w > d.out_w ||
+        (int64_t)d.pad_y + d.res_h > d.out_h)
+        return "the resized image does not fit the output";
+    if (d.pad_value < 0 || d.pad_value > 255) return "pad value is no byte";
+    if (d.live_x0 < 0 || d.live_y0 < 0 || d.live_x0 > d.live_x1 || d.live_y0 > d.live_y1 || d.live_x1 > d.win_w || d.live_y1 > d.win_h)
+        return "live rectangle outside the window";
+    const int64_t lw = d.live_x1 - d.live_x0, lh = d.live_y1 - d.live_y0;
+    // sources: a rectangle of a whole image in the arena, or a packed rectangle in the blob
+    const int32_t* r[2] = {&d.r1_x0, &d.r2_x0};
+    const uint64_t off[2] = {d.img1_off, d.img2_off};
+    for (int s = 0; s < (d.has2 ? 2 : 1); ++s) {
+        const int64_t x0 = r[s][0], y0 = r[s][1], w = r[s][2], h = r[s][3], stride = d.reserved[1 + s];
+        if (x0 < 0 || y0 < 0 || w < 0 || h < 0 || x0 + w > big || y0 + h > big) return "source rectangle out of range";
+        if (w == 0 || h == 0) continue;                             // (never read: every pixel of it fails the inside test)
+        if (d.reserved[0] & (Y3F_SRC1_ARENA << s)) {
+            if (stride < x0 + w) return "arena row stride smaller than the rectangle's right edge";
+            if (!fits(off[s], (uint64_t)(((y0 + h - 1) * stride + x0 + w) * 3), arena_bytes)) return "source rectangle past the arena";
+        } else if (!fits(off[s], (uint64_t)(w * h * 3), blob_bytes)) {
+            return "packed source past the blob";
+        }
+    }
+    if (d.reserved[0] & ~(Y3F_SRC1_ARENA | Y3F_SRC2_ARENA)) return "unknown source flags";
+    if (!d.has2 && lw * lh > 0 &&                                  // a single image is read without an inside test
+        (d.live_x0 + (int64_t)d.img_dx < d.r1_x0 || d.live_x1 + (int64_t)d.img_dx > (int64_t)d.r1_x0 + d.r1_w ||
+         d.live_y0 + (int64_t)d.img_dy < d.r1_y0 || d.live_y1 + (int64_t)d.img_dy > (int64_t)d.r1_y0 + d.r1_h))
+        return "live rectangle outside the source";
+    if (d.colour_on && !fits(d.jitter_off, 1024, blob_bytes)) return "jitter maps past the blob";
+    // tables
+    uint64_t xtab = 0, ytab = 0;
+    if (d.mode == Y3F_MODE_NEAREST) xtab = (uint64_t)d.res_w * 4, ytab = (uint64_t)d.res_h * 4;
+    if (d.mode == Y3F_MODE_LINEAR) xtab = (uint64_t)d.res_w * 16, ytab = (uint64_t)d.res_h * 16;
+    int64_t hor = 0;
+    if (d.mode == Y3F_MODE_RESAMPLE) {
+        if (!d.horizontal && !d.vertical) return "a resampling job with no pass";
+        if (d.ksize_x < 0 || d.ksize_y < 0 || d.ksize_x > big || d.ksize_y > big) return "filter size out of range";
+        if (d.horizontal) {
+            xtab = (uint64_t)d.res_w * (2 + (uint64_t)d.ksize_x) * 4;
+            if (d.tmp_rows < 0 || (d.tmp_rows > 0 && (d.tmp_y0 < d.live_y0 || (int64_t)d.tmp_y0 + d.tmp_rows > d.live_y1)))
+                return "horizontal pass outside the live rows";
+            hor = (int64_t)d.tmp_rows * d.res_w;
+        }
+        if (d.vertical) ytab = (uint64_t)d.res_h * (2 + (uint64_t)d.ksize_y) * 4;
+    }
+    if ((xtab && (d.xtab_off % 4 || !fits(d.xtab_off, xtab, blob_bytes))) || (ytab && (d.ytab_off % 4 || !fits(d.ytab_off, ytab, blob_bytes))))
+        return "table past the blob";
+    if (!fits(d.win_off, (uint64_t)(lw * lh * 3), scratch_bytes) || !fits(d.tmp_off, (uint64_t)(hor * 3), scratch_bytes))
+        return "scratch too small";
+    return nullptr;
 }
 
 }  // namespace y3fpx

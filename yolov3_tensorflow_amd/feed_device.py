@@ -38,27 +38,41 @@ class DevicePixels(object):
             del self.busy[i]
         return torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8).pin_memory()
 
-    def run(self, pixel_jobs, threads=0):
-        """[PixelJob] (all with the same output size) -> float32 device tensor [n, out_h, out_w, 3]."""
+    def run(self, pixel_jobs, threads=0, cache=None):
+        """[PixelJob] (all with the same output size) -> float32 device tensor [n, out_h, out_w, 3].  `cache`: a
+        feed_cache.SourceCache on this device; every source it holds (or takes in now) is read from its arena by reference
+        (y3f_plan_batch_src + y3_feed_run_src: the same bytes), the others are packed into the blob as without one."""
         import torch
         n = len(pixel_jobs)
         if n == 0:
             raise ValueError("DevicePixels.run: no jobs")
         jobs = feed_native.job_array(pixel_jobs)
-        need, scratch_bytes = feed_native.plan_sizes(jobs, n)
-        pinned = self._take(need)
-        got, scratch_bytes = feed_native.plan_into(jobs, n, pinned.data_ptr(), pinned.numel(), threads)
-        assert got == need
-        out_h, out_w = pixel_jobs[0].job.out_h, pixel_jobs[0].job.out_w
+        src1 = src2 = None
         with torch.cuda.device(self.device):
+            if cache is not None:       # (inserts copy on the current stream, ahead of the kernels below)
+                src1 = [cache.resolve(pj.key1, pj.img1) for pj in pixel_jobs]
+                src2 = [cache.resolve(pj.key2, pj.img2) for pj in pixel_jobs]
+            need, scratch_bytes = feed_native.plan_sizes(jobs, n, src1, src2)
+            pinned = self._take(need)
+            got, scratch_bytes = feed_native.plan_into(jobs, n, pinned.data_ptr(), pinned.numel(), threads, src1, src2)
+            assert got == need
+            out_h, out_w = pixel_jobs[0].job.out_h, pixel_jobs[0].job.out_w
             blob = torch.empty(need, dtype=torch.uint8, device=self.device)
             blob.copy_(pinned[:need], non_blocking=True)
-            scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=self.device)
             out = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().y3_feed_run(fw.context(self.device), ctypes.c_void_p(blob.data_ptr()),
-                                              ctypes.c_void_p(pinned.data_ptr()), n, ctypes.c_void_p(self.tables.data_ptr()),
-                                              ctypes.c_void_p(scratch.data_ptr()), scratch.numel(),
-                                              ctypes.c_void_p(out.data_ptr()), out_h, out_w))
+            p = lambda t: ctypes.c_void_p(t.data_ptr())
+            if cache is None:
+                scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=self.device)
+                _lib.check(_lib.lib().y3_feed_run(fw.context(self.device), p(blob), ctypes.c_void_p(pinned.data_ptr()), n,
+                                                  p(self.tables), p(scratch), scratch.numel(), p(out), out_h, out_w))
+            else:                       # (the checked copy of the records goes behind the jobs' scratch)
+                scratch = torch.empty(scratch_bytes + 16 + n * ctypes.sizeof(feed_native.DJob), dtype=torch.uint8,
+                                      device=self.device)
+                arena = cache.arena
+                _lib.check(_lib.lib().y3_feed_run_src(fw.context(self.device), p(blob), need, ctypes.c_void_p(pinned.data_ptr()), n,
+                                                      p(self.tables), p(scratch), scratch.numel(),
+                                                      None if arena is None else p(arena), 0 if arena is None else arena.numel(),
+                                                      p(out), out_h, out_w))
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
         self.busy.append((ev, pinned))

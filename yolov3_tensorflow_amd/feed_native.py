@@ -61,6 +61,8 @@ PROTOTYPES = {
     "y3f_sample": (c_int, [POINTER(Job), c_void_p, c_void_p]),
     "y3f_sample_batch": (c_int, [POINTER(Job), c_int, POINTER(c_void_p), POINTER(c_void_p), c_int]),
     "y3f_plan_batch": (c_int, [POINTER(Job), c_int, c_void_p, c_size_t, POINTER(c_size_t), POINTER(c_size_t), c_int]),
+    "y3f_plan_batch_src": (c_int, [POINTER(Job), c_void_p, c_void_p, c_int, c_void_p, c_size_t, POINTER(c_size_t),
+                                   POINTER(c_size_t), c_int]),
     "y3f_device_tables": (c_size_t, [c_void_p, c_size_t]),
     "y3f_crop_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_int,
                                     c_int, c_void_p, POINTER(c_int32)]),
@@ -147,13 +149,23 @@ def colour_distort(img, draws):
     return out
 
 
+class SourceRef(object):
+    """A source image that is not in host memory: only its key (the file's path) and size are known; the pixels lie in a
+    device arena (feed_cache.SourceCache).  make_job takes one wherever it takes an image."""
+    __slots__ = ('key', 'shape')
+
+    def __init__(self, key, h, w):
+        self.key, self.shape = key, (int(h), int(w), 3)
+
+
 class PixelJob(object):
     """One y3f_job and the arrays its pointers refer to (kept alive with it): what parse_sample hands back instead of pixels
-    when the pixel work is left to the device (feeder.Feeder(pixels='gpu'))."""
-    __slots__ = ('job', 'img1', 'img2')
+    when the pixel work is left to the device (feeder.Feeder(pixels='gpu')).  img1 / img2 is None where the source is a
+    SourceRef (the job's pointer is NULL then); key1 / key2: what a source cache knows the source by (None: not cacheable)."""
+    __slots__ = ('job', 'img1', 'img2', 'key1', 'key2')
 
-    def __init__(self, job, img1, img2):
-        self.job, self.img1, self.img2 = job, img1, img2
+    def __init__(self, job, img1, img2, key1=None, key2=None):
+        self.job, self.img1, self.img2, self.key1, self.key2 = job, img1, img2, key1, key2
 
     @property
     def shape(self):          # (what collate() asks of an image)
@@ -165,8 +177,8 @@ def make_job(img1, img2=None, lam=1.0, colour=None, offset=(0, 0), window=None, 
     """The y3f_job of one sample (see the header for the geometry).  img2 / lam: the mix-up partner and img1's weight;
     colour: color_distort_draws' tuple or None; offset = (x, y) of the image on the black canvas; window = (x, y, w, h) on
     the canvas (default: the image); resized = (w, h) the window is resized to (default: out_size); out_size = (w, h)."""
-    a = _rgb8(img1)
-    b = _rgb8(img2) if img2 is not None else None
+    a = img1 if isinstance(img1, SourceRef) else _rgb8(img1)
+    b = img2 if img2 is None or isinstance(img2, SourceRef) else _rgb8(img2)
     if window is None:
         mh = max(a.shape[0], b.shape[0]) if b is not None else a.shape[0]
         mw = max(a.shape[1], b.shape[1]) if b is not None else a.shape[1]
@@ -176,9 +188,10 @@ def make_job(img1, img2=None, lam=1.0, colour=None, offset=(0, 0), window=None, 
     if resized is None:
         resized = out_size
     job = Job()
-    job.img1, job.h1, job.w1 = a.ctypes.data, a.shape[0], a.shape[1]
+    ref1, ref2 = isinstance(a, SourceRef), isinstance(b, SourceRef)
+    job.img1, job.h1, job.w1 = None if ref1 else a.ctypes.data, a.shape[0], a.shape[1]
     if b is not None:
-        job.img2, job.h2, job.w2 = b.ctypes.data, b.shape[0], b.shape[1]
+        job.img2, job.h2, job.w2 = None if ref2 else b.ctypes.data, b.shape[0], b.shape[1]
     job.lam1, job.lam2 = float(lam), 1. - float(lam)
     job.colour = make_colour(colour)
     job.off_x, job.off_y = int(offset[0]), int(offset[1])
@@ -187,7 +200,7 @@ def make_job(img1, img2=None, lam=1.0, colour=None, offset=(0, 0), window=None, 
     job.res_w, job.res_h = int(resized[0]), int(resized[1])
     job.out_w, job.out_h = int(out_size[0]), int(out_size[1])
     job.pad_x, job.pad_y, job.pad_value, job.flip_x = int(pad[0]), int(pad[1]), int(pad_value), int(bool(flip_x))
-    return PixelJob(job, a, b)
+    return PixelJob(job, None if ref1 else a, None if ref2 else b, a.key if ref1 else None, b.key if ref2 else None)
 
 
 def sample(img1, img2=None, lam=1.0, colour=None, offset=(0, 0), window=None, interp=1, resized=None, out_size=None,
@@ -213,28 +226,46 @@ def job_array(pixel_jobs):
     return arr
 
 
-def plan_sizes(jobs, n):
-    """(blob bytes, scratch bytes) y3f_plan_batch wants for these n jobs."""
+NOT_IN_ARENA = 2 ** 64 - 1      # Y3F_NOT_IN_ARENA
+
+
+def _offsets(offs, n):
+    """One of y3f_plan_batch_src's offset arguments: None, or n arena offsets (None / NOT_IN_ARENA: not in the arena)."""
+    if offs is None:
+        return None
+    arr = np.array([NOT_IN_ARENA if v is None else int(v) for v in offs], np.uint64)
+    if arr.shape != (n,):
+        raise ValueError("expected %d source offsets, got %s" % (n, arr.shape))
+    return arr
+
+
+def plan_sizes(jobs, n, src1=None, src2=None):
+    """(blob bytes, scratch bytes) y3f_plan_batch wants for these n jobs (src1 / src2: see plan_into)."""
+    return plan_into(jobs, n, None, 0, 0, src1, src2)
+
+
+def plan_into(jobs, n, blob_ptr, capacity, threads=0, src1=None, src2=None):
+    """Writes the batch's blob at blob_ptr if `capacity` suffices; returns (blob bytes, scratch bytes) either way.  With
+    src1 / src2 (per job: the arena offset of the whole image, or None) the plan reads those sources by reference
+    (y3f_plan_batch_src)."""
     blob_bytes, scratch_bytes = c_size_t(0), c_size_t(0)
-    check(lib().y3f_plan_batch(jobs, n, None, 0, ctypes.byref(blob_bytes), ctypes.byref(scratch_bytes), 0))
+    if src1 is None and src2 is None:
+        check(lib().y3f_plan_batch(jobs, n, blob_ptr, capacity, ctypes.byref(blob_bytes), ctypes.byref(scratch_bytes),
+                                   int(threads)))
+    else:
+        s1, s2 = _offsets(src1, n), _offsets(src2, n)
+        check(lib().y3f_plan_batch_src(jobs, None if s1 is None else s1.ctypes.data, None if s2 is None else s2.ctypes.data, n,
+                                       blob_ptr, capacity, ctypes.byref(blob_bytes), ctypes.byref(scratch_bytes), int(threads)))
     return blob_bytes.value, scratch_bytes.value
 
 
-def plan_into(jobs, n, blob_ptr, capacity, threads=0):
-    """Writes the batch's blob at blob_ptr if `capacity` suffices; returns (blob bytes, scratch bytes) either way."""
-    blob_bytes, scratch_bytes = c_size_t(0), c_size_t(0)
-    check(lib().y3f_plan_batch(jobs, n, blob_ptr, capacity, ctypes.byref(blob_bytes), ctypes.byref(scratch_bytes),
-                               int(threads)))
-    return blob_bytes.value, scratch_bytes.value
-
-
-def plan_batch(pixel_jobs, threads=0):
+def plan_batch(pixel_jobs, threads=0, src1=None, src2=None):
     """[PixelJob] -> (blob as a uint8 array, scratch bytes, the DJob records as a ctypes array view of the blob's head)."""
     n = len(pixel_jobs)
     jobs = job_array(pixel_jobs)
-    need, _ = plan_sizes(jobs, n)
+    need, _ = plan_sizes(jobs, n, src1, src2)
     blob = np.zeros(max(need, 16), np.uint8)
-    _, scratch = plan_into(jobs, n, blob.ctypes.data, blob.size, threads)
+    _, scratch = plan_into(jobs, n, blob.ctypes.data, blob.size, threads, src1, src2)
     recs = (DJob * n).from_buffer(blob)
     return blob, scratch, recs
 

@@ -30,6 +30,9 @@ rebuilt for one process per GPU with the device-resident target assignment of th
     work (liby3feed.so: y3f_plan_batch, native threads), uploads ONE blob of 8-bit sources and tables and runs y3_feed_run
     on the side stream (feed_device.DevicePixels) - the same bytes as the host path, 5 of the 5.9 ms a core spends per
     image moved to three launches of a few hundred microseconds per batch;
+  * cache_bytes > 0 (with pixels='gpu'): every file is decoded once; its 8-bit pixels stay in a device arena of that many
+    bytes (feed_cache.SourceCache, kept over the epochs, nothing evicted) and later uses read them there by reference
+    (y3f_plan_batch_src / y3_feed_run_src): no decode, no source bytes in the blob.  The same batches, byte for byte;
   * the consumer makes its compute stream wait for the copy's event (no host synchronisation) and runs `y3_process_box`
     for the whole batch on the device (utils.data_utils.process_box_batch: bit-exact against the reference's
     process_box), so the three y_true tensors (3.6 MB per 416x416 image - more than the image itself) never cross PCIe;
@@ -49,14 +52,15 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 
-def _worker_sample(job, out=None, defer=False):
+def _worker_sample(job, out=None, defer=False, cached=None):
     """One sample in a worker: job = (line or mix-up pair, [w, h], mode, letterbox, rng key).  A thread is handed `out`, its
     float32 slot of the batch buffer; a process returns the 8-bit image (a quarter of the bytes to pickle); `defer`: the
-    decoded sources and the pixel JOB come back, the pixels are left to the device."""
+    decoded sources and the pixel JOB come back, the pixels are left to the device; `cached`: path -> (h, w) of a source
+    the feeder's cache holds (it is not decoded again) or None."""
     from .utils.data_utils import parse_sample
     line, size, mode, letterbox, key = job
     return parse_sample(line, size, mode, letterbox, rng=np.random.RandomState(key % (2 ** 31)), prng=random.Random(key),
-                        as_uint8=out is None and not defer, out=out, defer=defer)
+                        as_uint8=out is None and not defer, out=out, defer=defer, cached=cached)
 
 
 _ATTACHED = {}        # (in a worker process) path of a shared batch buffer -> its mapping
@@ -239,7 +243,7 @@ class Batch(object):
 class Feeder(object):
     def __init__(self, lines, batch_size, class_num, img_size, anchors, mode='train', multi_scale=False, use_mix_up=False,
                  letterbox_resize=True, num_threads=10, prefetch=5, shuffle=None, seed=0, rank=0, world=1, interval=10,
-                 device=None, drop_remainder=False, backend=None, pixels=None):
+                 device=None, drop_remainder=False, backend=None, pixels=None, cache_bytes=0):
         self.lines = [l for l in lines if (l.strip() if isinstance(l, str) else l)]
         self.batch_size, self.class_num = int(batch_size), int(class_num)
         self.img_size, self.anchors = list(img_size), np.asarray(anchors, np.float32).reshape(9, 2)
@@ -270,6 +274,11 @@ class Feeder(object):
                 raise ValueError("pixels='gpu' runs with the thread backend and the native job builder (Y3_FEED_NATIVE=1): "
                                  "the workers hand decoded sources to the coordinator")
         self.pixels = pixels
+        self.cache_bytes = int(cache_bytes)
+        if self.cache_bytes < 0 or (self.cache_bytes > 0 and pixels != 'gpu'):
+            raise ValueError("cache_bytes > 0 keeps decoded sources on the device for the device's pixel work: it needs "
+                             "pixels='gpu' (thread backend, native job builder)")
+        self.cache = None           # feed_cache.SourceCache, made with the side stream's device; lives as long as the feeder
         self._pool = None
         self._side = None           # (device, side stream, DevicePixels or None)
 
@@ -347,6 +356,11 @@ class Feeder(object):
                 from .feed_device import DevicePixels
                 self._side = (dev, copy_stream, DevicePixels(dev))
             device_pixels = self._side[2]
+            if self.cache_bytes > 0 and (self.cache is None or self.cache.device != dev):
+                from .feed_cache import SourceCache
+                self.cache = SourceCache(dev, self.cache_bytes)
+        cache = self.cache if on_device and self.cache_bytes > 0 else None
+        cached = cache.shape_of if cache is not None else None
         in_place = self.backend == 'thread'
         buffers = _PinnedBuffers()
         shared = None if in_place else _SharedBuffers()
@@ -379,7 +393,7 @@ class Feeder(object):
                         entry = shared.take(shape) if shared is not None else None
                         if on_device:               # worker threads decode and draw; the pixels are left to the device
                             pinned, owner = None, None
-                            futs = [pool.submit(_worker_sample, job, None, True) for job in jobs]
+                            futs = [pool.submit(_worker_sample, job, None, True, cached) for job in jobs]
                         elif entry is not None:     # worker processes fill the shared, page-locked batch buffer
                             pinned, owner = entry['tensor'], (shared, entry)
                             futs = [pool.submit(_worker_sample_shared, job, entry['path'], shape, j)
@@ -405,7 +419,7 @@ class Feeder(object):
                         ids, _, boxes, labels, counts = collate(samples, out_images=slots)
                     with torch.cuda.stream(copy_stream):
                         if on_device:
-                            images = device_pixels.run([s[1] for s in samples], threads=min(self.num_threads, 8))
+                            images = device_pixels.run([s[1] for s in samples], threads=min(self.num_threads, 8), cache=cache)
                         else:
                             images = pinned.to(dev, non_blocking=True)
                         bx = torch.from_numpy(boxes).pin_memory().to(dev, non_blocking=True)

@@ -219,7 +219,8 @@ def fix_crop_labels():
     return os.environ.get('Y3_FIX_CROP_LABELS', '0') == '1'
 
 
-def parse_sample(line, img_size, mode, letterbox_resize, rng=None, prng=None, as_uint8=False, out=None, defer=False):
+def parse_sample(line, img_size, mode, letterbox_resize, rng=None, prng=None, as_uint8=False, out=None, defer=False,
+                 cached=None):
     """The image half of the reference's parse_data (utils/data_utils.py:118-172): read (PIL, RGB), mix-up when `line` is
     a pair, the 'train' augmentation chain (colour distortion, expansion, constrained crop, resize with a random
     interpolation, horizontal flip) or the plain 'val' resize.  Returns (img_idx, float32 RGB image in [0,1] of shape
@@ -231,23 +232,30 @@ def parse_sample(line, img_size, mode, letterbox_resize, rng=None, prng=None, as
     through data_aug's numpy / Pillow functions one augmentation at a time (Y3_FEED_NATIVE=0).  `out`: a [h, w, 3] array
     (uint8 with as_uint8, else float32) to write the image into - the native path fills it directly.  `defer`: return the
     pixel JOB (feed_native.PixelJob) in place of the image - the feeder then runs a whole batch of them on the device
-    (feed_device.DevicePixels: the same bytes)."""
+    (feed_device.DevicePixels: the same bytes).  `cached` (with defer): path -> (h, w) of an image whose pixels the caller
+    already holds on the device (feed_cache.SourceCache.shape_of), or None; such a file is not opened - every draw and all
+    box arithmetic need only (h, w) and the boxes - and the job refers to it (feed_native.SourceRef).  Every job carries
+    its sources' paths as key1 / key2."""
     from . import data_aug
     from .. import feed_native
+
+    def read(pic_path):
+        hw = cached(pic_path) if defer and cached is not None else None
+        return _read_rgb(pic_path) if hw is None else feed_native.SourceRef(pic_path, hw[0], hw[1])
     rng = rng if rng is not None else np.random
     train = str(mode) == 'train'
     width, height = int(img_size[0]), int(img_size[1])
     partner, lam = None, 1.0
     if not isinstance(line, (list, tuple)):
         img_idx, pic_path, boxes, labels, _, _ = parse_line(line)
-        img = _read_rgb(pic_path)
+        img, keys = read(pic_path), (pic_path, None)
         # expand the 2nd dimension, mix up weight default to 1.
         boxes = np.concatenate((boxes, np.full(shape=(boxes.shape[0], 1), fill_value=1., dtype=np.float32)), axis=-1)
     else:
         # the mix up case
         _, pic_path1, boxes1, labels1, _, _ = parse_line(line[0])
         img_idx, pic_path2, boxes2, labels2, _, _ = parse_line(line[1])
-        img, partner = _read_rgb(pic_path1), _read_rgb(pic_path2)
+        img, partner, keys = read(pic_path1), read(pic_path2), (pic_path1, pic_path2)
         lam, boxes = data_aug.mix_up_boxes(boxes1, boxes2, rng=rng)
         labels = np.concatenate((labels1, labels2))
     carry = train and fix_crop_labels()
@@ -295,6 +303,7 @@ def parse_sample(line, img_size, mode, letterbox_resize, rng=None, prng=None, as
         resized, pad = (fit_w, fit_h), (pad_x, pad_y)
     if defer:
         image = feed_native.make_job(img, partner, lam, colour, offset, window, interp, resized, (width, height), pad, 128, flip)
+        image.key1, image.key2 = keys
     else:
         image = feed_native.sample(img, partner, lam, colour, offset, window, interp, resized, (width, height), pad, 128, flip,
                                    out=out, as_float=not as_uint8)
