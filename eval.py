@@ -37,6 +37,7 @@ OPTIONS = (
     ('use_voc_07_metric', _flag, False, 'true: the 11-point VOC 2007 AP'),
     ('batch_size', int, 32, 'images per device batch (the reference evaluates one at a time)'),
     ('compute_dtype', str, 'f32_wino', 'f32_wino (exact fp32, Winograd 3x3 kernels) | f32 | f32_bf16x6 (docs/history_r01_r05.md 4.3-4.4)'),
+    ('map_on_device', _flag, False, 'true: match detections and compute AP on the device (eval_utils.DeviceEval, DESIGN.md 4.5)'),
 )
 
 
@@ -53,7 +54,7 @@ def main(argv=None):
     import torch
     import yolov3_tensorflow_amd as y3
     from yolov3_tensorflow_amd.feeder import Feeder
-    from yolov3_tensorflow_amd.utils.eval_utils import get_preds_batch, voc_eval, parse_gt_rec
+    from yolov3_tensorflow_amd.utils.eval_utils import get_preds_batch, voc_eval, parse_gt_rec, DeviceEval
     from yolov3_tensorflow_amd.utils import eval_utils
     from yolov3_tensorflow_amd.utils.misc_utils import (parse_anchors, read_class_names, AverageMeter, load_weights,
                                                         run_ops, Saver)
@@ -77,6 +78,11 @@ def main(argv=None):
     print('\n----------- start to eval -----------\n')
     meters = [AverageMeter() for _ in range(5)]      # total, xy, wh, conf, class
     val_preds = []
+    device_eval = None
+    if args.map_on_device:      # the detections never leave the device: every batch is appended to the evaluator's arena
+        eval_utils.gt_dict = {}
+        gt_dict = parse_gt_rec(args.eval_file, args.img_size, args.letterbox_resize)
+        device_eval = DeviceEval(gt_dict, list(gt_dict), args.class_num)
     # the reference's tf.data pipeline (eval.py:54-62: batch, py_func(get_batch_data) on num_threads workers, prefetch) is
     # the feeder in 'val' mode: decode + resize (cv2.INTER_LINEAR arithmetic, plain or letterboxed) on worker threads into
     # pinned buffers, side-stream upload and target assignment on the device, overlapped with the forward of the batch before
@@ -86,7 +92,8 @@ def main(argv=None):
         # host-side bookkeeping of a batch whose device work was enqueued one batch ago: by now its counts have usually
         # landed, so the device never waits for the host between two batches (the reference ran two sess.run per IMAGE)
         ids, dets, loss = done
-        val_preds.extend(get_preds_batch(ids, dets))
+        if device_eval is None:
+            val_preds.extend(get_preds_batch(ids, dets))
         for m, v in zip(meters, loss):
             m.update(float(v), len(ids))
 
@@ -97,6 +104,8 @@ def main(argv=None):
         loss = yolo_model.compute_loss(fms, batch.y_true)
         pb, _, _, ps = yolo_model.predict(fms, with_scores=True)
         dets = gpu_nms_batched(pb, ps, args.class_num, args.nms_topk, args.score_threshold, args.nms_threshold, lazy=True)
+        if device_eval is not None:
+            device_eval.add(batch.image_ids, dets)
         if in_flight is not None:
             consume(in_flight)
         in_flight = (batch.image_ids, dets, loss)
@@ -105,12 +114,21 @@ def main(argv=None):
     feeder.close()
 
     rec_total, prec_total, ap_total = AverageMeter(), AverageMeter(), AverageMeter()
-    eval_utils.gt_dict = {}
-    gt_dict = parse_gt_rec(args.eval_file, args.img_size, args.letterbox_resize)
+    table = None
+    if device_eval is not None:
+        table = device_eval.finish(iou_thres=0.5, use_07_metric=args.use_voc_07_metric)
+    else:
+        eval_utils.gt_dict = {}
+        gt_dict = parse_gt_rec(args.eval_file, args.img_size, args.letterbox_resize)
     print('mAP eval:')
     for ii in range(args.class_num):
-        npos, nd, rec, prec, ap = voc_eval(gt_dict, val_preds, ii, iou_thres=0.5,
-                                           use_07_metric=args.use_voc_07_metric)
+        if table is not None:
+            npos, nd, rec, prec, ap = (float(v) for v in table[ii])
+            if nd == 1e-6:
+                print('no box, ignore')
+        else:
+            npos, nd, rec, prec, ap = voc_eval(gt_dict, val_preds, ii, iou_thres=0.5,
+                                               use_07_metric=args.use_voc_07_metric)
         rec_total.update(rec, npos)
         prec_total.update(prec, nd)
         ap_total.update(ap, 1)
@@ -121,7 +139,10 @@ def main(argv=None):
     print("recall: {:.3f}, precision: {:.3f}".format(rec_total.average, prec_total.average))
     print("total_loss: {:.3f}, loss_xy: {:.3f}, loss_wh: {:.3f}, loss_conf: {:.3f}, loss_class: {:.3f}".format(
         *[m.average for m in meters]))
-    return {'mAP': mAP, 'val_preds': val_preds, 'loss': [m.average for m in meters], 'gt_dict': gt_dict}
+    out = {'mAP': mAP, 'val_preds': val_preds, 'loss': [m.average for m in meters], 'gt_dict': gt_dict}
+    if table is not None:
+        out['table'] = table
+    return out
 
 
 if __name__ == '__main__':

@@ -567,6 +567,47 @@ int y3_jpeg_decode(y3_ctx* ctx, const void* blob_dev, size_t blob_bytes, const s
 int y3_box_iou(y3_ctx* ctx, const float* pred_boxes, long long num_pred, const float* true_boxes, int num_true,
                float* iou);
 
+/* PASCAL VOC mAP on the device: utils/eval_utils.py:235-261 (`get_preds_gpu`'s rows) and :312-423 (`voc_ap`, `voc_eval`),
+ * as restated in yolov3_tensorflow_amd/utils/eval_utils.py:123-146 and :184-244, on the tensors y3_nms leaves in HBM.
+ * All three are asynchronous on the context's stream; every index read from device memory is clamped to the extents
+ * passed here before it addresses anything.  Arithmetic is float64 in voc_eval's operation order, without contraction.
+ *
+ * y3_voc_append (eval_utils.py:235-261): rows k < out_counts[i] of batch image i = 0..n-1 of one y3_nms result
+ *   (cap = its per-image capacity) are appended, images ascending and rows ascending inside an image, to the caller's
+ *   arena: arena_box f64 [capacity_rows][4], arena_score f64 [capacity_rows], arena_label / arena_image int32
+ *   [capacity_rows] (image_index[i] is what lands in arena_image).  fp32 widens to fp64 exactly.  state: two int32 device
+ *   words the caller zeroes once: [0] rows in the arena, [1] rows that did not fit (not written; saturates at 2^31 - 1).
+ *   A row's position is state[0] plus an exclusive scan of the counts inside the kernel: nothing waits for the host.
+ *
+ * y3_voc_match (eval_utils.py:383-413): order[r] = the arena row of rank r, the rows sorted by (label ascending, score
+ *   descending, row ascending); the first *n_rows_dev ranks are detections (NULL: all `rows`).  Ground truth as a CSR over
+ *   image indices: gt_start int32 [num_images + 1], gt_box f64 [num_gt][4], gt_label int32 [num_gt].  Per rank: the first
+ *   maximum of the pixel-inclusive IoU over the image's objects of the detection's class, in ground-truth order; it is a
+ *   candidate when that IoU > iou_thres; the candidate of smallest rank per object (a 32-bit atomicMin on a claim word,
+ *   whose result does not depend on arrival order) is the true positive, every other detection a false positive - there
+ *   is no second choice of object.  Writes tp uint8 [rows] (0 past the detections) and seg_start int32 [class_num + 1],
+ *   the first rank of every class.  scratch: y3_voc_match_scratch_bytes(rows, num_gt).
+ *
+ * y3_voc_ap (eval_utils.py:312-340 and :415-423): out f64 [class_num][5] = (npos, nd, recall, precision, ap) per class;
+ *   (1e-6, 1e-6, 0, 0, 0) for a class without detections; recall and area AP are NaN, precision 0 and the 11-point AP 0
+ *   for a class with detections and no object, like numpy's.  One workgroup per class walks its segment in passes of
+ *   y3_voc_ap_pass() ranks.  use_07_metric: the 11-point metric with thresholds_host11 (HOST array: the eleven doubles of
+ *   np.arange(0., 1.1, 0.1)), added as ap + p / 11.; else the area under the precision envelope, summed in a fixed order
+ *   (within nd * 2^-52 of numpy's pairwise sum).  Same bits in every run.  scratch: y3_voc_ap_scratch_bytes(rows). */
+int y3_voc_append(y3_ctx* ctx, const float* out_boxes, const float* out_scores, const int32_t* out_labels,
+                  const int32_t* out_counts, const int32_t* image_index, int n, int cap, double* arena_box,
+                  double* arena_score, int32_t* arena_label, int32_t* arena_image, int capacity_rows, int32_t* state);
+size_t y3_voc_match_scratch_bytes(int rows, int num_gt);
+int y3_voc_match(y3_ctx* ctx, const double* arena_box, const int32_t* arena_label, const int32_t* arena_image,
+                 const int32_t* order, int rows, const int32_t* n_rows_dev, const int32_t* gt_start, const double* gt_box,
+                 const int32_t* gt_label, int num_images, int num_gt, int class_num, double iou_thres, void* scratch,
+                 size_t scratch_bytes, uint8_t* tp, int32_t* seg_start);
+int y3_voc_ap_pass(void);
+size_t y3_voc_ap_scratch_bytes(int rows);
+int y3_voc_ap(y3_ctx* ctx, const uint8_t* tp, const int32_t* seg_start, int rows, const int32_t* gt_label, int num_gt,
+              int class_num, int use_07_metric, const double* thresholds_host11, void* scratch, size_t scratch_bytes,
+              double* out);
+
 /* K11: g <- g*grad_scale + weight_decay*w (slim.l2_regularizer, model.py:49) ; g <- tf.clip_by_norm(g, clip)
  * (train.py:113-114) ; TF1 update rule (utils/misc_utils.py:151-161).  kind: 0 sgd, 1 momentum (slot0 =
  * accumulator), 2 adam (slot0 = m, slot1 = v, decay = beta1, lr = lr_t), 3 rmsprop (slot0 = ms, slot1 = mom).

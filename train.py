@@ -107,6 +107,8 @@ def build_parser():
     p.add_argument('--nms_topk', type=int, default=150)
     p.add_argument('--eval_threshold', type=float, default=0.5)
     p.add_argument('--use_voc_07_metric', type=_bool, default=False)
+    p.add_argument('--map_on_device', type=_bool, default=False,
+                   help='validation: match detections and compute AP on the device (eval_utils.DeviceEval)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compute_dtype', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'], default='f32',
                    help='train-step mode: fp32-accurate modes, or bf16 = mixed precision on the bf16 matrix pipe')
@@ -138,22 +140,37 @@ def validate(model, y3, args, lines):
                         backend=getattr(args, 'feeder_backend', None), cache_bytes=_cache_bytes(args))
         if feeder.cache_bytes > 0:
             args.val_feeder = feeder
+    on_device = bool(getattr(args, 'map_on_device', False))
+    device_eval = None
+    if on_device:       # the detections stay in HBM: each batch is appended to the evaluator's arena, one table comes back
+        eval_utils.gt_dict = {}
+        gt = eval_utils.parse_gt_rec(args.val_file, args.img_size, args.letterbox_resize)
+        device_eval = eval_utils.DeviceEval(gt, list(gt), args.class_num)
     for batch in feeder.epoch(0):
         with y3.variable_scope('yolov3'):
             fms = model.forward(batch.images, False)
         loss = model.compute_loss(fms, batch.y_true)
         pb, _, _, ps = model.predict(fms, with_scores=True)
-        dets = gpu_nms_batched(pb, ps, args.class_num, args.nms_topk, args.score_threshold, args.nms_threshold)
-        val_preds.extend(eval_utils.get_preds_batch(batch.image_ids, dets))
+        dets = gpu_nms_batched(pb, ps, args.class_num, args.nms_topk, args.score_threshold, args.nms_threshold, lazy=on_device)
+        if on_device:
+            device_eval.add(batch.image_ids, dets)
+        else:
+            val_preds.extend(eval_utils.get_preds_batch(batch.image_ids, dets))
         for m, v in zip(meters, loss):
             m.update(float(v), len(batch.image_ids))
-    eval_utils.gt_dict = {}
-    gt = eval_utils.parse_gt_rec(args.val_file, args.img_size, args.letterbox_resize)
+    if on_device:
+        table = device_eval.finish(iou_thres=args.eval_threshold, use_07_metric=args.use_voc_07_metric)
+    else:
+        eval_utils.gt_dict = {}
+        gt = eval_utils.parse_gt_rec(args.val_file, args.img_size, args.letterbox_resize)
     rec_total, prec_total, ap_total = AverageMeter(), AverageMeter(), AverageMeter()
     info = ''
     for ii in range(args.class_num):
-        npos, nd, rec, prec, ap = eval_utils.voc_eval(gt, val_preds, ii, iou_thres=args.eval_threshold,
-                                                      use_07_metric=args.use_voc_07_metric)
+        if on_device:
+            npos, nd, rec, prec, ap = (float(v) for v in table[ii])
+        else:
+            npos, nd, rec, prec, ap = eval_utils.voc_eval(gt, val_preds, ii, iou_thres=args.eval_threshold,
+                                                          use_07_metric=args.use_voc_07_metric)
         info += 'EVAL: Class {}: Recall: {:.4f}, Precision: {:.4f}, AP: {:.4f}\n'.format(ii, rec, prec, ap)
         rec_total.update(rec, npos)
         prec_total.update(prec, nd)

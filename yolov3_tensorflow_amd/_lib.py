@@ -4,7 +4,7 @@ The product path has NO fallback: if the HIP library is missing or fails to load
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("Y3_LIB_PATH") or os.path.join(HERE, "csrc", "libyolo355.so")   # (override: probe builds)
@@ -168,6 +168,15 @@ PROTOTYPES = {
     "y3_jpeg_decode": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                c_void_p]),
     "y3_box_iou": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_void_p]),
+    "y3_voc_append": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_int, c_void_p]),
+    "y3_voc_match_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "y3_voc_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_int, c_int, c_int, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "y3_voc_ap_pass": (c_int, []),
+    "y3_voc_ap_scratch_bytes": (c_size_t, [c_int]),
+    "y3_voc_ap": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p,
+                          c_size_t, c_void_p]),
     "y3_optimizer_scratch_bytes": (c_size_t, []),
     "y3_clip_update": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float,
                                c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p]),

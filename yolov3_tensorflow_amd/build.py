@@ -36,6 +36,7 @@ SOURCES = [
     ("y3_wgrad_wino.hip", []),
     ("y3_feed_gpu.hip", ["-ffp-contract=off"]),
     ("y3_jpeg.hip", []),
+    ("y3_voc.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -95,6 +96,7 @@ def needs_build():
         os.path.join(CSRC, "y3_net.h"),
         os.path.join(CSRC, "y3_feed_px.h"),
         os.path.join(CSRC, "y3_jpeg_px.h"),
+        os.path.join(CSRC, "y3_voc_px.h"),
         os.path.join(HERE, "..", "include", "yolo355_jpeg.h"),
         os.path.join(HERE, "..", "include", "yolo355_feed.h"),
         os.path.join(HERE, "..", "include", "yolo355.h"),

@@ -242,3 +242,142 @@ def voc_eval(gt_dict, val_preds, classidx, iou_thres=0.5, use_07_metric=False):
     prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
     ap = voc_ap(rec, prec, use_07_metric)
     return npos, nd, tp[-1] / float(npos), tp[-1] / float(nd), ap
+
+
+class DeviceEval(object):
+    """voc_eval for every class at once on the device (y3_voc_append / y3_voc_match / y3_voc_ap, include/yolo355.h):
+    the detections stay where the NMS kernels left them, and one [class_num, 5] table comes back.
+
+        ev = DeviceEval(gt_dict, image_ids, class_num)
+        ev.add(batch_image_ids, gpu_nms_batched(..., lazy=True))      # per batch; nothing waits for the host
+        table = ev.finish(iou_thres=0.5, use_07_metric=False)         # rows (npos, nd, recall, precision, ap)
+
+    A row of the table is what voc_eval(gt_dict, val_preds, c, iou_thres, use_07_metric) returns for the rows
+    get_preds_batch would have built, with two differences in the last bits' provenance:
+      - order: voc_eval ranks with np.argsort(-score), whose default sort is not stable; here the rank order is stable -
+        descending score, then ascending row in arrival (append) order.  For distinct scores within a class the two orders
+        are the same order;
+      - the area AP is summed in a fixed order of its own, so it lies within nd * 2**-52 of voc_ap's np.sum (pairwise);
+        npos, nd, recall, precision and the 11-point AP are the same float64 values.
+    Matching arithmetic is float64 on the device in voc_eval's operation order; ground-truth boxes stay float64 (parse_gt_rec's
+    letterboxed values are not fp32 numbers), detection boxes and scores are the NMS kernel's fp32 values widened exactly.
+    The table is bit-identical from run to run.
+
+    gt_dict: parse_gt_rec's dict.  image_ids: the ids of the set, each a key of gt_dict (ValueError otherwise); their order
+    fixes the image index inside the arena.  capacity_rows: detections the arena holds (48 bytes each; default 1,024 per
+    image); finish raises when more were added.  arena: caller-owned (box f64 [R,4], score f64 [R], label i32 [R],
+    image i32 [R]) device tensors to use instead of allocating them.
+    """
+
+    def __init__(self, gt_dict, image_ids, class_num, capacity_rows=None, arena=None, device=None):
+        import torch
+        from .. import framework as fw
+        self.class_num = int(class_num)
+        if self.class_num <= 0:
+            raise ValueError("DeviceEval: class_num must be positive")
+        self._index, starts, boxes, labels = {}, [0], [], []
+        for img_id in image_ids:
+            if img_id not in gt_dict:
+                raise ValueError("DeviceEval: image id %r is not in gt_dict" % (img_id,))
+            if img_id in self._index:
+                raise ValueError("DeviceEval: image id %r is listed twice" % (img_id,))
+            self._index[img_id] = len(self._index)
+            for obj in gt_dict[img_id]:
+                boxes.append([float(v) for v in obj[:4]])
+                labels.append(int(obj[-1]) if obj[-1] == int(obj[-1]) else -1)
+            starts.append(len(labels))
+        if not self._index:
+            raise ValueError("DeviceEval: no image")
+        self.num_gt = len(labels)
+        self._dev = torch.device(device) if device is not None else fw.default_device()
+        to_dev = lambda a: torch.from_numpy(a).to(self._dev)
+        self._gt_start = to_dev(np.asarray(starts, np.int32))
+        self._gt_box = to_dev(np.asarray(boxes or [[0.] * 4], np.float64).reshape(-1, 4))
+        self._gt_label = to_dev(np.asarray(labels or [-1], np.int32))
+        R = int(capacity_rows) if capacity_rows is not None else 1024 * len(self._index)
+        if not 0 < R < 2 ** 31:
+            raise ValueError("DeviceEval: capacity_rows must be in 1 .. 2**31 - 1")
+        self.capacity_rows = R
+        if arena is None:
+            arena = (torch.zeros((R, 4), dtype=torch.float64, device=self._dev), torch.zeros(R, dtype=torch.float64, device=self._dev),
+                     torch.zeros(R, dtype=torch.int32, device=self._dev), torch.zeros(R, dtype=torch.int32, device=self._dev))
+        for t, dtype, shape in zip(arena, (torch.float64, torch.float64, torch.int32, torch.int32), ((R, 4), (R,), (R,), (R,))):
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device.type != 'cuda':
+                raise ValueError("DeviceEval: arena tensors must be contiguous device tensors f64 [R,4], f64 [R], i32 [R], i32 [R]")
+        self._arena = tuple(arena)
+        self._state = torch.zeros(2, dtype=torch.int32, device=self._dev)        # rows in the arena, rows that did not fit
+
+    def _indices(self, image_ids_of_batch):
+        try:
+            return [self._index[i] for i in image_ids_of_batch]
+        except KeyError as e:
+            raise ValueError("DeviceEval: image id %r is not in gt_dict" % (e.args[0],))
+
+    def add(self, image_ids_of_batch, detections):
+        """Append one batch: `detections` is what gpu_nms_batched(..., lazy=True) / yolov3.detect returned (it is not
+        materialised), or the (boxes [n,cap,4], scores [n,cap], labels [n,cap], counts [n]) device tensors themselves."""
+        import torch
+        from .. import _lib, framework as fw
+        ob, osc, ol, cnt = detections.device_tensors() if hasattr(detections, 'device_tensors') else detections
+        n, cap = int(ob.shape[0]), int(ob.shape[1])
+        idx = self._indices(image_ids_of_batch)
+        if len(idx) != n or tuple(osc.shape) != (n, cap) or tuple(ol.shape) != (n, cap) or tuple(cnt.shape) != (n,):
+            raise ValueError("DeviceEval.add: %d image ids for detections of shapes %s %s %s %s" % (
+                len(idx), tuple(ob.shape), tuple(osc.shape), tuple(ol.shape), tuple(cnt.shape)))
+        if ob.dtype != torch.float32 or osc.dtype != torch.float32 or ol.dtype != torch.int32 or cnt.dtype != torch.int32:
+            raise ValueError("DeviceEval.add: detections must be fp32 boxes and scores, int32 labels and counts")
+        img = torch.tensor(idx, dtype=torch.int32).pin_memory().to(self._dev, non_blocking=True)
+        box, score, label, image = self._arena
+        _lib.check(_lib.lib().y3_voc_append(fw.context(self._dev), fw.ptr(ob), fw.ptr(osc), fw.ptr(ol), fw.ptr(cnt), fw.ptr(img), n,
+                                            cap, fw.ptr(box), fw.ptr(score), fw.ptr(label), fw.ptr(image), self.capacity_rows,
+                                            fw.ptr(self._state)))
+
+    def add_rows(self, image_ids, boxes, scores, labels):
+        """Append rows that are already on the host as float64 (one image id per row): the route of stored reference vectors,
+        whose boxes and scores are not fp32 numbers.  Plumbing only; synchronises."""
+        import torch
+        k = len(image_ids)
+        at = int(self._state[0].item())
+        if at + k > self.capacity_rows:
+            raise ValueError("DeviceEval.add_rows: %d rows do not fit behind %d of %d" % (k, at, self.capacity_rows))
+        box, score, label, image = self._arena
+        box[at:at + k] = torch.from_numpy(np.asarray(boxes, np.float64).reshape(k, 4)).to(self._dev)
+        score[at:at + k] = torch.from_numpy(np.asarray(scores, np.float64).reshape(k)).to(self._dev)
+        label[at:at + k] = torch.from_numpy(np.asarray(labels, np.int32).reshape(k)).to(self._dev)
+        image[at:at + k] = torch.from_numpy(np.asarray(self._indices(image_ids), np.int32)).to(self._dev)
+        self._state[0] += k
+
+    def finish(self, iou_thres=0.5, use_07_metric=False):
+        """The [class_num, 5] float64 table of (npos, nd, recall, precision, ap).  One device -> host copy (the table with the
+        arena's two counters behind it); raises Y3Error when rows were dropped for lack of capacity."""
+        import ctypes
+        import torch
+        from .. import _lib, framework as fw
+        L, ctx, dev, R, C = _lib.lib(), fw.context(self._dev), self._dev, self.capacity_rows, self.class_num
+        box, score, label, image = self._arena
+        # plumbing: rank order (label ascending, score descending, row ascending) from two stable sorts; the rows past the
+        # arena's count take the label C and so rank behind every detection.  Negating a float64 is exact.
+        live = torch.arange(R, device=dev, dtype=torch.int32) < self._state[0]
+        by_score = torch.sort(-score, stable=True).indices
+        key = torch.where(live, label, torch.full_like(label, C))[by_score]
+        order = by_score[torch.sort(key, stable=True).indices].to(torch.int32).contiguous()
+        m_bytes, a_bytes = L.y3_voc_match_scratch_bytes(R, self.num_gt), L.y3_voc_ap_scratch_bytes(R)
+        scratch = torch.empty(max(m_bytes, a_bytes), dtype=torch.uint8, device=dev)
+        tp = torch.empty(R, dtype=torch.uint8, device=dev)
+        seg = torch.empty(C + 1, dtype=torch.int32, device=dev)
+        out = torch.zeros((C + 1, 5), dtype=torch.float64, device=dev)
+        _lib.check(L.y3_voc_match(ctx, fw.ptr(box), fw.ptr(label), fw.ptr(image), fw.ptr(order), R, fw.ptr(self._state),
+                                  fw.ptr(self._gt_start), fw.ptr(self._gt_box), fw.ptr(self._gt_label), len(self._index),
+                                  self.num_gt, C, ctypes.c_double(iou_thres), fw.ptr(scratch), ctypes.c_size_t(m_bytes), fw.ptr(tp),
+                                  fw.ptr(seg)))
+        thresholds = (ctypes.c_double * 11)(*np.arange(0., 1.1, 0.1))
+        _lib.check(L.y3_voc_ap(ctx, fw.ptr(tp), fw.ptr(seg), R, fw.ptr(self._gt_label), self.num_gt, C, int(bool(use_07_metric)),
+                               thresholds, fw.ptr(scratch), ctypes.c_size_t(a_bytes), fw.ptr(out)))
+        out[C, 0:2] = self._state.to(torch.float64)
+        table = out.cpu().numpy()
+        fw.check_context(dev)
+        rows, lost = int(table[C, 0]), int(table[C, 1])
+        if lost:
+            raise _lib.Y3Error("DeviceEval: %d detections did not fit the arena's %d rows (%d kept): raise capacity_rows" % (
+                lost, R, rows))
+        return table[:C].copy()

@@ -38,9 +38,17 @@ class LazyDetections(object):
     on first access - so a caller can enqueue the next batch's forward before it reads this batch's detections, and no
     host round trip sits between two device batches (eval.py:114-123 did one per image)."""
 
-    def __init__(self, tensors, counts_host, event, device, return_index):
+    def __init__(self, tensors, counts_host, event, device, return_index, counts_dev=None):
         self._t, self._cnt, self._ev, self._dev, self._ri = tensors, counts_host, event, device, return_index
         self._items = None
+        self._hbm = tensors[:3] + (counts_dev,)
+
+    def device_tensors(self):
+        """(boxes [n,cap,4], scores [n,cap], labels [n,cap], counts [n]) as y3_nms left them in HBM, for a consumer that stays
+        on the device (eval_utils.DeviceEval.add).  Nothing waits for the host and nothing is materialised."""
+        if self._hbm[3] is None:
+            raise ValueError("these detections were built without their device counts")
+        return self._hbm
 
     def _materialise(self):
         if self._items is None:
@@ -123,7 +131,7 @@ def gpu_nms_batched(boxes, scores, num_classes, max_boxes=50, score_thresh=0.5, 
         cnt_h.copy_(cnt, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(b.device))
-        return LazyDetections((ob, osc, ol, oi), cnt_h, ev, b.device, return_index)
+        return LazyDetections((ob, osc, ol, oi), cnt_h, ev, b.device, return_index, counts_dev=cnt)
     cnt_h = cnt.cpu().tolist()
     fw.check_context(b.device)      # the stream is idle here: surface a device-side failure of the forward, if any
     out = []
