@@ -440,7 +440,11 @@ int y3_pad_channels(y3_ctx* ctx, const float* src, int c_src, long long rows, in
 /* K10: loss_layer forward + backward for one scale (model.py:192-304, box_iou :307-345).
  * feature_map [n,gh,gw,3*(5+C)], y_true [n,gh,gw,3,6+C] (utils/data_utils.py:69-113 layout), anchors3 = the
  * 3 (w,h) pairs of this scale.  loss4 (device, 4 floats: xy, wh, conf, class; each already divided by N)
- * is overwritten or accumulated; grad [n,gh,gw] x grad_stride receives d(sum of the four)/d(feature_map). */
+ * is overwritten or accumulated; grad [n,gh,gw] x grad_stride receives d(sum of the four)/d(feature_map): the first
+ * 3*(5+C) floats of each row are written, the pad lanes behind them are left as they were.
+ * The ignore mask takes the best IoU over every ground-truth box of the image on this scale: there is no limit on their
+ * number (up to gh*gw*3, one per record), and the result does not depend on the order in which the boxes were collected,
+ * so it is the same bits from run to run. */
 size_t y3_loss_scratch_bytes(int n, int gh, int gw);
 int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
                   int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,

@@ -41,6 +41,7 @@ class TrainGraph(object):
         self.batch_stats = OrderedDict()   # conv name -> (mean, biased var, unbiased var)
         self.trace = OrderedDict()         # conv name -> activation (NCHW), for per-layer checks
         self.keep_trace = True             # False: large no-grad forwards (bs=64 @416 in fp64 would pin ~48 GB)
+        self.iou_margins = None            # a list: loss_layer appends each call's smallest |best IoU - 0.5|
 
     # ---- graph --------------------------------------------------------------------------------------
     def _conv(self, x, filters, k, stride=1, bn=True, act=True):
@@ -141,13 +142,17 @@ class TrainGraph(object):
         offset, pred_boxes, conf_logits, prob_logits = self.reorg(fm, anchors)
         object_mask = y_true[..., 4:5]
         ignore = []
+        margin = float('inf')
         for n in range(N):
             valid = y_true[n, ..., 0:4][object_mask[n, ..., 0] > 0.5]
             if valid.shape[0] == 0:
                 ignore.append(torch.ones(gh, gw, 3, dtype=self.dtype))     # reduce_max over empty = -inf < 0.5
                 continue
-            iou = self.box_iou(pred_boxes[n].detach(), valid)
-            ignore.append((iou.max(dim=-1).values < 0.5).to(self.dtype))
+            best = self.box_iou(pred_boxes[n].detach(), valid).max(dim=-1).values
+            margin = min(margin, float((best - 0.5).abs().min()))
+            ignore.append((best < 0.5).to(self.dtype))
+        if self.iou_margins is not None:
+            self.iou_margins.append(margin)
         ignore_mask = torch.stack(ignore).unsqueeze(-1)
         pred_xy, pred_wh = pred_boxes[..., 0:2], pred_boxes[..., 2:4]
         true_xy = y_true[..., 0:2] / rr - offset
@@ -216,10 +221,14 @@ def apply_update(kind, w, g, slots, lr, step, momentum=0.9, decay=0.9, beta1=0.9
 
 def train_step(params, x, y_trues, anchors, class_num=80, optimizer='sgd', lr=1e-4, weight_decay=5e-4,
                bn_decay=0.99, clip=100.0, update_scopes=None, use_label_smooth=False, use_focal_loss=False,
-               dtype=torch.float64, slots=None, step=1, masks=None):
+               dtype=torch.float64, slots=None, step=1, masks=None, iou_margins=False):
     """One reference train step.  Returns dict(loss=[5 floats], l2, grads, new_params, batch_stats).
-    masks: see TrainGraph (LeakyReLU branches imposed from outside)."""
+    masks: see TrainGraph (LeakyReLU branches imposed from outside).
+    iou_margins: also return, per scale, the smallest |best IoU - 0.5| over the records of the images that have a box on
+    that scale (inf where none has): how far the ignore mask (a threshold, model.py:220-237) is from flipping a record."""
     g = TrainGraph(params, class_num, dtype, masks=masks)
+    if iou_margins:
+        g.iou_margins = []
     fms = g.forward(x)
     loss = g.compute_loss(fms, y_trues, anchors, use_label_smooth, use_focal_loss)
     l2 = g.l2_loss(weight_decay)
@@ -242,7 +251,8 @@ def train_step(params, x, y_trues, anchors, class_num=80, optimizer='sgd', lr=1e
         new_params[mv] = g.p[mv] * bn_decay + var_u * (1 - bn_decay)
     return dict(loss=[float(v) for v in loss], l2=float(l2), grads=out_grads,
                 new_params=OrderedDict((k, v.numpy()) for k, v in new_params.items()),
-                feature_maps=[f.detach().numpy() for f in fms], graph=g, slots=slots)
+                feature_maps=[f.detach().numpy() for f in fms], graph=g, slots=slots,
+                **({'iou_margins': list(g.iou_margins)} if iou_margins else {}))
 
 
 def reapply(params, ref, optimizer, lr, step=1):
@@ -285,17 +295,21 @@ def process_box(boxes, labels, img_size, class_num, anchors):
     return ys[0], ys[1], ys[2]
 
 
-def synthetic_targets(seed, n, img_size, class_num, anchors, max_boxes=10):
+def synthetic_targets(seed, n, img_size, class_num, anchors, max_boxes=10, mix_up=None):
     """SURVEY §8(d) C4 targets: per image K~U{1..10} boxes, class U{0..C-1}, w,h~U(10,300) clipped to the
-    image, centres uniform with the box inside the image, mix weight 1 -> process_box -> stacked y_true."""
+    image, centres uniform with the box inside the image, mix weight 1 -> process_box -> stacked y_true.
+    mix_up=(lo, hi): the boxes' mix-up weights are drawn from U(lo, hi) (the feeder's mix-up path, utils/data_utils.py)
+    by a generator of their own, so the boxes and labels of a seed are the same with and without."""
     rng = np.random.RandomState(seed)
+    rng_mix = None if mix_up is None else np.random.RandomState([seed, 0x6d6978])
     W, H = img_size
     out = [[], [], []]
     for _ in range(n):
         K = rng.randint(1, max_boxes + 1)
         w = np.minimum(rng.uniform(10, 300, K), W - 2.0); h = np.minimum(rng.uniform(10, 300, K), H - 2.0)
         cx = rng.uniform(w / 2, W - w / 2); cy = rng.uniform(h / 2, H - h / 2)
-        boxes = np.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2, np.ones(K)], 1).astype(np.float32)
+        mixw = np.ones(K) if rng_mix is None else rng_mix.uniform(mix_up[0], mix_up[1], K)
+        boxes = np.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2, mixw], 1).astype(np.float32)
         labels = rng.randint(0, class_num, K)
         for o, y in zip(out, process_box(boxes, labels, [W, H], class_num, anchors)):
             o.append(y)

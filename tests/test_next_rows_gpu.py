@@ -43,6 +43,46 @@ def test_process_box_batch_ragged_and_overwrite_semantics():
             np.testing.assert_array_equal(y[i].cpu().numpy(), r)
 
 
+@pytest.mark.parametrize('class_num', [1, 20, 80])
+@pytest.mark.parametrize('img_size', [[224, 160], [64, 32]])
+def test_process_box_batch_on_non_square_images_and_other_class_counts(img_size, class_num):
+    """The case above off the 416 x 416, 80-class point: img_size = [W, H] with W != H (grids 5x7 / 10x14 / 20x28 and
+    1x2 / 2x4 / 4x8: a w/h transposition would index another cell or fall off the grid), 1 / 20 / 80 classes, mix-up weights
+    in (0, 1), an image without boxes, and two boxes on one cell and anchor - bit-exact against train_ref.process_box."""
+    from yolov3_tensorflow_amd.utils import data_utils
+    from oracle import train_ref
+    W, H = img_size
+    rng = np.random.RandomState(W + class_num)
+    n, kmax = 4, 10
+    boxes = np.zeros((n, kmax, 5), np.float32)
+    labels = np.zeros((n, kmax), np.int64)
+    counts = [3, 0, 10, 6]
+    for i, K in enumerate(counts):
+        wh = rng.uniform(6, 300, (K, 2)); c = rng.uniform([1, 1], [W - 1, H - 1], (K, 2))
+        boxes[i, :K] = np.concatenate([c - wh / 2, c + wh / 2, rng.uniform(0.05, 0.95, (K, 1))], 1)
+        labels[i, :K] = rng.randint(0, class_num, K)
+    # the same box twice (same cell, same anchor), the second time as the image's last box under another label and weight: the
+    # later one wins, both class bits stay
+    boxes[2, 9] = boxes[2, 3]; boxes[2, 9, 4] = 0.125; labels[2, 9] = (labels[2, 3] + 1) % class_num
+    ys = data_utils.process_box_batch(boxes, labels, counts, img_size, class_num, COCO_ANCHORS)
+    assert [tuple(y.shape[1:3]) for y in ys] == [(H // s, W // s) for s in (32, 16, 8)]
+    twice = 0
+    for i, K in enumerate(counts):
+        got = [y[i].cpu().numpy() for y in ys]
+        if K == 0:
+            for g in got:
+                assert (g[..., :-1] == 0).all() and (g[..., -1] == 1).all()
+            continue
+        ref = train_ref.process_box(boxes[i, :K], labels[i, :K], img_size, class_num, COCO_ANCHORS)
+        for g, r in zip(got, ref):
+            np.testing.assert_array_equal(g, r)
+        if i == 2:
+            for g in got:
+                both = (g[..., 5 + labels[2, 3]] == 1) & (g[..., 5 + labels[2, 9]] == 1) & (g[..., -1] == 0.125)
+                twice += int(both.sum())
+    assert twice == 1
+
+
 def test_detect_equals_forward_predict_nms(gpu_model):
     import yolov3_tensorflow_amd as y3
     from yolov3_tensorflow_amd.utils import nms_utils

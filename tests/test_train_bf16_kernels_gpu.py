@@ -47,7 +47,9 @@ def conv_ref(x, w_hwio, k, stride):
 
 # the shapes of test_train_gpu.py::test_conv_wgrad_and_dgrad_match_autograd (Cin = 3: the stem keeps its fp32 kernels)
 SHAPES = [(2, 20, 28, 3, 1, 64, 128), (2, 20, 28, 1, 1, 128, 64), (3, 16, 24, 3, 2, 32, 64), (2, 13, 13, 1, 1, 256, 255),
-          (2, 26, 26, 3, 1, 32, 64), (2, 12, 12, 3, 2, 128, 256)]
+          (2, 26, 26, 3, 1, 32, 64), (2, 12, 12, 3, 2, 128, 256),
+          # the detection convs at 20 classes (VOC) and at one class: dz row stride 96 and 32, cout % 4 != 0
+          (2, 13, 13, 1, 1, 256, 75), (2, 13, 13, 1, 1, 512, 18)]
 MEASURED = {}
 
 

@@ -350,7 +350,7 @@ struct LossArgs {
     float* gt_boxes;      // scratch [N][cap][4]  (cx,cy,w,h) of the cells with object_mask == 1
     int* gt_count;        // scratch [N]
     float* partial;       // [blocks_x * N][4]
-    int N, gh, gw, C, cap, vmax;   // cap = row stride of gt_boxes, vmax = boxes staged in LDS
+    int N, gh, gw, C, cap, vmax;   // cap = row stride of gt_boxes, vmax = boxes staged in LDS (the rest are read from gt_boxes)
     float ratio_h, ratio_w, img_h, img_w;
     float anc_w[3], anc_h[3];     // anchors of this scale (pixels)
     float ra_w[3], ra_h[3];       // anchors / ratio
@@ -378,9 +378,19 @@ __device__ __forceinline__ float sigmoid_(float x) { return 1.f / (1.f + expf(-x
 // tf.nn.sigmoid_cross_entropy_with_logits: max(x,0) - x*z + log(1 + exp(-|x|))
 __device__ __forceinline__ float bce_(float z, float x) { return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x))); }
 
+// box_iou (model.py:307-345) of the predicted box (px, py, pw, ph) with the ground-truth box (tx, ty, tw, th)
+__device__ __forceinline__ float iou_(float px, float py, float pw, float ph, float tx, float ty, float tw, float th) {
+    const float iw = fmaxf(fminf(px + pw / 2.f, tx + tw / 2.f) - fmaxf(px - pw / 2.f, tx - tw / 2.f), 0.f);
+    const float ih = fmaxf(fminf(py + ph / 2.f, ty + th / 2.f) - fmaxf(py - ph / 2.f, ty - th / 2.f), 0.f);
+    const float inter = iw * ih;
+    return inter / (pw * ph + tw * th - inter + 1e-10f);
+}
+
 // A wave owns 64 consecutive (cell, anchor) records of one image.
-//   phase 1, one LANE per record: box decode, ignore mask (best IoU over the image's ground-truth boxes of this scale, read
-//            as LDS broadcasts), xy / wh / conf terms and their five gradients, parked in the LDS;
+//   phase 1, one LANE per record: box decode, ignore mask (best IoU over ALL the image's ground-truth boxes of this scale:
+//            the first vmax read as LDS broadcasts, any beyond that as uniform loads from gt_boxes - a maximum over a set,
+//            so the arrival order of loss_collect_gt_kernel's slots does not matter), xy / wh / conf terms and their five
+//            gradients, parked in the LDS;
 //   phase 2, lanes over the 64 x (5+C) contiguous logits of the chunk: the class terms - only where the record holds an
 //            object (object_mask is 0 for all but a few records, whose class logits and targets are then never read) -
 //            and ALL the chunk's gradients written out contiguously.
@@ -394,8 +404,10 @@ __global__ void __launch_bounds__(256) loss_kernel(const LossArgs a) {
     const int n = blockIdx.y;
     const int cells = a.gh * a.gw * 3;
     const int F = 5 + a.C, T = 6 + a.C;
-    const int V = min(a.gt_count[n], a.vmax);
-    for (int i = threadIdx.x; i < V * 4; i += 256) gts[i] = a.gt_boxes[(size_t)n * a.cap * 4 + i];
+    const int G = min(a.gt_count[n], a.cap);               // every box of this image (at most one per record: <= cap)
+    const int V = min(G, a.vmax);                          // ... of which the first V are staged in the LDS
+    const float* gt_n = a.gt_boxes + (size_t)n * a.cap * 4;
+    for (int i = threadIdx.x; i < V * 4; i += 256) gts[i] = gt_n[i];
     __syncthreads();
     const float invN = 1.f / (float)a.N;
     const float invF = 1.f / (float)F;
@@ -423,13 +435,10 @@ __global__ void __launch_bounds__(256) loss_kernel(const LossArgs a) {
             const float pw = (ex * a.ra_w[anc]) * a.ratio_w, ph = (ey * a.ra_h[anc]) * a.ratio_h;
             // ignore mask (model.py:220-237): best IoU with this image's GT boxes of THIS scale < 0.5
             float best = -INFINITY;
-            for (int v = 0; v < V; ++v) {
-                const float tx = gts[4 * v], ty = gts[4 * v + 1], tw = gts[4 * v + 2], th = gts[4 * v + 3];
-                const float iw = fmaxf(fminf(px + pw / 2.f, tx + tw / 2.f) - fmaxf(px - pw / 2.f, tx - tw / 2.f), 0.f);
-                const float ih = fmaxf(fminf(py + ph / 2.f, ty + th / 2.f) - fmaxf(py - ph / 2.f, ty - th / 2.f), 0.f);
-                const float inter = iw * ih;
-                best = fmaxf(best, inter / (pw * ph + tw * th - inter + 1e-10f));
-            }
+            for (int v = 0; v < V; ++v)
+                best = fmaxf(best, iou_(px, py, pw, ph, gts[4 * v], gts[4 * v + 1], gts[4 * v + 2], gts[4 * v + 3]));
+            for (int v = V; v < G; ++v)                  // more boxes than the LDS stages (no real annotation): from memory
+                best = fmaxf(best, iou_(px, py, pw, ph, gt_n[4 * v], gt_n[4 * v + 1], gt_n[4 * v + 2], gt_n[4 * v + 3]));
             const float ignore = best < 0.5f ? 1.f : 0.f;
             const float bls = 2.f - (y2 / a.img_w) * (y3 / a.img_h);
             const float wgt = m * bls * mixw;
@@ -984,8 +993,10 @@ extern "C" int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float*
     Y3_CHECK_HIP(hipMemsetAsync(a.gt_count, 0, (size_t)n * sizeof(int), ctx->stream));
     hipLaunchKernelGGL(loss_collect_gt_kernel, dim3(blocks, n), dim3(256), 0, ctx->stream, a);
     Y3_CHECK_HIP(hipGetLastError());
-    // GT boxes of one image are staged in LDS: up to 2048 per scale per image (32 KB) — far above any real
-    // annotation count (the reference's datasets have tens of boxes per image)
+    // The first 2048 GT boxes of an image and scale are staged in the LDS (32 KB; the reference's datasets have tens of
+    // boxes per image); the loss kernel reads any further ones from gt_boxes itself, which holds all of them (cap = cells).
+    // There is no limit on the number of boxes, and the ignore mask - a maximum over the set - does not depend on the
+    // order in which the collecting kernel's atomic counter handed out the slots.
     a.vmax = cells < 2048 ? cells : 2048;
     const size_t lds = (size_t)a.vmax * 4 * sizeof(float);
     hipLaunchKernelGGL(loss_kernel, dim3(blocks, n), dim3(256), lds, ctx->stream, a);
