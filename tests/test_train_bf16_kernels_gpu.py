@@ -173,7 +173,11 @@ def test_wgrad_at_the_largest_rows_count():
     assert e < 4e-6                        # measured: 1.2e-6 (2.8 M products of unit-variance terms per output)
 
 
-@pytest.mark.parametrize('rows,c,z_f32', [(2 * 13 * 13, 1024, 0), (3 * 20 * 28, 64, 0), (5000, 32, 1), (64, 256, 0)])
+@pytest.mark.parametrize('rows,c,z_f32', [
+    (2 * 13 * 13, 1024, 0), (3 * 20 * 28, 64, 0), (5000, 32, 1), (64, 256, 0),
+    # the column reduction's other paths (tests/test_train_gpu.py::test_bn_train_forward_backward): 85 rows per pass with an
+    # idle lane and a second trip of the row loop; two columns per thread, the second with one live lane
+    (43527, 12, 0), (600, 1028, 0)])
 def test_bn_apply_and_backward(rows, c, z_f32):
     fw, _lib, L, ctx, dev = _env()
     rng = np.random.RandomState(rows + c)
@@ -212,7 +216,11 @@ def test_bn_apply_and_backward(rows, c, z_f32):
     e_g, e_b = rel_err(dgam.cpu(), gamma.grad), rel_err(dbet.cpu(), beta.grad)
     e_z = within_one_rounding(dz.double().cpu(), z.grad)
     print('bn %d x %d: y %.2f roundings; dgamma %.1e dbeta %.1e; dz %.2f roundings' % (rows, c, e_y, e_g, e_b, e_z))
-    assert e_g < 3e-7 and e_b < 3e-7       # measured: <= 1.0e-7
+    # measured: <= 1.0e-7; 43527 x 12: 2.4e-7, 2.0e-7.  There a partial is a chain of up to 86 fp32 additions (two rows per
+    # lane, then the 85 row lanes in order), and 512 such partials with independent roundings give an error of the order of
+    # sqrt(512 * 86) * 2^-25 * |partial| / max|sum|, with |partial| ~ 11 and max|sum| ~ 3e2: 2e-7.  The inputs are seeded and the reduction has a fixed order (no
+    # atomics), so the figure is the same bits on every run, not a sample.
+    assert e_g < 3e-7 and e_b < 3e-7
     assert e_z <= 2.05                     # one rounding (measured 1.97-1.99)
 
 

@@ -261,7 +261,13 @@ def test_conv_epilogue_statistics_equal_the_separate_pass(n, h, w, k, stride, ci
         np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), rtol=2e-5, atol=2e-6)
 
 
-@pytest.mark.parametrize('rows,c', [(2 * 13 * 13, 1024), (3 * 20 * 28, 64), (5000, 32), (64, 256)])
+@pytest.mark.parametrize('rows,c', [
+    (2 * 13 * 13, 1024), (3 * 20 * 28, 64), (5000, 32), (64, 256),
+    # the shapes the column reduction (col_reduce_kernel) can get wrong:
+    (43527, 12),     # C/4 = 3: 85 rows per pass, lane 255 idle; 43527 > 512 * 85: a second trip of the row loop, ragged end
+    (600, 1028),     # C/4 = 257: two columns per thread, the second with one live lane; rows > 512 at one row per pass
+    (3, 256),        # fewer rows than rows per pass (4)
+])
 def test_bn_train_forward_backward(rows, c):
     fw, _lib, L, ctx = _ctx()
     dev = fw.default_device()
@@ -299,6 +305,50 @@ def test_bn_train_forward_backward(rows, c):
     assert rel_err(dgam.cpu().numpy(), gamma.grad.numpy()) < 2e-4
     assert rel_err(dbet.cpu().numpy(), beta.grad.numpy()) < 2e-4
     assert rel_err(dyg.cpu().numpy(), z.grad.numpy()) < 2e-4
+
+
+def test_bn_train_stats_and_apply_without_moving_statistics_or_residual():
+    """y3_bn_train_stats with moving_mean = moving_var = NULL, its inv_std / scale / shift looked at directly (rtol 2e-5, as
+    test_conv_epilogue_statistics_equal_the_separate_pass holds the same quantities), and y3_bn_apply_fwd with no residual,
+    linear (act=0) and with the LeakyReLU (act=1), against fp64.  One of the moving pair alone is refused.
+    Would catch: act ignored, a residual read through a null pointer, scale / shift folded with the wrong sign or the
+    wrong statistic, the moving update dereferencing NULL."""
+    fw, _lib, L, ctx = _ctx()
+    dev = fw.default_device()
+    rows, c = 338, 64
+    rng = np.random.RandomState(rows + c)
+    z = rng.standard_normal((rows, c)) * 2 + rng.standard_normal(c)
+    z = z.astype(np.float32).astype(np.float64)
+    gamma, beta = rng.uniform(0.5, 1.5, c).astype(np.float32), rng.normal(0, 0.3, c).astype(np.float32)
+    mean, var = z.mean(0), z.var(0)
+    inv_std = 1.0 / np.sqrt(var + 1e-5)
+    scale = gamma.astype(np.float64) * inv_std
+    shift = beta.astype(np.float64) - mean * scale
+    f32 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float32, device=dev)
+    zg, gg, bg = f32(z), f32(gamma), f32(beta)
+    stats = torch.full((4, c), float('nan'), device=dev)
+    sc = torch.empty(L.y3_reduce_scratch_bytes(c), dtype=torch.uint8, device=dev)
+    args = lambda mm, mv: (ctx, fw.ptr(zg), rows, c, fw.ptr(gg), fw.ptr(bg), ctypes.c_float(1e-5), ctypes.c_float(0.9),
+                           fw.ptr(stats[0]), fw.ptr(stats[1]), fw.ptr(stats[2]), fw.ptr(stats[3]), fw.ptr(mm), fw.ptr(mv),
+                           fw.ptr(sc))
+    one = torch.full((c,), 0.25, device=dev)
+    for pair in ((one, None), (None, one)):
+        with pytest.raises(ValueError):
+            _lib.check(L.y3_bn_train_stats(*args(*pair)))
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(stats).all()) and bool((one == 0.25).all())          # a refused call writes nothing
+    _lib.check(L.y3_bn_train_stats(*args(None, None)))
+    got = stats.cpu().numpy()
+    assert rel_err(got[0], mean) < 1e-5
+    np.testing.assert_allclose(got[1], inv_std, rtol=2e-5)
+    np.testing.assert_allclose(got[2], scale, rtol=2e-5)
+    np.testing.assert_allclose(got[3], shift, rtol=2e-5, atol=2e-5 * float(np.abs(mean * scale).max()))
+    u = z * scale + shift
+    assert (u < 0).mean() > 0.2                                                    # the two activations differ
+    for act, want in ((0, u), (1, np.where(u > 0, u, 0.1 * u))):
+        yg = torch.full((rows, c), float('nan'), device=dev)
+        _lib.check(L.y3_bn_apply_fwd(ctx, fw.ptr(zg), fw.ptr(stats[2]), fw.ptr(stats[3]), None, rows, c, act, fw.ptr(yg)))
+        assert rel_err(yg.cpu().numpy(), want) < 2e-5, 'act=%d' % act
 
 
 @pytest.mark.parametrize('smooth,focal', [(False, False), (True, True)])
