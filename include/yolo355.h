@@ -370,6 +370,27 @@ int y3_bias_grad(y3_ctx* ctx, const float* dy, long long rows, int c, float* dbi
 int y3_conv2d_dgrad(y3_ctx* ctx, const y3_conv_desc* fwd, const float* dz, int dz_stride, const float* w_d,
                     const float* ones, const float* zeros, int accumulate, float* dx, void* workspace,
                     size_t workspace_bytes);
+/* The data gradient of a stride-1 1x1 conv whose dx IS the dy of the batch-norm layer below it, with that layer's backward
+ * reduction taken in the epilogue where the tile is in registers (the backward twin of y3_conv2d_fwd_stats): dx as
+ * y3_conv2d_dgrad writes it, and partial [y3_conv_dgrad_bn_blocks(fwd)][2][cin] = per row block of dx, the column sums of
+ * g' = dx * leaky'(z*scale + shift) and of g' * (z - mean) * inv_std (dx = the stored sum when accumulate != 0).  bn_z
+ * [n*h*w][cin] is that layer's raw conv output, bn_vec [4][cin] its mean / inv_std / folded scale / folded shift as
+ * y3_bn_train_stats wrote them.  y3_conv_dgrad_bn_blocks returns 0 where there is no such kernel (3x3 or stride-2 convs,
+ * fused upsample inputs, cin %% 4 != 0); y3_conv2d_dgrad_bn then returns Y3_EINVAL and writes nothing.
+ * y3_bn_train_bwd_partials is y3_bn_train_bwd with the reduction already done (partial: [nblocks][2][c], combined in a fixed
+ * order in fp64): dgamma, dbeta and dz; same scratch. */
+int y3_conv_dgrad_bn_blocks(const y3_conv_desc* fwd);
+int y3_conv2d_dgrad_bn(y3_ctx* ctx, const y3_conv_desc* fwd, const float* dz, int dz_stride, const float* w_d,
+                       const float* ones, const float* zeros, int accumulate, float* dx, const float* bn_z,
+                       const float* bn_vec, float* partial);
+int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float* dy, const float* gamma, const float* scale,
+                             const float* shift, const float* mean, const float* inv_std, long long rows, int c,
+                             const float* partial, int nblocks, float* dgamma, float* dbeta, float* dz, float* scratch);
+/* Which schedule a launch of the exact-fp32 conv family takes (host arithmetic, no device): 0 = one workgroup per tile,
+ * 1 = stream-K (3x3 convs on 128x128 tiles, needs the workspace), 2 = the resident walk of the 64x64 tiles (1,024 workgroups
+ * walking runs of whole tiles).  `conv` is the conv as launched: for a data gradient [n,h,w,dz_stride] -> fwd cin at stride
+ * 1; tmode_taps = 1, 2 or 4 asks for one parity class of a stride-2 3x3 data gradient (h, w = the coarse map), else 0. */
+int y3_conv_schedule(const y3_conv_desc* conv, int tmode_taps, int with_workspace);
 /* The same data gradient on the bf16 matrix pipe (stride-1 convs; see y3_conv2d_fwd_split): w_split_d comes from
  * y3_pack_conv_weights_split_dgrad(w_d = the [k*k][cin][dz_stride] kernel above). */
 int y3_pack_conv_weights_split_dgrad(y3_ctx* ctx, const float* w_d, int k, int cin, int dz_stride, int planes,

@@ -1,0 +1,78 @@
+"""Host-only: the schedule the fp32 conv launchers pick (y3_conv_schedule: use_streamk and the data-parallel launcher's own
+grid choice, asked without launching) and the weight gradient's split count, pinned for the shapes of
+tests/test_conv_schedules_gpu.py (tests/conv_schedule_cases.py).  A change to a schedule rule shows up here as a diff; the
+GPU cases then have to move so that they still reach the path they are named for."""
+import ctypes
+
+import pytest
+
+import conv_schedule_cases as C
+
+
+@pytest.fixture(scope='module')
+def L():
+    from yolov3_tensorflow_amd import build, _lib
+    build.build(verbose=False)
+    return _lib.lib()
+
+
+def test_weight_gradient_splits_have_several_k_steps(L):
+    got = []
+    for (n, h, w, k, s, cin, cout, _, ragged), (ns_want, chunk_want) in zip(C.WGRAD, C.WGRAD_SPLITS):
+        ns, chunk, last, _ = C.wgrad_split(L, n, h, w, k, s, cin, cout)
+        got.append((ns, chunk))
+        assert chunk > 1 and ns > 1
+        if ragged is not None:
+            assert last == ragged < chunk
+    assert got == C.WGRAD_SPLITS
+    # every case of test_train_gpu.test_conv_wgrad_and_dgrad_match_autograd gets ONE K-step per split (why these cases exist)
+    for n, h, w, k, s, cin, cout in ((2, 20, 28, 3, 1, 64, 128), (2, 13, 13, 1, 1, 256, 255), (3, 16, 24, 3, 2, 32, 64)):
+        assert C.wgrad_split(L, n, h, w, k, s, cin, cout)[1] == 1
+    assert C.wgrad_split(L, 3, 150, 146, 1, 1, 64, 32)[3] == 4      # the ragged K-step: 4 of 32 pixels
+
+
+def test_data_gradient_schedules(L):
+    for n, h, w, cin, cout in C.DGRAD_S1:
+        assert C.schedule(L, n, h, w, cout, 0, cin, 3, 1, 0, 1) == C.STREAMK
+        assert C.schedule(L, n, h, w, cout, 0, cin, 3, 1, 0, 0) == C.ONE_PER_TILE
+    for n, h, w, cin, cout, want in C.DGRAD_S2:
+        got = tuple(C.schedule(L, n, h // 2, w // 2, cout, 0, cin, 3, 1, t, 1) for t in C.PARITY_TAPS)
+        assert got == want
+        assert all(C.schedule(L, n, h // 2, w // 2, cout, 0, cin, 3, 1, t, 0) == C.ONE_PER_TILE for t in C.PARITY_TAPS)
+    # fwd Cin = 64 (Cout' < 128): no stream-K however many tiles; the shapes of the per-kernel test in test_train_gpu.py neither
+    assert C.schedule(L, 3, 37, 37, 128, 0, 64, 3, 1, 0, 1) == C.ONE_PER_TILE
+    assert C.schedule(L, 2, 20, 28, 128, 0, 64, 3, 1, 0, 1) == C.ONE_PER_TILE
+    assert C.schedule(L, 2, 6, 6, 256, 0, 128, 3, 1, 4, 1) == C.ONE_PER_TILE
+
+
+def test_resident_walk_thresholds(L):
+    for name, n, h, w, cin, c_up, cout, _, want in C.FWD:
+        assert C.schedule(L, n, h, w, cin, c_up, cout, 1, 1) == want, name
+    n, h, w, cin, cout = C.FWD_STATS
+    assert C.schedule(L, n, h, w, cin, 0, cout, 1, 1) == C.RESIDENT
+    # the walk belongs to the 64x64 tiles: Cout <= 64 takes the 128-row tiles, a 3x3 conv the 128x128 tile
+    assert C.schedule(L, 3, 150, 146, 32, 0, 64, 1, 1) == C.ONE_PER_TILE
+    assert C.schedule(L, 8, 52, 52, 32, 0, 64, 3, 1, 0, 0) == C.ONE_PER_TILE
+    # the largest 1x1 grid of test_conv_gpu.py (216 tiles) is far below it
+    assert C.schedule(L, 3, 20, 28, 1024, 0, 512, 1, 1) == C.ONE_PER_TILE
+
+
+def test_fused_bn_backward_cases(L):
+    for n, h, w, cin, cout, dzs, bm, want in C.DGRAD_BN:
+        assert C.schedule(L, n, h, w, dzs, 0, cin, 1, 1) == want
+        blocks = L.y3_conv_dgrad_bn_blocks(ctypes.byref(C.desc(n, h, w, cin, 0, cout, 1, 1)))
+        assert blocks == -(-(n * h * w) // bm)
+    for bad in (C.desc(3, 20, 28, 64, 0, 128, 3, 1), C.desc(3, 20, 28, 64, 0, 128, 3, 2), C.desc(3, 20, 28, 64, 32, 128, 1, 1),
+                C.desc(3, 20, 28, 66, 0, 128, 1, 1)):
+        assert L.y3_conv_dgrad_bn_blocks(ctypes.byref(bad)) == 0
+    assert L.y3_conv_dgrad_bn_blocks(None) == 0
+
+
+def test_schedule_query_rejects_what_no_launcher_takes(L):
+    assert L.y3_conv_schedule(None, 0, 1) == 0
+    assert C.schedule(L, 2, 26, 26, 128, 0, 256, 5, 1) == 0           # kernel size
+    assert C.schedule(L, 2, 26, 26, 128, 0, 256, 3, 1, 3, 1) == 0     # no parity class has three taps
+    assert C.schedule(L, 32, 52, 52, 3, 0, 32, 3, 1) == 0             # the stem: one thread per pixel
+    # the forward 3x3 convs of the 52 grid at batch 8 and 32 (what y3_net_layer_is_streamk reports per layer)
+    assert C.schedule(L, 8, 52, 52, 128, 0, 256, 3, 1, 0, 1) == C.STREAMK
+    assert C.schedule(L, 8, 52, 52, 128, 0, 256, 3, 1, 0, 0) == C.ONE_PER_TILE

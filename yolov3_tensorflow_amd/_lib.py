@@ -146,6 +146,12 @@ PROTOTYPES = {
     "y3_bias_grad": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p]),
     "y3_conv2d_dgrad": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p, c_void_p, c_size_t]),
+    "y3_conv_dgrad_bn_blocks": (c_int, [POINTER(ConvDesc)]),
+    "y3_conv2d_dgrad_bn": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y3_bn_train_bwd_partials": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_longlong, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y3_conv_schedule": (c_int, [POINTER(ConvDesc), c_int, c_int]),
     "y3_pack_conv_weights_wino_dgrad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "y3_conv2d_dgrad_wino": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p, c_size_t]),

@@ -335,6 +335,27 @@ extern "C" int y3_conv2d_dgrad(y3_ctx* ctx, const y3_conv_desc* fwd, const float
                                 workspace_bytes, &o);
 }
 
+// ---- the 1x1 data gradient with the BN backward reduction of the layer below in its epilogue ----------------------------
+extern "C" int y3_conv_dgrad_bn_blocks(const y3_conv_desc* fwd) { return y3_conv_dgrad_stats_blocks_impl(fwd); }
+
+extern "C" int y3_conv2d_dgrad_bn(y3_ctx* ctx, const y3_conv_desc* fwd, const float* dz, int dz_stride, const float* w_d,
+                                  const float* ones, const float* zeros, int accumulate, float* dx, const float* bn_z,
+                                  const float* bn_vec, float* partial) {
+    Y3_CHECK_CTX(ctx, "y3_conv2d_dgrad_bn");
+    Y3_CHECK_ARG(fwd && bn_z && bn_vec && partial && y3_conv_dgrad_stats_blocks_impl(fwd) > 0,
+                 "y3_conv2d_dgrad_bn: null argument, or a conv without the fused reduction (y3_conv_dgrad_bn_blocks == 0)");
+    y3_sk_opts o;
+    o.err = ctx->err_host;
+    o.stats = partial;
+    o.bwd_z = bn_z;
+    o.bwd_vec = bn_vec;
+    return y3_launch_conv_dgrad(ctx->stream, fwd, dz, dz_stride, w_d, ones, zeros, accumulate, dx, nullptr, 0, &o);
+}
+
+extern "C" int y3_conv_schedule(const y3_conv_desc* conv, int tmode_taps, int with_workspace) {
+    return y3_conv_schedule_query(conv, tmode_taps, with_workspace);
+}
+
 // ------------------------------------------------------------------------------------------------
 // y3_net: the 75-conv graph.  Tensor ids: 0 = network input; 1.. = conv outputs in creation order.
 // ------------------------------------------------------------------------------------------------

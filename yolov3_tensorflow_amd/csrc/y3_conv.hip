@@ -339,9 +339,29 @@ __global__ void __launch_bounds__(256, 2) conv_mfma_f32_kernel(const ConvArgs p)
 
 constexpr int RESIDENT_64 = 1024;      // 64x64-tile workgroups resident at once: four per CU (37 KB of LDS, 72 VGPRs)
 
+// Grid of a data-parallel launch over `tiles` BM x BN tiles: one workgroup per tile, or the resident walk below.
+inline int data_parallel_grid(int bm, int bn, int tiles) {
+    // 64x64 tiles (the 1x1 convs), more tiles than the 1,024 resident workgroups but only a few rounds of them: a RESIDENT
+    // grid whose workgroups walk balanced runs of whole tiles.  The hardware dispatcher hands the tiles of a partly filled
+    // last round to the first slots that come free - four per CU on a quarter of the CUs while the rest idle (measured on
+    // the F(4x4) kernel: 1.5 rounds cost 2, tools/wino44_quant.py); a resident grid spreads them one or two per CU, and
+    // a workgroup fetches its next tile under the current one's store tail.
+    if (bm == 64 && bn == 64 && tiles > RESIDENT_64 && tiles < 8 * RESIDENT_64 && y3_exp_env("Y3_CONV_RESIDENT_OFF") == nullptr)
+        return RESIDENT_64;
+    return tiles;
+}
+
+// query != nullptr: nothing is launched; *query = the schedule this launch would take (y3_conv_schedule: 0 or 2)
 template <int BM, int BN, int WGM, int WGN, int KS, bool UPCAT, bool TMODE = false, bool STATS = false, bool BSTATS = false>
-int launch_data_parallel(hipStream_t stream, const ConvArgs& a) {
+int launch_data_parallel(hipStream_t stream, const ConvArgs& a, int* query = nullptr) {
     using G = Geo<BM, BN, WGM, WGN>;
+    const int nbm = (a.M + BM - 1) / BM;
+    const int nbn = (a.Cout + BN - 1) / BN;
+    const int grid = data_parallel_grid(BM, BN, nbm * nbn);
+    if (query) {
+        *query = grid != nbm * nbn ? 2 : 0;
+        return Y3_OK;
+    }
     auto kern = conv_mfma_f32_kernel<BM, BN, WGM, WGN, KS, UPCAT, false, TMODE, STATS, BSTATS>;
     static bool attr_set[Y3_MAX_DEVICES] = {};  // per instantiation; benign race (idempotent)
     const int dev_ = y3_current_device();
@@ -349,16 +369,6 @@ int launch_data_parallel(hipStream_t stream, const ConvArgs& a) {
         if (int rc = set_lds_attr(kern, G::LDS_BYTES)) return rc;
         if (dev_ >= 0) attr_set[dev_] = true;
     }
-    const int nbm = (a.M + BM - 1) / BM;
-    const int nbn = (a.Cout + BN - 1) / BN;
-    int grid = nbm * nbn;
-    // 64x64 tiles (the 1x1 convs), more tiles than the 1,024 resident workgroups but only a few rounds of them: a RESIDENT
-    // grid whose workgroups walk balanced runs of whole tiles.  The hardware dispatcher hands the tiles of a partly filled
-    // last round to the first slots that come free - four per CU on a quarter of the CUs while the rest idle (measured on
-    // the F(4x4) kernel: 1.5 rounds cost 2, tools/wino44_quant.py); a resident grid spreads them one or two per CU, and
-    // a workgroup fetches its next tile under the current one's store tail.
-    if (BM == 64 && BN == 64 && grid > RESIDENT_64 && grid < 8 * RESIDENT_64 && y3_exp_env("Y3_CONV_RESIDENT_OFF") == nullptr)
-        grid = RESIDENT_64;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), G::LDS_BYTES, stream, a);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
@@ -381,28 +391,44 @@ int launch_streamk(hipStream_t stream, const ConvArgs& a) {
 }
 
 template <int KS, bool UPCAT, bool TMODE = false, bool STATS = false, bool BSTATS = false>
-int dispatch_bn(hipStream_t stream, const ConvArgs& a) {
-    if (a.Cout <= 32) return launch_data_parallel<128, 32, 4, 1, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a);
-    if (a.Cout <= 64) return launch_data_parallel<128, 64, 4, 1, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a);
+int dispatch_bn(hipStream_t stream, const ConvArgs& a, int* query = nullptr) {
+    if (a.Cout <= 32) return launch_data_parallel<128, 32, 4, 1, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
+    if (a.Cout <= 64) return launch_data_parallel<128, 64, 4, 1, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
     // 1x1 layers have 8-32 K-steps per tile: 64x64 tiles (37 KB of LDS, 72 VGPRs -> 4 workgroups per CU) hide one
     // tile's prologue/epilogue under its neighbours' MFMAs and quantise the 172-1352-tile grids of the network 4x
     // finer (measured, batch 32: 52x52 -10 %, 26x26 -19 %, 13x13 -21 % against the 128x128 tile)
-    if (KS == 1 && !TMODE) return launch_data_parallel<64, 64, 2, 2, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a);
+    if (KS == 1 && !TMODE) return launch_data_parallel<64, 64, 2, 2, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
     static_assert(!BSTATS || KS == 1, "the fused BN backward reduction exists on the small tiles of the 1x1 data gradient only");
-    return launch_data_parallel<128, 128, 2, 2, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a);
+    return launch_data_parallel<128, 128, 2, 2, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
 }
 
 }  // namespace
 
-// 1 if y3_launch_conv would pick the stream-K schedule for this conv when given a workspace.
-int y3_conv_schedule_impl(const y3_conv_desc* d) {
-    if (!d || d->k != 3 || d->cin == 3 || d->c_up > 0) return 0;
-    ConvArgs a{};        // (value-initialised: use_streamk reads Cin, tmode and ntaps too)
+// The schedule a launch of `conv` takes: 0 = one workgroup per tile, 1 = stream-K, 2 = the resident walk.  `conv` is the conv
+// as launched (a data gradient: [n,h,w,dz_stride] -> fwd cin at stride 1); tmode_taps = 1/2/4: one parity class of a stride-2
+// data gradient.  Host arithmetic only: use_streamk and the launchers' own grid choice, asked without launching.
+int y3_conv_schedule_query(const y3_conv_desc* d, int tmode_taps, int with_workspace) {
+    if (!d || (d->k != 1 && d->k != 3) || (d->stride != 1 && d->stride != 2) || d->n <= 0 || d->h <= 0 || d->w <= 0 ||
+        d->cin <= 0 || d->cout <= 0 || d->cin == 3)
+        return 0;                                   // (the stem: one thread per pixel)
+    if (tmode_taps != 0 && (d->k != 3 || d->stride != 1 || d->c_up > 0 || (tmode_taps != 1 && tmode_taps != 2 && tmode_taps != 4)))
+        return 0;
+    ConvArgs a{};        // (value-initialised: use_streamk reads Cin, xu, tmode and ntaps too)
     a.Cin = d->cin;
     a.Cout = d->cout;
     a.M = d->n * (d->h / d->stride) * (d->w / d->stride);
-    return use_streamk(a, d->k, true) ? 1 : 0;
+    a.tmode = tmode_taps ? 1 : 0;
+    a.ntaps = tmode_taps;
+    int s = 0;
+    if (d->c_up > 0) return d->k == 1 && dispatch_bn<1, true>(nullptr, a, &s) == Y3_OK ? s : 0;
+    if (d->k == 1) return dispatch_bn<1, false>(nullptr, a, &s) == Y3_OK ? s : 0;
+    if (use_streamk(a, 3, with_workspace != 0)) return 1;
+    const int rc = tmode_taps ? dispatch_bn<3, false, true>(nullptr, a, &s) : dispatch_bn<3, false>(nullptr, a, &s);
+    return rc == Y3_OK ? s : 0;
 }
+
+// 1 if y3_launch_conv would pick the stream-K schedule for this conv when given a workspace.
+int y3_conv_schedule_impl(const y3_conv_desc* d) { return y3_conv_schedule_query(d, 0, 1) == 1; }
 
 int y3_streamk_range_impl(int kind, int units, int ksteps, int workers, int group, int local_worker, long long* begin,
                           long long* end) {

@@ -43,10 +43,7 @@ struct y3_sk_opts {
 int y3_conv_stats_blocks_impl(const y3_conv_desc* d, int wino);
 // rows of the fused BN-backward partial sums of the 1x1 data gradient of forward layer `fwd` (0: not available)
 int y3_conv_dgrad_stats_blocks_impl(const y3_conv_desc* fwd);
-// BN backward with the reduction already done: partial = [nblocks][2][c] sums of g' and g' * zhat (scratch: y3_bn_bwd_scratch_bytes)
-int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float* dy, const float* gamma, const float* scale, const float* shift,
-                             const float* mean, const float* inv_std, long long rows, int c, const float* partial, int nblocks,
-                             float* dgamma, float* dbeta, float* dz, float* scratch);
+// (y3_bn_train_bwd_partials, the BN backward with that reduction already done: include/yolo355.h)
 #define Y3_ERR_STREAMK_TIMEOUT 1u
 // Test hook: with Y3_STREAMK_FAULT=1 in the environment the producers of a stream-K launch never raise their flag and
 // the consumers give up after 2^10 polls, so the time-out path (error word -> Y3_EHIP) can be exercised.
@@ -97,6 +94,8 @@ int y3_launch_conv(hipStream_t stream, const y3_conv_desc* d, const float* x, co
                    float* y, void* workspace, size_t workspace_bytes, const y3_sk_opts* sk = nullptr);
 size_t y3_conv_workspace_bytes_impl(const y3_conv_desc* d);
 int y3_conv_schedule_impl(const y3_conv_desc* d);
+// 0 = one workgroup per tile, 1 = stream-K, 2 = the resident walk: asked of the launchers' own rules (y3_conv_schedule)
+int y3_conv_schedule_query(const y3_conv_desc* conv, int tmode_taps, int with_workspace);
 // host evaluation of the device-side stream-K work split (test hook): kind 0 = sk_range (direct / split kernels,
 // y3_conv_common.h), 1 = wk_range (Winograd kernel, every block may be cut), 2 = wk_range hybrid (whole rounds first)
 int y3_streamk_range_impl(int kind, int units, int ksteps, int workers, int group, int local_worker, long long* begin,

@@ -911,9 +911,10 @@ extern "C" int y3_bn_train_bwd(y3_ctx* ctx, const float* z, const float* dy, con
     return bn_bwd<float>(ctx, z, dy, gamma, scale, shift, mean, inv_std, rows, c, nullptr, 0, dgamma, dbeta, dz, scratch);
 }
 
-int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float* dy, const float* gamma, const float* scale, const float* shift,
-                             const float* mean, const float* inv_std, long long rows, int c, const float* partial, int nblocks,
-                             float* dgamma, float* dbeta, float* dz, float* scratch) {
+extern "C" int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float* dy, const float* gamma, const float* scale,
+                                        const float* shift, const float* mean, const float* inv_std, long long rows, int c,
+                                        const float* partial, int nblocks, float* dgamma, float* dbeta, float* dz,
+                                        float* scratch) {
     Y3_CHECK_ARG(ctx && z && dy && gamma && scale && shift && mean && inv_std && dz && scratch && partial && nblocks > 0,
                  "y3_bn_train_bwd_partials: null argument");
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_train_bwd_partials: bad shape");
