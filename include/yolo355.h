@@ -35,7 +35,9 @@ extern "C" {
 #define Y3_EHIP (-2)     /* a HIP runtime call failed */
 #define Y3_ESTATE (-3)   /* object used before it was fully configured */
 
-#define Y3_ABI_VERSION 4
+/* 5: y3_feed_run takes the blob's size and an arena (the arguments of version 4's second, checked feed entry, which is gone).
+ * A caller built against version 4 must not call a version 5 library: the name is the same, the arguments are not. */
+#define Y3_ABI_VERSION 5
 
 typedef struct y3_ctx y3_ctx; /* one per (device, stream) */
 typedef struct y3_net y3_net; /* the 75-conv YOLOv3 graph bound to caller-owned parameters */
@@ -555,26 +557,23 @@ int y3_process_box(y3_ctx* ctx, const float* boxes, const int32_t* labels, const
 /* ---- row 8(f)#1, the feeder's pixel work on the device (utils/data_utils.py:118-172 parse_data after its draws:
  * mix_up blend, random_color_distort, the crop window of the expanded canvas, cv2.resize with the drawn interpolation,
  * letterbox padding, random_flip, / 255) for a BATCH of samples.  The host half - the draws, the box arithmetic, Pillow's
- * double-precision filter windows and weights - is liby3feed.so's y3f_plan_batch (include/yolo355_feed.h), which writes one
- * relocatable blob per batch; the caller uploads it and passes its device address here, together with the host copy of
- * the n y3f_djob records at its start (launch geometry), the y3f_dtables uploaded once per device, and `scratch_bytes` >=
- * the plan's scratch.  out: [n][out_h][out_w][3] float32, the bytes y3f_sample writes (tests/test_feed_gpu.py).
- * Asynchronous on the context's stream; blob, tables and scratch must stay untouched until it has run. */
+ * double-precision filter windows and weights - is liby3feed.so's y3f_plan_batch or y3f_plan_batch_src
+ * (include/yolo355_feed.h), which writes one relocatable blob per batch; the caller uploads it and passes its device address
+ * and size here, together with the host copy of the n y3f_djob records at its start and the y3f_dtables uploaded once per
+ * device.  A source whose record says so (y3f_plan_batch_src) is not in the blob but in the caller's device arena src_dev of
+ * src_bytes (whole 8-bit RGB images), and is read where it lies; a packed plan passes NULL, 0.
+ * Every record is checked before anything is launched: each blob offset plus extent (records, packed sources, jitter maps,
+ * tables by their ksize and counts) against blob_bytes, each arena rectangle (img_off + ((r_y0 + r_h - 1) * stride + r_x0 +
+ * r_w) * 3, stride >= r_x0 + r_w) against src_bytes, live inside win, the scratch extents; anything out of range is
+ * Y3_EINVAL naming the job.  The kernels read the records from the copy that was checked, uploaded behind the jobs' scratch:
+ * scratch_bytes >= the plan's scratch + 16 + n * sizeof(y3f_djob).
+ * out: [n][out_h][out_w][3] float32, the bytes y3f_sample writes (tests/test_feed_gpu.py, tests/test_feed_src_gpu.py).
+ * Asynchronous on the context's stream; blob, tables, arena and scratch must stay untouched until it has run.
+ * (ABI version 5: up to version 4 this name took no blob size and no arena, and checked no record.) */
 struct y3f_djob;
-int y3_feed_run(y3_ctx* ctx, const void* blob_dev, const struct y3f_djob* jobs_host, int n, const void* tables_dev,
-                void* scratch_dev, size_t scratch_bytes, float* out, int out_h, int out_w);
-
-/* y3_feed_run over a y3f_plan_batch_src plan (include/yolo355_feed.h): a source whose record says so is not in the blob but in
- * the caller's device arena src_dev of src_bytes (whole 8-bit RGB images; NULL when no record refers to it), and is read where
- * it lies.  This entry is given every size and checks every record before it launches anything: each blob offset plus extent
- * (records, packed sources, jitter maps, tables by their ksize and counts) against blob_bytes, each arena rectangle
- * (img_off + ((r_y0 + r_h - 1) * stride + r_x0 + r_w) * 3, stride >= r_x0 + r_w) against src_bytes, live inside win, the
- * scratch extents; anything out of range is Y3_EINVAL naming the job.  The kernels read the records from the copy that was
- * checked, uploaded behind the jobs' scratch: scratch_bytes >= the plan's scratch + 16 + n * sizeof(y3f_djob).  Same bytes
- * as y3_feed_run gives for the packed plan of the same jobs (tests/test_feed_src_gpu.py). */
-int y3_feed_run_src(y3_ctx* ctx, const void* blob_dev, size_t blob_bytes, const struct y3f_djob* jobs_host, int n,
-                    const void* tables_dev, void* scratch_dev, size_t scratch_bytes, const void* src_dev, size_t src_bytes,
-                    float* out, int out_h, int out_w);
+int y3_feed_run(y3_ctx* ctx, const void* blob_dev, size_t blob_bytes, const struct y3f_djob* jobs_host, int n,
+                const void* tables_dev, void* scratch_dev, size_t scratch_bytes, const void* src_dev, size_t src_bytes,
+                float* out, int out_h, int out_w);
 
 /* The device half of the feeder's JPEG decoder (include/yolo355_jpeg.h).  liby3feed.so's y3f_jpeg_plan wrote n files into
  * one blob; the caller uploads it and passes its device address and size, the host copy of the n y3j_rec records at its

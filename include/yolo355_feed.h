@@ -107,8 +107,9 @@ int y3f_crop_candidates(uint32_t* mt_state, const double* boxes, int n_boxes, in
  * look-ups, a few hundred microseconds per batch - once the host has done what must be done in double precision exactly as
  * Pillow / OpenCV do it: y3f_plan_batch turns n jobs into ONE relocatable blob (the job records, the source pixels the
  * windows need, the jitter maps, the resampling coefficient tables), the caller uploads the blob, and y3_feed_run
- * (include/yolo355.h, libyolo355.so) produces the float32 batch on the device.  Same bytes as y3f_sample
- * (tests/test_feed_gpu.py; tests/test_feed_plan.py runs the device functions on the host against y3f_sample).
+ * (include/yolo355.h, libyolo355.so) checks every record against the blob's size and produces the float32 batch on the
+ * device.  Same bytes as y3f_sample (tests/test_feed_gpu.py; tests/test_feed_plan.py runs the device functions on the host
+ * against y3f_sample).
  *
  * All offsets are bytes from the start of the blob (sources, maps, tables) or of the device scratch (win, tmp). */
 #define Y3F_MODE_NEAREST 0
@@ -155,8 +156,8 @@ int y3f_plan_batch(const y3f_job* jobs, int n, uint8_t* blob, size_t capacity, s
  *     arena + img_off + (y * stride + x) * 3,
  * and the blob holds no bytes for it.  Every other source is packed as y3f_plan_batch packs it; a batch may mix both kinds job
  * by job and source by source.  src1_off / src2_off may be NULL (= nothing in the arena); with nothing in the arena the blob
- * is byte-identical to y3f_plan_batch's.  Sizing and a too small capacity behave as there.  y3_feed_run_src (include/yolo355.h)
- * runs such a plan. */
+ * is byte-identical to y3f_plan_batch's.  Sizing and a too small capacity behave as there.  y3_feed_run (include/yolo355.h)
+ * runs either plan, given the arena's device address and size. */
 #define Y3F_NOT_IN_ARENA UINT64_MAX
 #define Y3F_SRC1_ARENA 1
 #define Y3F_SRC2_ARENA 2

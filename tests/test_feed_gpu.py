@@ -2,8 +2,6 @@
 utils/data_utils.py:118-172 after its draws): the three kernels against liby3feed.so's y3f_sample - which is itself
 held bit for bit to the numpy / Pillow definition (tests/test_feed_native.py) - on the random jobs of feed_cases.py, on
 full-size jobs, and through the Feeder."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -83,25 +81,73 @@ def test_every_colour_goes_through_the_device_jitter_like_the_host():
         assert np.array_equal(got, want), 'jitter %r: %d colours differ' % (colour, int((got != want).any(-1).sum()))
 
 
+def _packed_plan(runner, rng, accept):
+    """Three random 32x32 jobs, all sources packed (no arena), drawn until accept(records, blob) holds."""
+    while True:
+        cases = [random_case(rng, out_size=(32, 32)) for _ in range(3)]
+        p = runner.plan(cases, np.zeros(16, np.uint8), [None] * 3, [None] * 3)
+        if accept(p['recs'], p['blob']):
+            return cases, p
+
+
 def test_run_reports_bad_arguments():
-    from yolov3_tensorflow_amd import _lib, feed_native as fn
-    from yolov3_tensorflow_amd import framework as fw
+    """The one entry on a PACKED plan: what it must refuse before launching anything, each followed by a good call."""
+    from feed_src_cases import Runner
+    runner = Runner()
+    fn, EINVAL = runner.fn, runner._lib.Y3_EINVAL
     rng = np.random.RandomState(0)
-    pjs = [fn.make_job(**random_case(rng, out_size=(32, 32))) for _ in range(3)]
-    blob, scratch, recs = fn.plan_batch(pjs)
-    dev_blob = torch.from_numpy(blob).cuda()
-    tables = torch.from_numpy(fn.device_tables()).cuda()
-    out = torch.empty((3, 32, 32, 3), device='cuda')
-    sc = torch.empty(max(scratch, 16), dtype=torch.uint8, device='cuda')
-    call = lambda *a: _lib.lib().y3_feed_run(fw.context(), *a)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    assert call(p(dev_blob), blob.ctypes.data, 3, p(tables), p(sc), sc.numel(), p(out), 32, 32) == 0
-    assert call(p(dev_blob), blob.ctypes.data, 3, p(tables), p(sc), sc.numel(), p(out), 48, 32) == _lib.Y3_EINVAL
-    if scratch > 16:
-        assert call(p(dev_blob), blob.ctypes.data, 3, p(tables), p(sc), scratch - 16, p(out), 32, 32) == _lib.Y3_EINVAL
-        assert b'scratch' in _lib.lib().y3_last_error()
-    assert call(None, blob.ctypes.data, 3, p(tables), p(sc), sc.numel(), p(out), 32, 32) == _lib.Y3_EINVAL
-    torch.cuda.synchronize()
+    live = lambda d: (d.live_x1 - d.live_x0) * (d.live_y1 - d.live_y0)
+    hpass = lambda d: d.mode == 4 and d.horizontal and d.tmp_rows > 0
+    cases, p = _packed_plan(runner, rng, lambda recs, blob: all(live(d) and d.r1_w * d.r1_h for d in recs) and any(hpass(d) for d in recs))
+    recs, n, blob_bytes = p['recs'], 3, p['blob'].size
+    assert all(tuple(d.reserved) == (0, 0, 0) for d in recs)
+
+    def good(**kw):
+        p['out'].fill_(float('nan'))
+        assert runner.call(p, arena=False, src_bytes=0, **kw) == 0, runner.lib.y3_last_error()
+        _compare(cases, fn, p['out'])
+
+    def refused(what, **kw):
+        p['out'].fill_(float('nan'))
+        assert runner.call(p, arena=False, src_bytes=0, **kw) == EINVAL
+        message = runner.lib.y3_last_error()
+        assert what in message, message
+        torch.cuda.synchronize()
+        assert torch.isnan(p['out']).all()          # nothing was launched
+        good()
+
+    def edited(change, of=None):
+        copy = (fn.DJob * n).from_buffer_copy(bytes(recs if of is None else of))
+        change(copy)
+        return copy
+
+    good()
+    refused(b'the batch is', out_hw=(48, 32))                       # a wrong output size
+    # the scratch: what the jobs write, 16-aligned, then the records; that much is enough and 16 bytes less is not
+    need = max(max(d.win_off + live(d) * 3, d.tmp_off + (d.tmp_rows * d.res_w * 3 if hpass(d) else 0)) for d in recs)
+    enough = (need + 15) // 16 * 16 + n * 208
+    assert 16 < enough <= p['scratch'].numel()
+    good(scratch_bytes=enough)
+    refused(b'scratch', scratch_bytes=enough - 16)
+    refused(b'null argument', blob=False)                           # a NULL blob
+    # a packed source that ends one byte past blob_bytes
+    k = 1
+    size = recs[k].r1_w * recs[k].r1_h * 3
+    refused(b'job %d: packed source past the blob' % k, recs=edited(lambda r: setattr(r[k], 'img1_off', blob_bytes - size + 1)))
+    # a live rectangle wider than the window
+    refused(b'job %d: live rectangle outside the window' % k, recs=edited(lambda r: setattr(r[k], 'live_x1', r[k].win_w + 1)))
+    # a horizontal pass whose rows run past the scratch
+    k = next(i for i, d in enumerate(recs) if hpass(d))
+    rows = (p['scratch'].numel() - recs[k].tmp_off) // (recs[k].res_w * 3) + 1
+    assert recs[k].tmp_off + rows * recs[k].res_w * 3 > p['scratch'].numel()
+    refused(b'job %d: ' % k, recs=edited(lambda r: setattr(r[k], 'tmp_rows', rows)))
+    # stale records: those of another batch, whose blob is larger and whose last job's y table is that blob's last piece
+    tabled = lambda d: d.mode in (0, 1) or (d.mode == 4 and d.vertical)
+    _, other = _packed_plan(runner, rng, lambda r, blob: blob.size > blob_bytes + 16 and tabled(r[2]) and
+                            r[2].ytab_off + r[2].res_h * 4 > blob_bytes)
+    refused(b': job ', recs=edited(lambda r: None, of=other['recs']))
+    # a blob too small to hold the records themselves
+    refused(b'records do not fit', blob_bytes=n * 208 - 1)
 
 
 def test_feeder_with_device_pixels_serves_the_batches_of_the_host_path(tmp_path):

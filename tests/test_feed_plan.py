@@ -27,7 +27,7 @@ def emul(tmp_path_factory):
                            os.path.join(ROOT, 'tests', 'feed_emul.cpp'), '-o', out])
     lib = ctypes.CDLL(out)
     lib.y3f_emulate.restype = ctypes.c_int
-    lib.y3f_emulate.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.y3f_emulate.argtypes = [ctypes.c_void_p] + [ctypes.c_int] + [ctypes.c_void_p] * 4
     return lib
 
 
@@ -38,7 +38,7 @@ def run_emulated(fn, emul, cases):
     scratch = np.full(max(scratch_bytes, 16), 0xA5, np.uint8)         # poisoned: nothing may be read before it is written
     oh, ow = pjs[0].job.out_h, pjs[0].job.out_w
     out = np.full((len(pjs), oh, ow, 3), np.nan, np.float32)
-    assert emul.y3f_emulate(blob.ctypes.data, len(pjs), tables.ctypes.data, scratch.ctypes.data, out.ctypes.data) == 0
+    assert emul.y3f_emulate(blob.ctypes.data, len(pjs), tables.ctypes.data, None, scratch.ctypes.data, out.ctypes.data) == 0
     return out, recs
 
 

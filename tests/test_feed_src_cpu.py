@@ -1,6 +1,6 @@
 """CPU tests of the feeder's by-reference plan (include/yolo355_feed.h: y3f_plan_batch_src): with nothing in the arena it is
 y3f_plan_batch's plan byte for byte; with sources in an arena its records are consistent, and the per-pixel functions the
-GPU kernels are made of (csrc/y3_feed_px.h, the arena form of window_pixel) run on the host (tests/feed_src_emul.cpp) give
+GPU kernels are made of (csrc/y3_feed_px.h, the arena form of window_pixel) run on the host (tests/feed_emul.cpp) give
 y3f_sample's bytes.  tests/test_feed_src_gpu.py repeats the comparison with the kernels themselves."""
 import ctypes
 import os
@@ -23,12 +23,12 @@ def fn():
 
 @pytest.fixture(scope='module')
 def emul(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp('feed_src_emul') / 'libfeed_src_emul.so')
+    out = str(tmp_path_factory.mktemp('feed_emul') / 'libfeed_emul.so')
     subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-fno-fast-math',
-                           os.path.join(ROOT, 'tests', 'feed_src_emul.cpp'), '-o', out])
+                           os.path.join(ROOT, 'tests', 'feed_emul.cpp'), '-o', out])
     lib = ctypes.CDLL(out)
-    lib.y3f_emulate_src.restype = ctypes.c_int
-    lib.y3f_emulate_src.argtypes = [ctypes.c_void_p] + [ctypes.c_int] + [ctypes.c_void_p] * 4
+    lib.y3f_emulate.restype = ctypes.c_int
+    lib.y3f_emulate.argtypes = [ctypes.c_void_p] + [ctypes.c_int] + [ctypes.c_void_p] * 4
     lib.y3f_record_fault.restype = ctypes.c_char_p
     lib.y3f_record_fault.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t]
     return lib
@@ -101,7 +101,7 @@ def test_device_functions_equal_y3f_sample_by_reference(fn, emul, interp):
     scratch = np.full(max(scratch_bytes, 16), POISON, np.uint8)      # poisoned: nothing may be read before it is written
     out = np.full((len(cases), 48, 48, 3), np.nan, np.float32)
     before = arena.copy()
-    assert emul.y3f_emulate_src(blob.ctypes.data, len(cases), tables.ctypes.data, arena.ctypes.data, scratch.ctypes.data,
+    assert emul.y3f_emulate(blob.ctypes.data, len(cases), tables.ctypes.data, arena.ctypes.data, scratch.ctypes.data,
                                 out.ctypes.data) == 0
     assert np.array_equal(arena, before)
     bad = []
@@ -115,7 +115,7 @@ def test_device_functions_equal_y3f_sample_by_reference(fn, emul, interp):
 
 
 def test_record_check_names_what_is_out_of_range(fn, emul):
-    """The check y3_feed_run_src makes before launching (y3fpx::record_fault), on the host: every record of a good plan
+    """The check y3_feed_run makes before launching (y3fpx::record_fault), on the host: every record of a good plan
     passes at the exact sizes, and fails one byte short of each."""
     rng = np.random.RandomState(11)
     cases = [random_case(rng, out_size=(48, 48)) for _ in range(64)]

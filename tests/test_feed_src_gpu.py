@@ -1,46 +1,16 @@
-"""The feeder's pixel work over sources kept in HBM (y3f_plan_batch_src + y3_feed_run_src, include/yolo355.h): the kernels
+"""The feeder's pixel work over sources kept in HBM (y3f_plan_batch_src + y3_feed_run, include/yolo355.h): the kernels
 against liby3feed.so's y3f_sample on mixed batches (sources in an arena next to packed ones), at training geometry, with
 bad arguments, and through Feeder(cache_bytes=...), whose batches must be the uncached feeder's byte for byte - also once
 the files are gone from the disk."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import COCO_ANCHORS
 from feed_cases import describe, random_case, random_image
-from feed_src_cases import place, ref_jobs
+from feed_src_cases import Runner, place, ref_jobs
 
 pytestmark = pytest.mark.gpu
-
-
-class Runner(object):
-    """y3_feed_run_src on a plan of feed_native.plan_batch(..., src1, src2) and a numpy arena."""
-
-    def __init__(self):
-        from yolov3_tensorflow_amd import _lib, feed_native
-        from yolov3_tensorflow_amd import framework as fw
-        self.lib, self._lib, self.fn, self.ctx = _lib.lib(), _lib, feed_native, fw.context()
-        self.tables = torch.from_numpy(feed_native.device_tables()).cuda()
-
-    def plan(self, cases, arena, src1, src2):
-        blob, scratch_bytes, recs = self.fn.plan_batch(ref_jobs(self.fn, cases, src1, src2), src1=src1, src2=src2)
-        n = len(cases)
-        ow, oh = cases[0]['out_size']
-        return dict(blob=blob, recs=recs, n=n, oh=oh, ow=ow, dev_blob=torch.from_numpy(blob).cuda(),
-                    arena=torch.from_numpy(arena).cuda(),
-                    scratch=torch.full((scratch_bytes + 16 + n * 208,), 0xA5, dtype=torch.uint8, device='cuda'),
-                    out=torch.full((n, oh, ow, 3), float('nan'), device='cuda'))
-
-    def call(self, p, recs=None, blob_bytes=None, arena=True, src_bytes=None):
-        """The status of one call; recs: a host copy of the records to pass in place of the blob's."""
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-        return self.lib.y3_feed_run_src(
-            self.ctx, ptr(p['dev_blob']), p['blob'].size if blob_bytes is None else blob_bytes,
-            ctypes.c_void_p(p['blob'].ctypes.data if recs is None else ctypes.addressof(recs)), p['n'], ptr(self.tables),
-            ptr(p['scratch']), p['scratch'].numel(), ptr(p['arena']) if arena else None,
-            p['arena'].numel() if src_bytes is None else src_bytes, ptr(p['out']), p['oh'], p['ow'])
 
 
 @pytest.fixture(scope='module')

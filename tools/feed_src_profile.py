@@ -1,11 +1,14 @@
 #!/usr/bin/env python
-"""One training-size batch (64 jobs, 640x480 sources, mix-up, expansion, letterbox to 416x416) through y3_feed_run (packed
-sources) and through y3_feed_run_src (every source in a device arena), a few times each, for a kernel trace:
+"""One training-size batch (64 jobs, 640x480 sources, mix-up, expansion, letterbox to 416x416) a few times through one leg,
+for a kernel trace:
 
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/feed_src_profile.py [--repeat 20]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/feed_src_profile.py --leg LEG [--repeat 20]
 
-The three kernels of either entry show up under their own names (feed_*_kernel / feed_*_src_kernel).  The two results
-are compared before the script ends."""
+    packed  every source packed into the batch's blob (what a feeder without a source cache runs)
+    arena   every source in a device arena, read there by reference
+
+Both go through y3_feed_run (feed_window_kernel<false> / <true>, feed_horizontal_kernel, feed_output_kernel).  Every leg first
+computes the packed result in its own process and ends by comparing its bytes with it."""
 import argparse
 import os
 import sys
@@ -18,6 +21,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--leg', choices=('packed', 'arena'), required=True)
     ap.add_argument('--repeat', type=int, default=20)
     args = ap.parse_args()
     import torch
@@ -26,7 +30,7 @@ def main():
     from yolov3_tensorflow_amd.feed_device import DevicePixels
     rng = np.random.RandomState(0)
     images = [rng.randint(0, 256, (48, 64, 3)).astype(np.uint8).repeat(10, 0).repeat(10, 1) for _ in range(64)]
-    packed, by_ref = [], []
+    packed, keyed = [], []
     for i in range(64):
         partner = (i + 1) % 64 if i % 2 else None
         ratio = rng.uniform(1, 4) if i % 2 else 1.0
@@ -41,20 +45,24 @@ def main():
                           float(rng.uniform(0.5, 1.5))),
                   offset=off, window=window, interp=i % 5, resized=resized, out_size=(416, 416),
                   pad=((416 - resized[0]) // 2, (416 - resized[1]) // 2), pad_value=128, flip_x=bool(i % 2))
-        for jobs in (packed, by_ref):
+        for jobs in (packed, keyed):
             pj = fn.make_job(images[i], None if partner is None else images[partner], **kw)
-            pj.key1, pj.key2 = i, partner
             jobs.append(pj)
+        keyed[-1].key1, keyed[-1].key2 = i, partner
     dp = DevicePixels()
-    cache = SourceCache(dp.device, 64 * 480 * 640 * 3 + 4096)
     want = dp.run(packed)
-    got = dp.run(by_ref, cache=cache)           # (takes every image in)
+    cache = SourceCache(dp.device, 64 * 480 * 640 * 3 + 4096) if args.leg == 'arena' else None
+    jobs = packed if cache is None else keyed
+    got = dp.run(jobs, cache=cache)             # (arena: takes every image in)
     for _ in range(args.repeat):
-        want = dp.run(packed)
-        got = dp.run(by_ref, cache=cache)
+        got = dp.run(jobs, cache=cache)
     torch.cuda.synchronize()
-    print('cache: %r' % (cache.stats(),))
-    print('y3_feed_run_src == y3_feed_run: %s' % bool(torch.equal(want, got)))
+    if cache is not None:
+        print('cache: %r' % (cache.stats(),))
+        assert cache.stats()['images'] == 64, cache.stats()
+    same = bool(torch.equal(want, got))
+    print('%s == packed: %s' % (args.leg, same))
+    assert same
 
 
 if __name__ == '__main__':

@@ -168,9 +168,8 @@ PROTOTYPES = {
                               POINTER(c_float), c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     "y3_process_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                POINTER(c_float), c_void_p, c_void_p, c_void_p]),
-    "y3_feed_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int]),
-    "y3_feed_run_src": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                c_void_p, c_int, c_int]),
+    "y3_feed_run": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                            c_void_p, c_int, c_int]),
     "y3_jpeg_decode": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                c_void_p]),
     "y3_box_iou": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_void_p]),
@@ -215,7 +214,7 @@ def lib():
             fn = getattr(handle, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args
-        if handle.y3_abi_version() != 4:
+        if handle.y3_abi_version() != 5:
             raise Y3Error("libyolo355.so ABI version mismatch")
         _lib = handle
     return _lib

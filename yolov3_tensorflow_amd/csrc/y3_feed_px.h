@@ -87,6 +87,7 @@ Y3F_HD void window_pixel(const y3f_djob& d, const uint8_t* blob, const uint8_t* 
     }
 }
 
+// a packed plan: every source in the blob
 Y3F_HD void window_pixel(const y3f_djob& d, const uint8_t* blob, const y3f_dtables& T, int wx, int wy, uint8_t out[3]) {
     window_pixel<false>(d, blob, nullptr, T, wx, wy, out);
 }
@@ -207,7 +208,7 @@ Y3F_HD void output_pixel(const y3f_djob& d, const uint8_t* blob, const uint8_t* 
     out[0] = T.unit255[px[0]], out[1] = T.unit255[px[1]], out[2] = T.unit255[px[2]];
 }
 
-// ---- 5. is a record safe to run?  (y3_feed_run_src checks every record of its own copy before it launches anything) ------
+// ---- 5. is a record safe to run?  (y3_feed_run checks every record of its own copy before it launches anything) ----------
 // Every byte the functions above read or write for `d` through the record's own fields lies inside a blob of blob_bytes, an
 // arena of arena_bytes (0: there is none) and a scratch of scratch_bytes.  Returns what is wrong, or nullptr.
 inline const char* record_fault(const y3f_djob& d, size_t blob_bytes, size_t arena_bytes, size_t scratch_bytes) {

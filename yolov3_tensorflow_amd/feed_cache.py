@@ -3,14 +3,14 @@
 
 A training run reads the same files every epoch and a decoded image never changes, so each file is decoded once, its 8-bit
 RGB pixels are copied into one device arena, and from then on the feed kernels read them where they lie
-(y3f_plan_batch_src / y3_feed_run_src): for such an image the host decodes nothing, packs no source rectangle into the
+(y3f_plan_batch_src / y3_feed_run): for such an image the host decodes nothing, packs no source rectangle into the
 batch's blob and uploads no pixels.  The arena is a torch tensor this object owns (the library allocates nothing), filled
 front to back; nothing is ever evicted or moved, so an offset handed out stays valid for the life of the cache, and an
 image that does not fit is left out for good and served packed, as without a cache.
 
 Threads: `shape_of` may be called from any thread (the feeder's workers ask it before they open a file); everything else
 belongs to the feeder's coordinator thread.  Ordering: an insert's copy goes onto torch's CURRENT stream - the feeder's
-side stream, the one that later runs y3_feed_run_src - and stream order is all that is needed.
+side stream, the one that later runs y3_feed_run - and stream order is all that is needed.
 """
 import numpy as np
 

@@ -3,8 +3,8 @@
 
 Host: y3f_plan_batch (liby3feed.so) writes one blob per batch into a recycled pinned buffer - the job records, the source
 pixels the crop windows can see, the jitter maps, Pillow's filter tables -; one asynchronous H2D copy (8-bit sources: a
-third of the bytes of the float32 batch the host path uploads); then y3_feed_run (libyolo355.so): three launches.  The
-result is bit-identical to feed_native.sample (tests/test_feed_gpu.py).  There is no CPU form of this module: without a
+third of the bytes of the float32 batch the host path uploads); then y3_feed_run (libyolo355.so) checks every record
+against the sizes it is given and makes three launches.  The result is bit-identical to feed_native.sample (tests/test_feed_gpu.py).  There is no CPU form of this module: without a
 HIP device it raises.
 """
 import ctypes
@@ -41,7 +41,7 @@ class DevicePixels(object):
     def run(self, pixel_jobs, threads=0, cache=None):
         """[PixelJob] (all with the same output size) -> float32 device tensor [n, out_h, out_w, 3].  `cache`: a
         feed_cache.SourceCache on this device; every source it holds (or takes in now) is read from its arena by reference
-        (y3f_plan_batch_src + y3_feed_run_src: the same bytes), the others are packed into the blob as without one."""
+        (y3f_plan_batch_src: the same bytes), the others are packed into the blob as without one."""
         import torch
         n = len(pixel_jobs)
         if n == 0:
@@ -61,18 +61,13 @@ class DevicePixels(object):
             blob.copy_(pinned[:need], non_blocking=True)
             out = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
             p = lambda t: ctypes.c_void_p(t.data_ptr())
-            if cache is None:
-                scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=self.device)
-                _lib.check(_lib.lib().y3_feed_run(fw.context(self.device), p(blob), ctypes.c_void_p(pinned.data_ptr()), n,
-                                                  p(self.tables), p(scratch), scratch.numel(), p(out), out_h, out_w))
-            else:                       # (the checked copy of the records goes behind the jobs' scratch)
-                scratch = torch.empty(scratch_bytes + 16 + n * ctypes.sizeof(feed_native.DJob), dtype=torch.uint8,
-                                      device=self.device)
-                arena = cache.arena
-                _lib.check(_lib.lib().y3_feed_run_src(fw.context(self.device), p(blob), need, ctypes.c_void_p(pinned.data_ptr()), n,
-                                                      p(self.tables), p(scratch), scratch.numel(),
-                                                      None if arena is None else p(arena), 0 if arena is None else arena.numel(),
-                                                      p(out), out_h, out_w))
+            # (the checked copy of the records goes behind the jobs' scratch)
+            scratch = torch.empty(scratch_bytes + 16 + n * ctypes.sizeof(feed_native.DJob), dtype=torch.uint8, device=self.device)
+            arena = None if cache is None else cache.arena
+            _lib.check(_lib.lib().y3_feed_run(fw.context(self.device), p(blob), need, ctypes.c_void_p(pinned.data_ptr()), n,
+                                              p(self.tables), p(scratch), scratch.numel(),
+                                              None if arena is None else p(arena), 0 if arena is None else arena.numel(),
+                                              p(out), out_h, out_w))
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
         self.busy.append((ev, pinned))

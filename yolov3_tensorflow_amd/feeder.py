@@ -32,7 +32,7 @@ rebuilt for one process per GPU with the device-resident target assignment of th
     image moved to three launches of a few hundred microseconds per batch;
   * cache_bytes > 0 (with pixels='gpu'): every file is decoded once; its 8-bit pixels stay in a device arena of that many
     bytes (feed_cache.SourceCache, kept over the epochs, nothing evicted) and later uses read them there by reference
-    (y3f_plan_batch_src / y3_feed_run_src): no decode, no source bytes in the blob.  The same batches, byte for byte;
+    (y3f_plan_batch_src / y3_feed_run): no decode, no source bytes in the blob.  The same batches, byte for byte;
   * the consumer makes its compute stream wait for the copy's event (no host synchronisation) and runs `y3_process_box`
     for the whole batch on the device (utils.data_utils.process_box_batch: bit-exact against the reference's
     process_box), so the three y_true tensors (3.6 MB per 416x416 image - more than the image itself) never cross PCIe;
