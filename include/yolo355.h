@@ -632,6 +632,30 @@ int y3_voc_ap(y3_ctx* ctx, const uint8_t* tp, const int32_t* seg_start, int rows
               int class_num, int use_07_metric, const double* thresholds_host11, void* scratch, size_t scratch_bytes,
               double* out);
 
+/* Recall / precision counts of one training batch on the device: utils/eval_utils.py:142-232 (`evaluate_on_gpu`), as
+ * restated in yolov3_tensorflow_amd/utils/eval_utils.py:53-99, on the tensors y3_nms leaves in HBM (out_boxes f32
+ * [n][cap][4], out_labels int32 [n][cap], out_counts int32 [n]) and the three y_true tensors of the batch
+ * (f32 [n][g][g'][3][5 + class_num + 1] with g = h/32, h/16, h/8 and g' = w/32, w/16, w/8; h, w = the network input size).
+ *   gather: per image, the cells of y_true_1, _2, _3 in that order, row-major (row, column, anchor) inside a scale.  A
+ *     cell holds an object when an entry of its class slice (channels 5 .. 5+class_num-1) is > 0 - the precondition is that
+ *     the slice is finite and >= 0, where this is eval_utils' `sum > 0`; its label is the slice's first maximum, its box
+ *     x0y0 = xy - wh / 2., x1y1 = x0y0 + wh in float64.  Objects are compacted IN THAT ORDER into the scratch; at most gt_cap
+ *     per image are kept and state[0] += the number dropped (the caller zeroes state; a non-zero word voids the table).
+ *   match: every detection k < out_counts[i] adds 1 to n_pred[label]; its IoU (calc_iou, eval_utils.py:35-50: float64 with
+ *     the detection's width, height and area in float32) with every object of the image, of any label; the first maximum
+ *     in gather order (a NaN counts as one); a hit when that IoU > iou_thresh and that object's label is the detection's.
+ *   tally: every object adds 1 to n_true[label], every object hit at least once adds 1 to n_tp[label].
+ * table: int64 [class_num][3] = (n_tp, n_true, n_pred), accumulated with integer atomics into what the caller zeroed, so
+ * several batches can be summed in one table; the counts are the same in every run.  Every index read from device memory
+ * is clamped to the extents passed here.  scratch: y3_batch_eval_scratch_bytes(n, gt_cap) (0 for non-positive arguments);
+ * its contents on entry do not matter.  Asynchronous on the context's stream.  Y3_EINVAL before any launch: a null
+ * pointer, a non-positive size, h or w not a multiple of 32, n > 65535, a scratch too small, a product (n * cap,
+ * n * gt_cap, n * cells, 1024 * channels) beyond 2^31 - 1. */
+size_t y3_batch_eval_scratch_bytes(int n, int gt_cap);
+int y3_batch_eval(y3_ctx* ctx, const float* out_boxes, const int32_t* out_labels, const int32_t* out_counts, int n, int cap,
+                  const float* y_true_1, const float* y_true_2, const float* y_true_3, int h, int w, int class_num,
+                  double iou_thresh, int gt_cap, void* scratch, size_t scratch_bytes, long long* table, int32_t* state);
+
 /* K11: g <- g*grad_scale + weight_decay*w (slim.l2_regularizer, model.py:49) ; g <- tf.clip_by_norm(g, clip)
  * (train.py:113-114) ; TF1 update rule (utils/misc_utils.py:151-161).  kind: 0 sgd, 1 momentum (slot0 =
  * accumulator), 2 adam (slot0 = m, slot1 = v, decay = beta1, lr = lr_t), 3 rmsprop (slot0 = ms, slot1 = mom).

@@ -109,6 +109,9 @@ def build_parser():
     p.add_argument('--use_voc_07_metric', type=_bool, default=False)
     p.add_argument('--map_on_device', type=_bool, default=False,
                    help='validation: match detections and compute AP on the device (eval_utils.DeviceEval)')
+    p.add_argument('--batch_eval_on_device', type=_bool, default=False,
+                   help='training-batch recall / precision: NMS, matching and counts for the whole batch on the device '
+                        '(eval_utils.evaluate_on_device)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compute_dtype', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'], default='f32',
                    help='train-step mode: fp32-accurate modes, or bf16 = mixed precision on the bf16 matrix pipe')
@@ -190,7 +193,7 @@ def main(argv=None):
     import torch.distributed as dist
     import yolov3_tensorflow_amd as y3
     from yolov3_tensorflow_amd import training, framework as fw
-    from yolov3_tensorflow_amd.utils.eval_utils import evaluate_on_gpu
+    from yolov3_tensorflow_amd.utils.eval_utils import evaluate_on_gpu, evaluate_on_device
     from yolov3_tensorflow_amd.utils.misc_utils import (parse_anchors, read_class_names, AverageMeter,
                                                         config_learning_rate, config_optimizer, load_weights,
                                                         save_weights, run_ops, Saver)
@@ -291,8 +294,12 @@ def main(argv=None):
             if gs % args.train_evaluation_step == 0 and gs > 0:
                 with y3.variable_scope('yolov3'):
                     y_pred = yolo_model.predict(yolo_model.forward(images, False))
-                recall, precision = evaluate_on_gpu(None, gpu_nms_op, None, None, y_pred, y_true, args.class_num,
-                                                    args.nms_threshold)
+                if args.batch_eval_on_device:
+                    recall, precision = evaluate_on_device(y_pred, y_true, args.class_num, args.nms_topk, args.score_threshold,
+                                                           args.nms_threshold, iou_thresh=args.nms_threshold)
+                else:
+                    recall, precision = evaluate_on_gpu(None, gpu_nms_op, None, None, y_pred, y_true, args.class_num,
+                                                        args.nms_threshold)
                 history['recall'].append(recall)
                 info = "Epoch: {}, global_step: {} | loss: total: {:.2f}, xy: {:.2f}, wh: {:.2f}, conf: {:.2f}, " \
                        "class: {:.2f} | ".format(epoch, int(gs), *[m.average for m in meters])

@@ -182,6 +182,9 @@ PROTOTYPES = {
     "y3_voc_ap_scratch_bytes": (c_size_t, [c_int]),
     "y3_voc_ap": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p,
                           c_size_t, c_void_p]),
+    "y3_batch_eval_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "y3_batch_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                              c_int, c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "y3_optimizer_scratch_bytes": (c_size_t, []),
     "y3_clip_update": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float,
                                c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p]),

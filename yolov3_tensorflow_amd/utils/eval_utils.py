@@ -5,6 +5,7 @@ SURVEY.md §8(f) row 2.  Same function names, argument order and return values a
   calc_iou            utils/eval_utils.py:13-46     IoU matrix [N,V] (numpy, float64 in / float64 out)
   evaluate_on_cpu     utils/eval_utils.py:49-139    recall / precision of one batch, NMS = cpu_nms semantics
   evaluate_on_gpu     utils/eval_utils.py:142-232   same with the gpu_nms op
+  evaluate_on_device  (same rule)                   the batch at once on the device (y3_batch_eval), one table back
   get_preds_gpu       utils/eval_utils.py:235-261   [[image_id, x_min, y_min, x_max, y_max, score, label], ...]
   parse_gt_rec        utils/eval_utils.py:264-307   annotation file -> {img_id: [[x0, y0, x1, y1, label], ...]}
   voc_ap, voc_eval    utils/eval_utils.py:312-423   PASCAL VOC AP (area and 11-point) per class
@@ -118,6 +119,91 @@ def evaluate_on_gpu(sess, gpu_nms_op, pred_boxes_flag, pred_scores_flag, y_pred,
     `sess`, `pred_boxes_flag`, `pred_scores_flag` exist for signature compatibility and are ignored.
     '''
     return _evaluate(y_pred, y_true, num_classes, gpu_nms_op, iou_thresh, calc_now)
+
+
+_BEVAL_WS = {}      # (device index, stream) -> uint8 tensor: y3_batch_eval's scratch, reused by every call on that stream
+
+
+def _beval_workspace(dev, nbytes):
+    """Scratch of one y3_batch_eval call: one buffer per (device, stream), grown on demand, like nms_utils._workspace."""
+    import torch
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+    ws = _BEVAL_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _BEVAL_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def batch_eval_counts(detections, y_true, num_classes, iou_thresh=0.5, gt_cap=None, table=None):
+    """y3_batch_eval (include/yolo355.h) on device tensors: `detections` is what gpu_nms_batched(..., lazy=True) returned, or
+    its (boxes [n,cap,4] f32, scores, labels [n,cap] i32, counts [n] i32) device tensors; y_true the batch's three
+    process_box tensors.  Returns the int64 device tensor [num_classes + 1, 3]: rows (n_tp, n_true, n_pred) per class, and in
+    row num_classes, column 0, the number of objects dropped for lack of gt_cap.  `table`: such a tensor to add to
+    (several batches in one table).  Nothing waits for the host."""
+    import ctypes
+    import torch
+    from .. import _lib, framework as fw
+    ob, _, ol, cnt = detections.device_tensors() if hasattr(detections, 'device_tensors') else detections
+    yt = [fw.as_device_f32(t) for t in y_true]
+    n, cap, C = int(ob.shape[0]), int(ob.shape[1]), int(num_classes)
+    if len(yt) != 3 or any(t.dim() != 5 or int(t.shape[0]) != n or int(t.shape[3]) != 3 or int(t.shape[4]) != C + 6 for t in yt):
+        raise ValueError("batch_eval_counts: y_true must be three [%d, g, g, 3, %d] tensors, got %s" % (
+            n, C + 6, [tuple(t.shape) for t in yt]))
+    h, w = 32 * int(yt[0].shape[1]), 32 * int(yt[0].shape[2])
+    if [tuple(t.shape[1:3]) for t in yt] != [(h // 32, w // 32), (h // 16, w // 16), (h // 8, w // 8)]:
+        raise ValueError("batch_eval_counts: y_true grids %s are not those of one input size" % [tuple(t.shape[1:3]) for t in yt])
+    if ob.dtype != torch.float32 or ol.dtype != torch.int32 or cnt.dtype != torch.int32 or tuple(ol.shape) != (n, cap) \
+            or tuple(cnt.shape) != (n,):
+        raise ValueError("batch_eval_counts: detections must be fp32 boxes [n,cap,4], int32 labels [n,cap] and counts [n]")
+    dev = ob.device
+    if gt_cap is None:
+        gt_cap = min(sum(int(t.shape[1]) * int(t.shape[2]) * 3 for t in yt), 4096)
+    gt_cap = int(gt_cap)
+    L = _lib.lib()
+    nbytes = L.y3_batch_eval_scratch_bytes(n, gt_cap)
+    if nbytes == 0:
+        raise ValueError("batch_eval_counts: non-positive dimension (n=%d, gt_cap=%d)" % (n, gt_cap))
+    ws = _beval_workspace(dev, nbytes)
+    if table is None:
+        table = torch.zeros((C + 1, 3), dtype=torch.int64, device=dev)
+    ob, ol, cnt = ob.contiguous(), ol.contiguous(), cnt.contiguous()
+    state = table[C].view(torch.int32)      # the overflow word: the first 4 bytes of the row behind the classes
+    _lib.check(L.y3_batch_eval(fw.context(dev), fw.ptr(ob), fw.ptr(ol), fw.ptr(cnt), n, cap, fw.ptr(yt[0]), fw.ptr(yt[1]),
+                               fw.ptr(yt[2]), h, w, C, ctypes.c_double(iou_thresh), gt_cap, fw.ptr(ws), ctypes.c_size_t(nbytes),
+                               fw.ptr(table), fw.ptr(state)))
+    return table
+
+
+def evaluate_on_device(y_pred, y_true, num_classes, max_boxes=50, score_thresh=0.5, nms_thresh=0.5, iou_thresh=0.5,
+                       calc_now=True, gt_cap=None):
+    '''
+    evaluate_on_gpu with the whole batch kept on the device: one gpu_nms_batched call, then y3_batch_eval
+    (include/yolo355.h) gathers the ground truth out of y_true, matches and counts; one [num_classes + 1, 3] integer table
+    comes back.  y_pred: (boxes, confs, probs) as yolov3.predict returns them, or (boxes, scores) with scores = confs * probs
+    (predict(..., with_scores=True)).  Returns what evaluate_on_gpu returns for
+    gpu_nms_op = functools.partial(gpu_nms, num_classes=.., max_boxes=.., score_thresh=.., nms_thresh=..).
+    gt_cap: objects kept per image (default: the image's cell count, at most 4096); ValueError when an image has more.
+    Precondition: y_true's class entries are finite and >= 0 (csrc/y3_beval_px.h).
+    '''
+    from .. import framework as fw
+    from .nms_utils import gpu_nms_batched
+    if len(y_pred) == 2:
+        boxes, scores = y_pred
+    else:
+        boxes, confs, probs = y_pred
+        scores = fw.as_device_f32(confs) * fw.as_device_f32(probs)
+    dets = gpu_nms_batched(boxes, scores, num_classes, max_boxes, score_thresh, nms_thresh, lazy=True)
+    table = batch_eval_counts(dets, y_true, num_classes, iou_thresh, gt_cap).cpu().numpy()      # the one transfer
+    fw.check_context(dets.device_tensors()[0].device)
+    dropped = int(table[num_classes, 0] & 0xFFFFFFFF)
+    if dropped:
+        raise ValueError("evaluate_on_device: %d objects did not fit gt_cap: raise gt_cap" % dropped)
+    n_tp, n_true, n_pred = table[:num_classes, 0], table[:num_classes, 1], table[:num_classes, 2]
+    if calc_now:
+        # avoid divided by 0
+        return n_tp.sum() / (n_true.sum() + 1e-6), n_tp.sum() / (n_pred.sum() + 1e-6)
+    as_dict = lambda a: {c: int(a[c]) for c in range(num_classes)}
+    return as_dict(n_tp), as_dict(n_true), as_dict(n_pred)
 
 
 def _rows(image_id, boxes, scores, labels):
