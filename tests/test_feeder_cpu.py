@@ -264,3 +264,122 @@ def test_fix_crop_labels_keeps_each_box_with_its_class(tmp_path, monkeypatch, na
     monkeypatch.setenv('Y3_FIX_CROP_LABELS', '1')                    # 'val' mode has no crop: nothing to carry
     _, _, bv, lv = parse_sample(line, [96, 64], 'val', True)
     assert bv.shape == (2, 5) and list(lv) == [0, 2]
+
+
+class _Ledger(object):
+    """Mixed into a pool of batch buffers: every buffer it lent, and every one that came back (handed back or dropped)."""
+
+    def __init__(self):
+        super(_Ledger, self).__init__()
+        self.lent, self.back = [], []
+
+    def take(self, shape):
+        buf = super(_Ledger, self).take(shape)
+        self.lent.append(id(buf))
+        return buf
+
+    def give(self, event, buf):
+        self.back.append(id(buf))
+        super(_Ledger, self).give(event, buf)
+
+    def _drop(self, buf):
+        self.back.append(id(buf))
+        super(_Ledger, self)._drop(buf)
+
+
+class _NoSharedMemory(object):
+    def take(self, shape):
+        return None
+
+
+def _flat_set(tmp_path, n=5):
+    from PIL import Image
+    rng = np.random.RandomState(8)
+    lines = []
+    for i in range(n):
+        path = str(tmp_path / ('flat_%d.jpg' % i))
+        Image.fromarray(rng.randint(0, 256, (64, 96, 3)).astype(np.uint8)).save(path, quality=90)
+        x0, y0 = rng.uniform(0, 40), rng.uniform(0, 24)
+        lines.append('%d %s 96 64 %d %.1f %.1f %.1f %.1f' % (i, path, i % 3, x0, y0, x0 + rng.uniform(10, 50), y0 + rng.uniform(10, 36)))
+    return lines
+
+
+def _host_half(lines, backend, buffers, shared, stop_after=None):
+    """Feeder._host_batches alone over one plan: [(ids, images, boxes, labels, counts)] as copies, every buffer handed back
+    as the device half does after its upload (no event: nothing reads it any more)."""
+    import threading
+    from yolov3_tensorflow_amd import feeder
+    f = feeder.Feeder(lines, 3, 3, [96, 64], np.arange(18, dtype=np.float32) + 5, mode='train', use_mix_up=True,
+                      letterbox_resize=True, num_threads=3, prefetch=2, seed=7, backend=backend, pixels='host')
+    stop, got = threading.Event(), []
+    for size, ids, images, boxes, labels, counts, owner in f._host_batches(0, f._delivery(buffers, shared), stop):
+        assert size == [96, 64] and np.asarray(images).shape == (len(ids), 64, 96, 3)
+        got.append((ids, np.asarray(images).copy(), boxes.copy(), labels.copy(), counts.copy()))
+        owner[0].give(None, owner[1])
+        if len(got) == stop_after:
+            stop.set()
+    f.close()
+    for pool in (buffers, shared):
+        assert sorted(getattr(pool, 'lent', [])) == sorted(getattr(pool, 'back', []))      # each one back exactly once
+    return got
+
+
+def _same_batches(a, b):
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        assert x[0] == y[0]
+        for u, v in zip(x[1:], y[1:]):
+            assert u.dtype == v.dtype and u.shape == v.shape and u.tobytes() == v.tobytes()
+
+
+def test_host_half_delivers_the_same_bytes_by_threads_shared_memory_and_pickled_images(tmp_path, monkeypatch):
+    """Feeder._host_batches needs no device.  Worker threads that fill their slots of a batch buffer, worker processes that
+    fill a batch buffer in /dev/shm and worker processes that hand back pickled 8-bit images deliver the same batches (the
+    last one ragged), byte for byte, and every batch buffer taken is handed back once."""
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    from yolov3_tensorflow_amd import feeder, feed_native
+
+    class Arrays(_Ledger, feeder._Buffers):
+        pass
+
+    class Shared(_Ledger, feeder._SharedBuffers):
+        pass
+
+    lines = _flat_set(tmp_path)
+    threads = _host_half(lines, 'thread', Arrays(), None)
+    assert [len(b[0]) for b in threads] == [3, 2] and threads[0][1].dtype == np.float32 and threads[0][1].max() > 0.5
+    pickled = _host_half(lines, 'process', Arrays(), _NoSharedMemory())
+    _same_batches(threads, pickled)
+    if os.path.isdir('/dev/shm'):
+        shared, spare = Shared(), Arrays()
+        try:
+            _same_batches(threads, _host_half(lines, 'process', spare, shared))
+            assert len(shared.lent) == 2 and not spare.lent           # (both batches went through /dev/shm)
+        finally:
+            shared.close()
+    # the numpy / Pillow pixel path, where processes are the default backend: workers started with Y3_FEED_NATIVE=0
+    monkeypatch.setenv('Y3_FEED_NATIVE', '0')
+    pool = ProcessPoolExecutor(3, mp_context=multiprocessing.get_context('spawn'))
+    monkeypatch.setattr(feeder, '_shared_process_pool', lambda workers: pool)
+    try:
+        assert pool.submit(feed_native.enabled).result(timeout=120) is False
+        runs = [_host_half(lines, 'process', Arrays(), _NoSharedMemory()) for _ in range(2)]
+    finally:
+        pool.shutdown(wait=False, cancel_futures=True)
+    _same_batches(runs[0], runs[1])
+    assert [len(b[0]) for b in runs[0]] == [3, 2]
+
+
+def test_host_half_ends_on_stop_and_lets_its_buffers_go(tmp_path):
+    """`stop` set after the first batch: the second, whose jobs are in flight (prefetch=2), is not collected, and its batch
+    buffer goes back to its pool all the same."""
+    from yolov3_tensorflow_amd import feeder
+
+    class Arrays(_Ledger, feeder._Buffers):
+        pass
+
+    buffers = Arrays()
+    got = _host_half(_flat_set(tmp_path), 'thread', buffers, None, stop_after=1)
+    assert len(got) == 1 and len(got[0][0]) == 3
+    assert len(buffers.lent) == 2 and len(buffers.busy) == 1         # one handed back for reuse, the other one dropped

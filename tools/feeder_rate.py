@@ -42,6 +42,35 @@ def write_set(folder, n, seed=0):
     return lines
 
 
+def timed_batches(it, batches, sync=lambda: None, meet=lambda: None):
+    """Three batches of warm-up (pool start-up, pinned buffers), then `batches` on the clock: (start, end, CPU seconds)."""
+    for _ in range(3):
+        next(it)
+    sync()
+    meet()
+    t0, c0 = time.time(), time.process_time()
+    for _ in range(batches):
+        next(it)
+    sync()
+    return t0, time.time(), time.process_time() - c0
+
+
+def host_half(f):
+    """The feeder's host half alone (decode, augmentation chain, resize into a float32 batch buffer, collate): nothing is
+    uploaded or launched, so eight of these on a one-GPU box measure the HOST of an eight-GPU node (with uploads, eight
+    processes time-slice the one device here and the figure is the slicing, not the host)."""
+    import threading
+    from yolov3_tensorflow_amd import feeder as fd
+    shared = fd._SharedBuffers()
+    try:
+        for batch in f._host_batches(0, f._delivery(fd._Buffers(), shared), threading.Event()):
+            if batch[-1] is not None:       # recycled at once, as the feeder's buffers are after their upload
+                batch[-1][0].give(None, batch[-1][1])
+            yield batch
+    finally:
+        shared.close()
+
+
 def _one_feeder(rank, nfeed, lines, args, backend, workers, barrier, out):
     """One rank's feeder in its own process: warm up, meet the others, serve `batches` batches, report the window."""
     import torch
@@ -49,53 +78,9 @@ def _one_feeder(rank, nfeed, lines, args, backend, workers, barrier, out):
     try:
         f = Feeder(lines, args.batch_size, 80, [416, 416], ANCHORS, mode='train', use_mix_up=True, num_threads=workers,
                    prefetch=5, seed=1 + rank, backend=backend, pixels=args.pixels.split(',')[0])
-        if args.host_only:
-            # the host half alone (decode, augmentation chain, resize into a float32 batch buffer, collate): no device call at
-            # all, so eight of these on a one-GPU box measure the HOST of an eight-GPU node (with uploads, eight processes
-            # time-slice the one device here and the figure is the slicing, not the host)
-            from yolov3_tensorflow_amd import feeder as fd
-            from yolov3_tensorflow_amd.utils.data_utils import collate
-            pool, plan = f._executor(), f._plan(0)
-
-            free = []           # batch buffers are recycled, as the feeder's pinned buffers are (no page faults per batch)
-
-            def submit(entry):
-                b, size, mine = entry
-                shape = (len(mine), size[1], size[0], 3)
-                slots = free.pop() if free and free[-1].shape == shape else np.empty(shape, np.float32)
-                return slots, [pool.submit(fd._worker_sample, f._job(0, b, j, line, size), slots[j]) for j, line in enumerate(mine)]
-
-            def finish(item):
-                slots, futs = item
-                samples = [x.result() for x in futs]
-                collate([(s_[0], slots[j] if s_[1] is None else s_[1], s_[2], s_[3]) for j, s_ in enumerate(samples)], out_images=slots)
-                free.append(slots)
-            pending = [submit(e) for e in plan[:5]]
-            nxt = 5
-            for _ in range(3):
-                finish(pending.pop(0))
-                pending.append(submit(plan[nxt])); nxt += 1
-            barrier.wait(timeout=180)
-            t0 = time.time()
-            for _ in range(args.batches):
-                finish(pending.pop(0))
-                if nxt < len(plan):
-                    pending.append(submit(plan[nxt])); nxt += 1
-            t1 = time.time()
-            out.put((rank, t0, t1, None))
-            f.close()
-            return
-        it = f.epoch(0)
-        for _ in range(3):
-            next(it)
-        torch.cuda.synchronize()
-        barrier.wait(timeout=180)
-        t0, c0 = time.time(), time.process_time()
-        for _ in range(args.batches):
-            next(it)
-        torch.cuda.synchronize()
-        t1, c1 = time.time(), time.process_time()
-        out.put((rank, t0, t1, None, c1 - c0))
+        it, sync = (host_half(f), lambda: None) if args.host_only else (f.epoch(0), torch.cuda.synchronize)
+        t0, t1, cpu = timed_batches(it, args.batches, sync, lambda: barrier.wait(timeout=180))
+        out.put((rank, t0, t1, None, cpu))
         it.close()
         f.close()
     except BaseException as e:      # noqa: BLE001 - reported by the parent; never leave the others at the barrier
@@ -217,14 +202,8 @@ def main():
                         f.close()
                         continue
                     it = f.epoch(0)
-                    for _ in range(3):              # pool start-up, pinned buffers
-                        next(it)
-                    torch.cuda.synchronize()
-                    t0, c0 = time.perf_counter(), time.process_time()
-                    for _ in range(args.batches):
-                        next(it)
-                    torch.cuda.synchronize()
-                    dt, cpu = time.perf_counter() - t0, time.process_time() - c0
+                    t0, t1, cpu = timed_batches(it, args.batches, torch.cuda.synchronize)
+                    dt = t1 - t0
                     it.close()
                     f.close()
                     images = args.batches * args.batch_size

@@ -9,23 +9,22 @@ rebuilt for one process per GPU with the device-resident target assignment of th
     (utils.data_utils.parse_sample).  The pixel work - blend, colour jitter, crop, resize, pad, flip, /255 - and the crop
     search run in liby3feed.so (include/yolo355_feed.h: native code where the reference's is OpenCV), which releases the
     GIL, as PIL's JPEG decoder does; a worker holds the GIL for a little under a millisecond per image (which levels one
-    process off at 1,000-1,200 images/s: profiles/r03_feeder_rate.txt).  So the workers are
-    THREADS by default (backend='thread') and each writes its float32 image straight into its slot of the batch's pinned
-    host buffer: no pickling, no second pass.  backend='process' is the arrangement that scales past one interpreter's
-    GIL: worker processes from a `forkserver` (one pool per process and worker count, shared by the training and the
-    validation feeder) write their float32 slots into batch buffers that live in /dev/shm and that the parent has
-    page-locked for the device (hipHostRegister), so only boxes and labels travel through the pipes: 3,320 images/s with
-    32 workers; it is also the default for the numpy / Pillow pixel path (Y3_FEED_NATIVE=0), which holds the GIL most of the
-    time.  (Without /dev/shm the workers hand back 8-bit images that the coordinator divides into a pinned buffer: the
-    round-2 arrangement.)  Why a forkserver: forking the
-    training process itself copies every PINNED host page eagerly - measured 93 s for four workers once 8 GB were pinned,
-    against 0.4 s in a fresh process (tools/feeder_diag.py) - and the feeder is what pins them.  (As with any
-    multiprocessing start method but fork, a SCRIPT that builds a process-backed Feeder needs the usual
-    `if __name__ == '__main__':` guard.)
-  * a coordinator thread keeps `prefetch` batches of jobs in flight, and copies each finished batch to the device on a
-    SIDE stream; a bounded queue of `prefetch` batches (reference: prefetech_buffer = 5) decouples it from the train step,
-    so decode / resize / H2D of batch i+1.. overlap the step on batch i.  The pinned buffers are recycled once their copy
-    has completed (pinning 130 MB per batch afresh costs more than filling it);
+    process off at 1,000-1,200 images/s: profiles/r03_feeder_rate.txt).  So the workers are THREADS by default
+    (backend='thread'); backend='process' scales past one interpreter's GIL (3,320 images/s with 32 workers) and is the
+    default for the numpy / Pillow pixel path (Y3_FEED_NATIVE=0), which holds the GIL most of the time.  The processes come
+    from a `forkserver` (one pool per process and worker count, shared by the training and the validation feeder): forking
+    the training process itself copies every PINNED host page eagerly - measured 93 s for four workers once 8 GB were
+    pinned, against 0.4 s in a fresh process (tools/feeder_diag.py) - and the feeder is what pins them.  (As with any start
+    method but fork, a SCRIPT that builds a process-backed Feeder needs the usual `if __name__ == '__main__':` guard.)
+  * how a batch comes back from the workers is a DELIVERY, chosen once per epoch (Feeder._delivery) and told in its class:
+    _HostPixels (threads write float32 slots of a pinned batch buffer: no pickling, no second pass), _DeferredPixels
+    (pixels='gpu'), _SharedPixels (processes; without /dev/shm it falls back to _HostPixels' pickled 8-bit images);
+  * the host half, Feeder._host_batches, keeps `prefetch` batches of jobs in flight and yields them collated, oldest first.
+    It touches no device (tools/feeder_rate.py --host-only and the tests run it alone, over numpy buffers);
+  * the device half, Feeder.epoch: a coordinator thread copies each host batch to the device on a SIDE stream; a bounded
+    queue of `prefetch` batches (reference: prefetech_buffer = 5) decouples it from the train step, so decode / resize /
+    H2D of batch i+1.. overlap the step on batch i.  The pinned buffers are recycled once their copy has completed
+    (_Buffers: pinning 130 MB per batch afresh costs more than filling it);
   * pixels='gpu': the workers only decode and draw (parse_sample(defer=True)); the coordinator plans the batch's pixel
     work (liby3feed.so: y3f_plan_batch, native threads), uploads ONE blob of 8-bit sources and tables and runs y3_feed_run
     on the side stream (feed_device.DevicePixels) - the same bytes as the host path, 5 of the 5.9 ms a core spends per
@@ -48,6 +47,7 @@ import random
 import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
+from itertools import islice
 
 import numpy as np
 
@@ -78,15 +78,53 @@ def _worker_sample_shared(job, path, shape, index):
     return idx, None, boxes, labels
 
 
-class _SharedBuffers(object):
+class _Buffers(object):
+    """Batch buffers by shape, handed out again once the H2D copy that read them has completed.  A subclass says what a
+    buffer is (`_make`, `_shape`) and how it goes (`_drop`); as it stands: plain numpy arrays, for a host half run alone."""
+
+    def __init__(self):
+        self.busy = []          # (event, buffer)
+
+    def take(self, shape):
+        shape = tuple(int(v) for v in shape)
+        free = [i for i, (ev, _) in enumerate(self.busy) if ev is None or ev.query()]
+        for i in free:
+            if self._shape(self.busy[i][1]) == shape:
+                return self.busy.pop(i)[1]
+        # none of this shape is free.  Multi-scale training moves from size to size: keep a handful of free buffers of
+        # other shapes (the size may come back), let go of the rest
+        for i in reversed(free[:-4]):
+            self._drop(self.busy.pop(i)[1])
+        return self._make(shape)
+
+    def give(self, event, buf):
+        self.busy.append((event, buf))      # free again once `event` has completed (None: nothing reads it any more)
+
+    def _make(self, shape):
+        return np.empty(shape, np.float32)
+
+    def _shape(self, buf):
+        return tuple(buf.shape)
+
+    def _drop(self, buf):
+        pass
+
+
+class _PinnedBuffers(_Buffers):       # (tensors)
+    def _make(self, shape):
+        import torch
+        return torch.empty(shape, dtype=torch.float32).pin_memory()
+
+
+class _SharedBuffers(_Buffers):
     """Batch buffers for worker processes: files in /dev/shm mapped here and in the workers, page-locked for the device
-    (hipHostRegister) so that the upload reads them like any pinned buffer; recycled like _PinnedBuffers.  Where shared memory
-    or the registration is not available, `take` returns None and the feeder falls back to pickled 8-bit images."""
+    (hipHostRegister) so that the upload reads them like any pinned buffer.  Where shared memory or the registration is not
+    available, `take` returns None and the feeder falls back to pickled 8-bit images."""
 
     _live = []              # instances with files in /dev/shm: closed at interpreter exit at the latest
 
     def __init__(self):
-        self.busy = []          # (event, entry)
+        _Buffers.__init__(self)
         self.entries = []       # every live entry: dict(path, map, array, tensor, registered)
         self.broken = False
         if not _SharedBuffers._live:
@@ -99,7 +137,7 @@ class _SharedBuffers(object):
         for inst in list(_SharedBuffers._live):
             inst.close()
 
-    def _create(self, shape):
+    def _make(self, shape):
         import mmap
         import os
         import tempfile
@@ -135,30 +173,23 @@ class _SharedBuffers(object):
         self.entries.append(entry)
         return entry
 
+    def _shape(self, entry):
+        return tuple(entry['array'].shape)
+
     def take(self, shape):
         if self.broken:
             return None
-        shape = tuple(int(v) for v in shape)
-        free = [i for i, (ev, _) in enumerate(self.busy) if ev.query()]
-        for i in free:
-            if tuple(self.busy[i][1]['array'].shape) == shape:
-                return self.busy.pop(i)[1]
-        for i in reversed(free[:-4]):
-            self._release(self.busy.pop(i)[1])
         try:
-            entry = self._create(shape)
+            entry = _Buffers.take(self, shape)
         except (OSError, ValueError):
             self.broken = True
             return None
         if self.broken:                 # (the mapping could not be page-locked)
-            self._release(entry)
+            self._drop(entry)
             return None
         return entry
 
-    def give(self, event, entry):
-        self.busy.append((event, entry))
-
-    def _release(self, entry):
+    def _drop(self, entry):
         import os
         import torch
         if entry in self.entries:
@@ -181,32 +212,9 @@ class _SharedBuffers(object):
     def close(self):
         self.busy = []
         for entry in list(self.entries):
-            self._release(entry)
+            self._drop(entry)
         if self in _SharedBuffers._live:
             _SharedBuffers._live.remove(self)
-
-
-class _PinnedBuffers(object):
-    """Pinned host batch buffers by shape, handed out again once the H2D copy that read them has completed."""
-
-    def __init__(self):
-        self.busy = []          # (event, tensor)
-
-    def take(self, shape):
-        import torch
-        shape = tuple(int(v) for v in shape)
-        free = [i for i, (ev, _) in enumerate(self.busy) if ev.query()]
-        for i in free:
-            if tuple(self.busy[i][1].shape) == shape:
-                return self.busy.pop(i)[1]
-        # none of this shape is free.  Multi-scale training moves from size to size: keep a handful of free buffers of
-        # other shapes (the size may come back), unpin the rest
-        for i in reversed(free[:-4]):
-            del self.busy[i]
-        return torch.empty(shape, dtype=torch.float32).pin_memory()
-
-    def give(self, event, tensor):
-        self.busy.append((event, tensor))
 
 
 _POOLS = {}
@@ -233,6 +241,63 @@ def _shutdown_pools():
         for pool in _POOLS.values():
             pool.shutdown(wait=False, cancel_futures=True)
         _POOLS.clear()
+
+
+class _DeferredPixels(object):
+    """Delivery with pixels='gpu': worker threads decode and draw; the batch comes back as pixel JOBS for the device.
+    Every delivery has two steps.  `submit(pool, jobs, shape)` takes the batch buffer it needs, submits the worker calls and
+    returns `pending` = (futures, owner, buffer); `collect(pending)` waits for them and returns the collated host batch:
+    (ids, images or pixel jobs, boxes, labels, counts, owner).  owner = (pool of buffers, buffer) to hand back, or None."""
+
+    def __init__(self, cached):
+        self.cached = cached        # path -> (h, w) of a source the feeder's cache holds, or None
+
+    def submit(self, pool, jobs, shape):
+        return [pool.submit(_worker_sample, job, None, True, self.cached) for job in jobs], None, None
+
+    def collect(self, pending):
+        from .utils.data_utils import collate
+        samples = [f.result() for f in pending[0]]
+        ids, _, boxes, labels, counts = collate(samples, with_images=False)
+        return ids, [s[1] for s in samples], boxes, labels, counts, None
+
+
+class _HostPixels(object):
+    """Delivery of float32 images in a batch buffer of `buffers`: worker threads write their slots of it (in_place), or
+    worker processes hand back 8-bit images (a quarter of the bytes to pickle) that `collect` divides into it."""
+
+    def __init__(self, buffers, in_place):
+        self.buffers, self.in_place = buffers, in_place
+
+    def submit(self, pool, jobs, shape):
+        buf = self.buffers.take(shape)
+        slots = np.asarray(buf) if self.in_place else [None] * len(jobs)
+        return [pool.submit(_worker_sample, job, slots[j]) for j, job in enumerate(jobs)], (self.buffers, buf), buf
+
+    def collect(self, pending):
+        from .utils.data_utils import collate
+        futs, owner, buf = pending
+        slots = np.asarray(buf)         # (a view of the tensor's memory)
+        samples = [f.result() for f in futs]
+        samples = [(s[0], slots[j] if s[1] is None else s[1], s[2], s[3]) for j, s in enumerate(samples)]
+        ids, _, boxes, labels, counts = collate(samples, out_images=slots)
+        return ids, buf, boxes, labels, counts, owner
+
+
+class _SharedPixels(_HostPixels):
+    """Delivery by worker processes that fill a shared, page-locked batch buffer of `shared`; a batch for which there is
+    none (no /dev/shm, no registration: then for every later batch too) travels as pickled 8-bit images."""
+
+    def __init__(self, shared, buffers):
+        _HostPixels.__init__(self, buffers, False)
+        self.shared = shared
+
+    def submit(self, pool, jobs, shape):
+        entry = self.shared.take(shape)
+        if entry is None:
+            return _HostPixels.submit(self, pool, jobs, shape)
+        futs = [pool.submit(_worker_sample_shared, job, entry['path'], shape, j) for j, job in enumerate(jobs)]
+        return futs, (self.shared, entry), entry['tensor']
 
 
 class Batch(object):
@@ -332,13 +397,42 @@ class Feeder(object):
         key = ((self.seed * 1000003 + epoch) * 100003 + b) * 1009 + j * self.world + self.rank
         return (line, size, self.mode, self.letterbox, key)
 
+    def _delivery(self, buffers, shared, cached=None):
+        """How this feeder's batches come from the workers (module docstring), over the given pools of batch buffers."""
+        if self.pixels == 'gpu':
+            return _DeferredPixels(cached)
+        if self.backend == 'thread':
+            return _HostPixels(buffers, True)
+        return _SharedPixels(shared, buffers)
+
+    def _host_batches(self, epoch, delivery, stop):
+        """The host half of an epoch, which needs no device: keeps up to `prefetch` batches of worker jobs in flight and
+        yields (img_size,) + delivery.collect(oldest) until the plan is served or `stop` is set.  The consumer hands each
+        batch's buffer back (owner[0].give); the buffers of batches never collected are let go here."""
+        pool = self._executor()
+        pending = []
+        plan = iter(self._plan(epoch))
+        try:
+            while not stop.is_set():
+                for b, size, lines in islice(plan, self.prefetch - len(pending)):
+                    jobs = [self._job(epoch, b, j, line, size) for j, line in enumerate(lines)]
+                    pending.append((size, delivery.submit(pool, jobs, (len(lines), size[1], size[0], 3))))
+                if not pending:
+                    break
+                size, oldest = pending.pop(0)
+                yield (size,) + delivery.collect(oldest)
+        finally:
+            for _, (_, owner, _) in pending:        # (workers may still be writing: dropped, never handed out again)
+                if owner is not None:
+                    owner[0]._drop(owner[1])
+
     def epoch(self, epoch=0):
-        """Iterate over one epoch: yields Batch objects whose tensors live on the device."""
+        """Iterate over one epoch: yields Batch objects whose tensors live on the device.  The device half: a coordinator
+        thread uploads what _host_batches delivers on a side stream, the consumer assigns the targets."""
         import torch
         from . import framework as fw
-        from .utils.data_utils import collate, process_box_batch
+        from .utils.data_utils import process_box_batch
         dev = torch.device(self.device) if self.device is not None else fw.default_device()
-        plan = self._plan(epoch)
         q = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
         # one side stream (and, with pixels='gpu', one set of device tables + pinned blob buffers) per feeder and device, kept
@@ -346,8 +440,6 @@ class Feeder(object):
         if self._side is None or self._side[0] != dev:
             self._side = (dev, torch.cuda.Stream(device=dev), None)
         copy_stream = self._side[1]
-
-        pool = self._executor()
 
         on_device = self.pixels == 'gpu'
         device_pixels = None
@@ -360,10 +452,8 @@ class Feeder(object):
                 from .feed_cache import SourceCache
                 self.cache = SourceCache(dev, self.cache_bytes)
         cache = self.cache if on_device and self.cache_bytes > 0 else None
-        cached = cache.shape_of if cache is not None else None
-        in_place = self.backend == 'thread'
-        buffers = _PinnedBuffers()
-        shared = None if in_place else _SharedBuffers()
+        shared = _SharedBuffers()       # (no file in /dev/shm before a worker process needs one)
+        delivery = self._delivery(_PinnedBuffers(), shared, cache.shape_of if cache is not None else None)
 
         def put(item):
             # every hand-over gives up as soon as the consumer has stopped: a blocking put on a full queue that nobody
@@ -377,51 +467,12 @@ class Feeder(object):
 
         def produce():
             try:
-                # keep up to `prefetch` batches of decode jobs in flight
-                pending = []
-                it = iter(plan)
-                exhausted = False
-                while not stop.is_set():
-                    while not exhausted and len(pending) < self.prefetch:
-                        try:
-                            b, size, lines = next(it)
-                        except StopIteration:
-                            exhausted = True
-                            break
-                        shape = (len(lines), size[1], size[0], 3)
-                        jobs = [self._job(epoch, b, j, line, size) for j, line in enumerate(lines)]
-                        entry = shared.take(shape) if shared is not None else None
-                        if on_device:               # worker threads decode and draw; the pixels are left to the device
-                            pinned, owner = None, None
-                            futs = [pool.submit(_worker_sample, job, None, True, cached) for job in jobs]
-                        elif entry is not None:     # worker processes fill the shared, page-locked batch buffer
-                            pinned, owner = entry['tensor'], (shared, entry)
-                            futs = [pool.submit(_worker_sample_shared, job, entry['path'], shape, j)
-                                    for j, job in enumerate(jobs)]
-                        else:
-                            pinned = buffers.take(shape)
-                            owner = (buffers, pinned)
-                            slots = pinned.numpy()
-                            if in_place:            # worker threads fill the pinned batch buffer
-                                futs = [pool.submit(_worker_sample, job, slots[j]) for j, job in enumerate(jobs)]
-                            else:                   # worker processes hand back 8-bit images
-                                futs = [pool.submit(_worker_sample, job) for job in jobs]
-                        pending.append((b, size, futs, pinned, owner))
-                    if not pending:
-                        break
-                    b, size, futs, pinned, owner = pending.pop(0)
-                    samples = [f.result() for f in futs]
-                    if on_device:
-                        ids, _, boxes, labels, counts = collate(samples, with_images=False)
-                    else:
-                        slots = pinned.numpy()
-                        samples = [(s[0], slots[j] if s[1] is None else s[1], s[2], s[3]) for j, s in enumerate(samples)]
-                        ids, _, boxes, labels, counts = collate(samples, out_images=slots)
+                for size, ids, images, boxes, labels, counts, owner in self._host_batches(epoch, delivery, stop):
                     with torch.cuda.stream(copy_stream):
                         if on_device:
-                            images = device_pixels.run([s[1] for s in samples], threads=min(self.num_threads, 8), cache=cache)
+                            images = device_pixels.run(images, threads=min(self.num_threads, 8), cache=cache)
                         else:
-                            images = pinned.to(dev, non_blocking=True)
+                            images = images.to(dev, non_blocking=True)
                         bx = torch.from_numpy(boxes).pin_memory().to(dev, non_blocking=True)
                         lb = torch.from_numpy(labels.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
                         ct = torch.from_numpy(counts.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
@@ -429,8 +480,7 @@ class Feeder(object):
                         ev.record(copy_stream)
                     if owner is not None:
                         owner[0].give(ev, owner[1])
-                    item = (ids, size, images, bx, lb, ct, ev)
-                    put(item)
+                    put((ids, size, images, bx, lb, ct, ev))
                 put(None)
             except BaseException as e:       # noqa: BLE001 - handed to the consumer
                 put(e)
@@ -468,8 +518,7 @@ class Feeder(object):
                 except queue.Empty:
                     break
             copy_stream.synchronize()
-            if shared is not None:
-                shared.close()
+            shared.close()
 
     def __iter__(self):
         return self.epoch(0)
