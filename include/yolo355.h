@@ -388,6 +388,31 @@ int y3_conv2d_dgrad_bn(y3_ctx* ctx, const y3_conv_desc* fwd, const float* dz, in
 int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float* dy, const float* gamma, const float* scale,
                              const float* shift, const float* mean, const float* inv_std, long long rows, int c,
                              const float* partial, int nblocks, float* dgamma, float* dbeta, float* dz, float* scratch);
+/* Synchronised batch norm: the two finalizes above cut in two, with a caller-owned device buffer between the halves,
+ *   sums = double[2*c + 1]: [0:c) and [c:2c) the two column sums over this rank's rows, [2c] the row count,
+ * so that ONE sum of the buffer over ranks (between the halves, on the context's stream) yields the sums and the count of the
+ * global batch.  With the buffer left alone, sums-then-finish writes bit for bit what the one-call entries write.
+ *   stats_sums    (sum z, sum z^2): of partial [nblocks][2][c] where the conv epilogue took them (y3_bn_train_stats_partials'
+ *                 argument; z and scratch unused), else, partial NULL, of z [rows][c] (fp32, or bf16 when z_bf16; c %% 4 == 0)
+ *                 through scratch (y3_reduce_scratch_bytes(c)).
+ *   stats_finish  y3_bn_train_stats from the sums on: mean, inv_std, scale, shift, and the moving statistics, the unbiased
+ *                 factor count / (count - 1) taken of the count in the buffer (the global one after an exchange).
+ *   bwd_sums      (sum g', sum g' * zhat) as y3_bn_train_bwd / _partials reduce them (partial NULL / given), written to the buffer,
+ *                 and dgamma / dbeta (either may be NULL) from THIS rank's sums: each rank's loss is a mean over its own images
+ *                 and the gradient exchange averages over ranks, so the parameter gradients stay local (their average is the
+ *                 gradient of the global mean loss); all-reduced sums there would come out world times too large.
+ *   bwd_finish    the coefficients from the (exchanged) buffer, then the unchanged apply pass: dz (may alias dy; bf16 when z_bf16).
+ *                 scratch: the same y3_bn_bwd_scratch_bytes(c) buffer bwd_sums was given. */
+int y3_bn_sync_stats_sums(y3_ctx* ctx, const void* z, int z_bf16, const float* partial, int nblocks, long long rows, int c,
+                          double* sums, float* scratch);
+int y3_bn_sync_stats_finish(y3_ctx* ctx, const double* sums, int c, const float* gamma, const float* beta, float eps, float decay,
+                            float* mean, float* inv_std, float* scale, float* shift, float* moving_mean, float* moving_var);
+int y3_bn_sync_bwd_sums(y3_ctx* ctx, const void* z, int z_bf16, const float* dy, const float* scale, const float* shift,
+                        const float* mean, const float* inv_std, long long rows, int c, const float* partial, int nblocks,
+                        float* dgamma, float* dbeta, double* sums, float* scratch);
+int y3_bn_sync_bwd_finish(y3_ctx* ctx, const void* z, int z_bf16, const float* dy, const float* gamma, const float* scale,
+                          const float* shift, const float* mean, const float* inv_std, long long rows, int c, const double* sums,
+                          void* dz, float* scratch);
 /* Which schedule a launch of the exact-fp32 conv family takes (host arithmetic, no device): 0 = one workgroup per tile,
  * 1 = stream-K (3x3 convs on 128x128 tiles, needs the workspace), 2 = the resident walk of the 64x64 tiles (1,024 workgroups
  * walking runs of whole tiles).  `conv` is the conv as launched: for a data gradient [n,h,w,dz_stride] -> fwd cin at stride
@@ -540,6 +565,19 @@ int y3_net_train_step(y3_net* net, const y3_train_var* vars, const float* x, int
  * than on one stream). */
 #define Y3_OWN_STREAM ((void*)(size_t)1)
 int y3_net_train_set_wgrad_stream(y3_net* net, void* stream);
+/* Optional synchronised batch norm for a data-parallel caller (off by default; a NULL fn switches it off again).  With a hook
+ * set, y3_net_train_forward / _backward / _step run every BN layer's finalize as its two halves (y3_bn_sync_*): the sums half
+ * is enqueued on the context's stream into exchange_dev, fn(user, layer, phase, doubles) is called on the host thread (phase 0
+ * forward, 1 backward; doubles = 2 * cout + 1), then the finish half is enqueued.  On return from fn, work enqueued LATER on
+ * the context's stream must see exchange_dev[0:doubles) summed over ranks (the `ready` hook's contract: order the collective
+ * behind the stream, and the stream behind the collective).  One buffer serves every layer - all of it is ordered on that
+ * stream; it is the caller's, of at least (2 * 1024 + 1) * 8 bytes (else Y3_EINVAL).  fn is not called while the workspace is
+ * sized, nor, in backward, for layers below the first trainable one; the calls come in layer order in forward and in reverse
+ * in backward - the same sequence on every rank that runs the same variable table and input size.  A nonzero return ends the
+ * call with Y3_ESTATE.  The weight gradients (and their second stream) are untouched; parameter gradients stay per rank (to be
+ * averaged by the caller), dz and the statistics - the moving ones included - are those of the global batch. */
+typedef int (*y3_bn_sync_fn)(void* user, int layer, int phase, int doubles);
+int y3_net_train_set_bn_sync(y3_net* net, y3_bn_sync_fn fn, void* user, double* exchange_dev, size_t exchange_bytes);
 /* test hook: byte offsets inside the last forward's workspace of layer i's raw conv output z and of its [4][cout]
  * mean / inv_std / folded scale / folded shift (the tensors that fix the LeakyReLU branches); SIZE_MAX for non-BN layers */
 int y3_net_train_saved(const y3_net* net, int layer, size_t* z_offset, size_t* stats_offset);

@@ -2,6 +2,11 @@
 """Throughput of one training step (BASELINE configs[3]: 416x416, bs=64 per GPU, SGD) on synthetic batches.
 
     python tools/train_bench.py [--batch 64] [--steps 5] [--optimizer sgd] [--head-only]
+
+--sync_bn measures what synchronised batch norm (training.Trainer(sync_bn=True)) costs on ONE GPU: a one-rank `nccl` group
+with the 144 collectives per step forced (as tests/test_rccl_gpu.py forces the gradient buckets), rounds of --steps steps
+alternating with and without the hook in one job, written to profiles/sync_bn_rate.txt.  It says nothing about the cost
+with more than one RCCL rank, where each collective also crosses xGMI and waits for the slowest rank.
 """
 import argparse
 import os
@@ -34,6 +39,49 @@ def synthetic_y_true(n, size, class_num, anchors, seed, device):
     return out
 
 
+def sync_bn_ab(a, model, upd, x, yt):
+    """Rounds of a.steps steps, alternately without and with the batch-norm exchange hook (one Trainer, one workspace)."""
+    import tempfile
+    import torch
+    import torch.distributed as dist
+    from yolov3_tensorflow_amd import training
+    from yolov3_tensorflow_amd.utils.misc_utils import config_optimizer
+    os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
+    dist.init_process_group('nccl', init_method='file://' + os.path.join(tempfile.mkdtemp(), 'init'), rank=0, world_size=1)
+    # (the weight-gradient stream fixed on: the 'auto' calibration would spend its seven steps inside the first rounds)
+    trainer = training.Trainer(model, config_optimizer(a.optimizer, 1e-4), update_vars=upd, process_group=dist.group.WORLD,
+                               wgrad_stream=True, sync_bn=True)
+    ms = {False: [], True: []}
+    for on in (False, True):      # warm both arms (RCCL sets its communicator up in the first collective)
+        trainer.bn_sync.force = on
+        for _ in range(2):
+            trainer.step(x, yt)
+    for _ in range(a.rounds):
+        for on in (False, True):
+            trainer.bn_sync.force = on
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                trainer.step(x, yt)
+            torch.cuda.synchronize()
+            ms[on].append((time.perf_counter() - t0) / a.steps * 1e3)
+    calls = len(trainer.bn_sync.calls)
+    dist.destroy_process_group()
+    med = lambda v: sorted(v)[len(v) // 2]
+    lines = ['# synchronised batch norm on ONE GPU: a one-rank nccl group, the collectives forced (tools/train_bench.py --sync_bn)',
+             '# train step [%s] batch %d @%d, %s%s, wgrad_stream on; %d rounds x %d steps per arm, alternating in one job'
+             % (a.precision, a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', a.rounds, a.steps),
+             '# hook calls per step: %d' % calls,
+             'without ms/step: %s  median %.2f' % (' '.join('%.2f' % v for v in ms[False]), med(ms[False])),
+             'with    ms/step: %s  median %.2f' % (' '.join('%.2f' % v for v in ms[True]), med(ms[True])),
+             'difference of the medians: %+.2f ms/step (%+.2f%%)' % (med(ms[True]) - med(ms[False]),
+                                                                   100 * (med(ms[True]) / med(ms[False]) - 1)),
+             '# one rank: no xGMI traffic and no waiting for a slower rank - not the cost at world > 1']
+    print('\n'.join(lines))
+    with open(a.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
@@ -43,6 +91,9 @@ def main():
     ap.add_argument('--head-only', action='store_true')
     ap.add_argument('--precision', default='f32', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'],
                     help='the train mode (training._TRAIN_DTYPES): bf16 = mixed precision on the bf16 matrix pipe')
+    ap.add_argument('--sync_bn', action='store_true', help='A/B of synchronised batch norm over a one-rank nccl group')
+    ap.add_argument('--rounds', type=int, default=4, help='--sync_bn: rounds per arm')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sync_bn_rate.txt'))
     a = ap.parse_args()
     import torch
     import yolov3_tensorflow_amd as y3
@@ -59,6 +110,8 @@ def main():
         upd = None
         if a.head_only:
             upd = [v for v in y3.global_variables(scope='yolov3') if v.op_name.startswith('yolov3/yolov3_head')]
+        if a.sync_bn:
+            return sync_bn_ab(a, model, upd, x, yt)
         trainer = training.Trainer(model, config_optimizer(a.optimizer, 1e-4), update_vars=upd)
         for _ in range(2):
             loss = trainer.step(x, yt)

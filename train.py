@@ -115,6 +115,11 @@ def build_parser():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compute_dtype', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'], default='f32',
                    help='train-step mode: fp32-accurate modes, or bf16 = mixed precision on the bf16 matrix pipe')
+    p.add_argument('--sync_bn', type=_bool, default=False,
+                   help='data-parallel runs: synchronised batch norm - every BN layer normalises with the statistics of the '
+                        'global batch and all ranks keep the same moving statistics (training.Trainer(sync_bn=True)).  Cost: '
+                        'two small collectives per BN layer per step, 144 in total; all ranks need the same --batch_size, '
+                        '--update_part and image size')
     return p
 
 
@@ -262,7 +267,7 @@ def main(argv=None):
         if resumed_step is not None and args.global_step == 0:
             args.global_step = int(resumed_step)
     trainer = training.Trainer(yolo_model, optimizer, update_vars=update_vars, global_step=float(args.global_step),
-                               process_group=dist.group.WORLD if world > 1 else None)
+                               process_group=dist.group.WORLD if world > 1 else None, sync_bn=args.sync_bn)
     gpu_nms_op = functools.partial(gpu_nms, num_classes=args.class_num, max_boxes=args.nms_topk,
                                    score_thresh=args.score_threshold, nms_thresh=args.nms_threshold)
     if rank == 0:

@@ -34,6 +34,7 @@ class TrainOpts(ctypes.Structure):      # y3_train_opts
 
 
 GradReadyFn = ctypes.CFUNCTYPE(None, c_void_p, c_longlong)      # y3_grad_ready_fn
+BnSyncFn = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_int, c_int)      # y3_bn_sync_fn
 
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header.
@@ -92,6 +93,7 @@ PROTOTYPES = {
     "y3_net_train_step": (c_int, [c_void_p, POINTER(TrainVar), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   POINTER(TrainOpts), c_void_p, c_void_p, c_size_t, c_void_p, GradReadyFn, c_void_p]),
     "y3_net_train_set_wgrad_stream": (c_int, [c_void_p, c_void_p]),
+    "y3_net_train_set_bn_sync": (c_int, [c_void_p, BnSyncFn, c_void_p, c_void_p, c_size_t]),
     "y3_net_train_saved": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "y3_net_train_saved_type": (c_int, [c_void_p, c_int]),
     "y3_pack_conv_weights_bf16_train": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -151,6 +153,13 @@ PROTOTYPES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "y3_bn_train_bwd_partials": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_longlong, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y3_bn_sync_stats_sums": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p]),
+    "y3_bn_sync_stats_finish": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y3_bn_sync_bwd_sums": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong,
+                                    c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y3_bn_sync_bwd_finish": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
     "y3_conv_schedule": (c_int, [POINTER(ConvDesc), c_int, c_int]),
     "y3_pack_conv_weights_wino_dgrad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "y3_conv2d_dgrad_wino": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,

@@ -122,6 +122,10 @@ struct y3_net {
     y3_train_state* train = nullptr;
     void* wgrad_stream = nullptr;   // y3_net_train_set_wgrad_stream: the weight gradients of backward run on this stream (nullptr: on the context's)
     void* own_stream = nullptr;     // the low-priority stream y3_net_train_set_wgrad_stream(net, Y3_OWN_STREAM) created (destroyed with the net)
+    // y3_net_train_set_bn_sync: the host hook between the two halves of every BN finalize, and the caller's exchange buffer
+    y3_bn_sync_fn bn_sync_fn = nullptr;
+    void* bn_sync_user = nullptr;
+    double* bn_sync_buf = nullptr;
     NetDtype dtype = NetDtype::F32;
     std::vector<Tensor> tensors;
     std::vector<Layer> layers;

@@ -75,6 +75,15 @@ int det_pad_of(int class_num) { return ((3 * (5 + class_num) + 31) / 32) * 32; }
         }                               \
     } while (0)
 
+// synchronised batch norm (y3_net_train_set_bn_sync): the host hook between the two halves of a BN layer's finalize
+int bn_sync_call(const y3_net* net, int layer, int phase, int cout) {
+    if (net->bn_sync_fn(net->bn_sync_user, layer, phase, 2 * cout + 1) != 0) {
+        y3_set_error("y3_net_train: the batch-norm exchange hook failed (layer %d, %s)", layer, phase ? "backward" : "forward");
+        return Y3_ESTATE;
+    }
+    return Y3_OK;
+}
+
 // sizes the persistent scratch and runs (or, dry, only sizes) the training forward
 int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, int h, int w, const y3_train_opts* o,
                  void* ws, size_t ws_bytes, bool dry) {
@@ -191,7 +200,13 @@ int forward_impl(y3_net* net, const y3_train_var* vars, const float* x, int n, i
         if (l.bn) {
             S.stats[i] = A.alloc((size_t)4 * cout * 4);
             float* st = A.p(S.stats[i]);
-            if (nblk)
+            if (net->bn_sync_fn) {      // the same statistics as sums | exchange | finish (the dry run launches and calls nothing)
+                Y3_TRY(y3_bn_sync_stats_sums(ctx, y, 0, nblk ? A.p(part) : nullptr, nblk, rows, cout, net->bn_sync_buf,
+                                             A.p(S.reduce_sc)));
+                Y3_TRY(bn_sync_call(net, (int)i, 0, cout));
+                Y3_TRY(y3_bn_sync_stats_finish(ctx, net->bn_sync_buf, cout, v.gamma, v.beta, BN_EPS, o->bn_decay, st, st + cout,
+                                               st + 2 * cout, st + 3 * cout, v.moving_mean, v.moving_variance));
+            } else if (nblk)
                 Y3_TRY(y3_bn_train_stats_partials(ctx, A.p(part), nblk, rows, cout, v.gamma, v.beta, BN_EPS, o->bn_decay, st,
                                                   st + cout, st + 2 * cout, st + 3 * cout, v.moving_mean, v.moving_variance));
             else
@@ -380,7 +395,15 @@ int backward_impl(y3_net* net, const y3_train_var* vars, float* flat_grad, y3_gr
             float* dbet = trainable(v.g_beta) ? gptr(v.g_beta) : A.p(tmp) + cout;
             const float* st = A.p(S.stats[i]);
             const float *sc = st + 2 * cout, *sh = st + 3 * cout, *mean = st, *istd = st + cout;
-            if (b16) {
+            if (net->bn_sync_fn) {      // sums (d gamma, d beta from this rank's) | exchange | coefficients and apply pass
+                const float* fp = fused_nb[i] > 0 ? A.p(fused_part[i]) : nullptr;
+                Y3_TRY(y3_bn_sync_bwd_sums(ctx, A.p(S.z[i]), b16, A.p(dy), sc, sh, mean, istd, rows, cout, fp, fused_nb[i], dgam, dbet,
+                                           net->bn_sync_buf, A.p(S.bnbwd_sc)));
+                if (fused_nb[i] > 0) A.release(fused_part[i]);
+                Y3_TRY(bn_sync_call(net, i, 1, cout));
+                Y3_TRY(y3_bn_sync_bwd_finish(ctx, A.p(S.z[i]), b16, A.p(dy), v.gamma, sc, sh, mean, istd, rows, cout, net->bn_sync_buf,
+                                             A.p(dz_buf), A.p(S.bnbwd_sc)));
+            } else if (b16) {
                 Y3_TRY(y3_bn_train_bwd_bf16(ctx, A.p(S.z[i]), A.p(dy), v.gamma, sc, sh, mean, istd, rows, cout, dgam, dbet, A.p(dz_buf),
                                             A.p(S.bnbwd_sc)));
             } else if (fused_nb[i] > 0) {
@@ -565,6 +588,17 @@ extern "C" int y3_net_train_set_wgrad_stream(y3_net* net, void* stream) {
         stream = net->own_stream;
     }
     net->wgrad_stream = stream;
+    return Y3_OK;
+}
+
+extern "C" int y3_net_train_set_bn_sync(y3_net* net, y3_bn_sync_fn fn, void* user, double* exchange_dev, size_t exchange_bytes) {
+    Y3_CHECK_ARG(net, "y3_net_train_set_bn_sync: null net");
+    if (fn)
+        Y3_CHECK_ARG(exchange_dev && exchange_bytes >= (size_t)(2 * MAXC + 1) * sizeof(double),
+                     "y3_net_train_set_bn_sync: the exchange buffer must hold %d doubles", 2 * MAXC + 1);
+    net->bn_sync_fn = fn;
+    net->bn_sync_user = fn ? user : nullptr;
+    net->bn_sync_buf = fn ? exchange_dev : nullptr;
     return Y3_OK;
 }
 

@@ -154,21 +154,12 @@ __device__ __forceinline__ void block_sum2_fixed(const float* __restrict__ parti
     r1 = sh[256];
 }
 
-// BN forward finalize: batch mean / biased variance, folded scale & shift for the apply pass, and the
-// moving-statistics update  moving <- moving*decay + batch*(1-decay)  with the UNBIASED variance going
-// into moving_variance (TF fused batch norm; SURVEY App. B.5).
-__global__ void __launch_bounds__(256) bn_stats_finalize_kernel(const float* __restrict__ partial, int nblocks, int C,
-                                                                double count, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, float eps, float decay,
-                                                                float* __restrict__ mean, float* __restrict__ inv_std,
-                                                                float* __restrict__ scale, float* __restrict__ shift,
-                                                                float* __restrict__ moving_mean,
-                                                                float* __restrict__ moving_var) {
-    __shared__ double sh[512];
-    const int c = blockIdx.x;   // one workgroup per channel
-    double s0, s1;
-    block_sum2_fixed(partial, nblocks, (size_t)2 * C, (size_t)c, (size_t)C + c, sh, s0, s1);
-    if (threadIdx.x != 0) return;
+// What both forward finalizes do with a channel's two column sums and the row count they were taken over (one thread).
+__device__ __forceinline__ void bn_stats_finish(int c, double s0, double s1, double count, const float* __restrict__ gamma,
+                                                const float* __restrict__ beta, float eps, float decay,
+                                                float* __restrict__ mean, float* __restrict__ inv_std,
+                                                float* __restrict__ scale, float* __restrict__ shift,
+                                                float* __restrict__ moving_mean, float* __restrict__ moving_var) {
     const double mu = s0 / count;
     double var = s1 / count - mu * mu;
     if (var < 0.0) var = 0.0;
@@ -184,6 +175,24 @@ __global__ void __launch_bounds__(256) bn_stats_finalize_kernel(const float* __r
         moving_mean[c] = moving_mean[c] * decay + muf * (1.f - decay);
         moving_var[c] = moving_var[c] * decay + unbiased * (1.f - decay);
     }
+}
+
+// BN forward finalize: batch mean / biased variance, folded scale & shift for the apply pass, and the
+// moving-statistics update  moving <- moving*decay + batch*(1-decay)  with the UNBIASED variance going
+// into moving_variance (TF fused batch norm; SURVEY App. B.5).
+__global__ void __launch_bounds__(256) bn_stats_finalize_kernel(const float* __restrict__ partial, int nblocks, int C,
+                                                                double count, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, float eps, float decay,
+                                                                float* __restrict__ mean, float* __restrict__ inv_std,
+                                                                float* __restrict__ scale, float* __restrict__ shift,
+                                                                float* __restrict__ moving_mean,
+                                                                float* __restrict__ moving_var) {
+    __shared__ double sh[512];
+    const int c = blockIdx.x;   // one workgroup per channel
+    double s0, s1;
+    block_sum2_fixed(partial, nblocks, (size_t)2 * C, (size_t)c, (size_t)C + c, sh, s0, s1);
+    if (threadIdx.x != 0) return;
+    bn_stats_finish(c, s0, s1, count, gamma, beta, eps, decay, mean, inv_std, scale, shift, moving_mean, moving_var);
 }
 
 // BN backward finalize: d beta, d gamma (the parameter gradients) and the coefficients of the apply pass.
@@ -204,6 +213,52 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __res
         coef[C + c] = (float)(s0 / count);
         coef[2 * C + c] = (float)(s1 / count);
     }
+}
+
+// ---- the two finalizes cut in two (synchronised batch norm) ---------------------------------------------------------------
+// Between "sum" and "divide" lies an exchange buffer  sums = double[2*C + 1]: [0:C) and [C:2C) the two column sums of this
+// rank's rows, [2C] their count - so ONE sum over ranks of the whole buffer gives the statistics of the global batch.
+// The sums half of either direction: the walk of the finalizes above.  Backward also writes d beta / d gamma here, from the
+// LOCAL sums: every rank's loss is the mean over its own images and the gradient exchange averages over ranks, so the
+// parameter gradients must stay this rank's share (their average is the global gradient), while dz needs the global means.
+__global__ void __launch_bounds__(256) bn_sums_kernel(const float* __restrict__ partial, int nblocks, int C, double count,
+                                                      double* __restrict__ sums, float* __restrict__ dbeta,
+                                                      float* __restrict__ dgamma) {
+    __shared__ double sh[512];
+    const int c = blockIdx.x;
+    double s0, s1;
+    block_sum2_fixed(partial, nblocks, (size_t)2 * C, (size_t)c, (size_t)C + c, sh, s0, s1);
+    if (threadIdx.x != 0) return;
+    if (dbeta) dbeta[c] = (float)s0;
+    if (dgamma) dgamma[c] = (float)s1;
+    sums[c] = s0;
+    sums[C + c] = s1;
+    if (c == 0) sums[2 * C] = count;
+}
+
+// forward finish: bn_stats_finalize_kernel from its `mu = s0 / count` line on, the count read from the buffer (one thread per channel)
+__global__ void __launch_bounds__(256) bn_stats_finish_kernel(const double* __restrict__ sums, int C,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              float eps, float decay, float* __restrict__ mean,
+                                                              float* __restrict__ inv_std, float* __restrict__ scale,
+                                                              float* __restrict__ shift, float* __restrict__ moving_mean,
+                                                              float* __restrict__ moving_var) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    bn_stats_finish(c, sums[c], sums[C + c], sums[2 * C], gamma, beta, eps, decay, mean, inv_std, scale, shift, moving_mean,
+                    moving_var);
+}
+
+// backward finish: the coefficients of the apply pass, as bn_bwd_finalize_kernel writes them
+__global__ void __launch_bounds__(256) bn_bwd_finish_kernel(const double* __restrict__ sums, int C,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ inv_std, float* __restrict__ coef) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const double count = sums[2 * C];
+    coef[c] = gamma[c] * inv_std[c];
+    coef[C + c] = (float)(sums[c] / count);
+    coef[2 * C + c] = (float)(sums[C + c] / count);
 }
 
 // y = leaky(z*scale + shift) (+ residual); the residual is stored as y is
@@ -855,6 +910,38 @@ extern "C" int y3_bn_train_stats_partials(y3_ctx* ctx, const float* partial, int
     return Y3_OK;
 }
 
+// The two halves of the forward statistics (include/yolo355.h, synchronised batch norm).  partial != NULL: the conv epilogue's
+// column sums; else z (fp32, or bf16 when z_bf16) is reduced into scratch first.
+extern "C" int y3_bn_sync_stats_sums(y3_ctx* ctx, const void* z, int z_bf16, const float* partial, int nblocks, long long rows,
+                                     int c, double* sums, float* scratch) {
+    Y3_CHECK_ARG(ctx && sums && (partial ? nblocks > 0 : (z && scratch)), "y3_bn_sync_stats_sums: null argument");
+    Y3_CHECK_ARG(rows > 0 && c > 0 && (partial || c % 4 == 0), "y3_bn_sync_stats_sums: bad shape rows=%lld c=%d", rows, c);
+    if (!partial) {
+        const int rc = z_bf16 ? reduce_launch<0, Bf16>(ctx, static_cast<const bf16_t*>(z), nullptr, nullptr, nullptr, nullptr,
+                                                       nullptr, rows, c, scratch, &nblocks)
+                              : reduce_launch<0, F32>(ctx, static_cast<const float*>(z), nullptr, nullptr, nullptr, nullptr,
+                                                      nullptr, rows, c, scratch, &nblocks);
+        if (rc) return rc;
+        partial = scratch;
+    }
+    hipLaunchKernelGGL(bn_sums_kernel, dim3(c), dim3(256), 0, ctx->stream, partial, nblocks, c, (double)rows, sums,
+                       (float*)nullptr, (float*)nullptr);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
+extern "C" int y3_bn_sync_stats_finish(y3_ctx* ctx, const double* sums, int c, const float* gamma, const float* beta, float eps,
+                                       float decay, float* mean, float* inv_std, float* scale, float* shift,
+                                       float* moving_mean, float* moving_var) {
+    Y3_CHECK_ARG(ctx && sums && gamma && beta && mean && inv_std && scale && shift, "y3_bn_sync_stats_finish: null argument");
+    Y3_CHECK_ARG(c > 0, "y3_bn_sync_stats_finish: bad shape");
+    Y3_CHECK_ARG((moving_mean == nullptr) == (moving_var == nullptr), "y3_bn_sync_stats_finish: moving stats must come in pairs");
+    hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((c + 255) / 256), dim3(256), 0, ctx->stream, sums, c, gamma, beta, eps,
+                       decay, mean, inv_std, scale, shift, moving_mean, moving_var);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
 // How the passes over a tensor stored as T read it (measured, profiles/r06_bn_nt_ab.txt): the fp32 reduction keeps z and dy in
 // the caches for the apply pass right behind it, the fp32 apply passes stream; the bf16 passes read plainly.
 template <class T> struct BnAccess;
@@ -881,24 +968,39 @@ extern "C" int y3_bn_apply_fwd(y3_ctx* ctx, const float* z, const float* scale, 
 
 // BN backward of a tensor stored as T, dz stored alike: the reduction (unless the caller hands its partial sums in: `partial`,
 // [nblocks][2][c]), the finalize and the apply pass.  scratch: y3_bn_bwd_scratch_bytes - the partial rows, then [3][c] coefficients.
+// With an exchange buffer `sums` the finalize is its two halves, and `halves` says which side of the exchange to run:
+// BN_SUMS the reduction and the sums (d gamma, d beta from the local ones), BN_FINISH the coefficients and the apply pass.
+enum { BN_SUMS = 1, BN_FINISH = 2 };
 template <class T>
 static int bn_bwd(y3_ctx* ctx, const T* z, const float* dy, const float* gamma, const float* scale, const float* shift,
                   const float* mean, const float* inv_std, long long rows, int c, const float* partial, int nblocks, float* dgamma,
-                  float* dbeta, T* dz, float* scratch) {
+                  float* dbeta, T* dz, float* scratch, double* sums = nullptr, int halves = BN_SUMS | BN_FINISH) {
     typedef BnAccess<T> Acc;
-    if (!partial) {
-        if (int rc = (reduce_launch<1, typename Acc::Reduce>(ctx, z, dy, scale, shift, mean, inv_std, rows, c, scratch, &nblocks)))
-            return rc;
-        partial = scratch;
-    }
     float* coef = scratch + (size_t)RED_BLOCKS * 2 * c;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, partial, nblocks, c,
-                       (double)rows, gamma, inv_std, dbeta, dgamma, coef);
-    Y3_CHECK_HIP(hipGetLastError());
-    const long long total4 = rows * (c / 4);
-    hipLaunchKernelGGL((bn_apply_bwd_kernel<typename Acc::Apply, typename Acc::Apply>), dim3(grid_for(total4)), dim3(256), 0,
-                       ctx->stream, z, dy, scale, shift, mean, inv_std, coef, total4, c / 4, dz);
-    Y3_CHECK_HIP(hipGetLastError());
+    if (halves & BN_SUMS) {
+        if (!partial) {
+            if (int rc = (reduce_launch<1, typename Acc::Reduce>(ctx, z, dy, scale, shift, mean, inv_std, rows, c, scratch, &nblocks)))
+                return rc;
+            partial = scratch;
+        }
+        if (sums)
+            hipLaunchKernelGGL(bn_sums_kernel, dim3(c), dim3(256), 0, ctx->stream, partial, nblocks, c, (double)rows, sums, dbeta,
+                               dgamma);
+        else
+            hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, ctx->stream, partial, nblocks, c,
+                               (double)rows, gamma, inv_std, dbeta, dgamma, coef);
+        Y3_CHECK_HIP(hipGetLastError());
+    }
+    if (halves & BN_FINISH) {
+        if (sums) {
+            hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((c + 255) / 256), dim3(256), 0, ctx->stream, sums, c, gamma, inv_std, coef);
+            Y3_CHECK_HIP(hipGetLastError());
+        }
+        const long long total4 = rows * (c / 4);
+        hipLaunchKernelGGL((bn_apply_bwd_kernel<typename Acc::Apply, typename Acc::Apply>), dim3(grid_for(total4)), dim3(256), 0,
+                           ctx->stream, z, dy, scale, shift, mean, inv_std, coef, total4, c / 4, dz);
+        Y3_CHECK_HIP(hipGetLastError());
+    }
     return Y3_OK;
 }
 
@@ -919,6 +1021,32 @@ extern "C" int y3_bn_train_bwd_partials(y3_ctx* ctx, const float* z, const float
                  "y3_bn_train_bwd_partials: null argument");
     Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_train_bwd_partials: bad shape");
     return bn_bwd<float>(ctx, z, dy, gamma, scale, shift, mean, inv_std, rows, c, partial, nblocks, dgamma, dbeta, dz, scratch);
+}
+
+// The two halves of the backward (include/yolo355.h, synchronised batch norm): z fp32, or bf16 (then dz too) when z_bf16.
+extern "C" int y3_bn_sync_bwd_sums(y3_ctx* ctx, const void* z, int z_bf16, const float* dy, const float* scale, const float* shift,
+                                   const float* mean, const float* inv_std, long long rows, int c, const float* partial,
+                                   int nblocks, float* dgamma, float* dbeta, double* sums, float* scratch) {
+    Y3_CHECK_ARG(ctx && z && dy && scale && shift && mean && inv_std && sums && scratch && (!partial || nblocks > 0),
+                 "y3_bn_sync_bwd_sums: null argument");
+    Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_sync_bwd_sums: bad shape");
+    return z_bf16 ? bn_bwd<bf16_t>(ctx, static_cast<const bf16_t*>(z), dy, nullptr, scale, shift, mean, inv_std, rows, c, partial,
+                                   nblocks, dgamma, dbeta, nullptr, scratch, sums, BN_SUMS)
+                  : bn_bwd<float>(ctx, static_cast<const float*>(z), dy, nullptr, scale, shift, mean, inv_std, rows, c, partial,
+                                  nblocks, dgamma, dbeta, nullptr, scratch, sums, BN_SUMS);
+}
+
+extern "C" int y3_bn_sync_bwd_finish(y3_ctx* ctx, const void* z, int z_bf16, const float* dy, const float* gamma, const float* scale,
+                                     const float* shift, const float* mean, const float* inv_std, long long rows, int c,
+                                     const double* sums, void* dz, float* scratch) {
+    Y3_CHECK_ARG(ctx && z && dy && gamma && scale && shift && mean && inv_std && sums && dz && scratch,
+                 "y3_bn_sync_bwd_finish: null argument");
+    Y3_CHECK_ARG(rows > 0 && c > 0 && c % 4 == 0, "y3_bn_sync_bwd_finish: bad shape");
+    double* s = const_cast<double*>(sums);      // (read only by this half)
+    return z_bf16 ? bn_bwd<bf16_t>(ctx, static_cast<const bf16_t*>(z), dy, gamma, scale, shift, mean, inv_std, rows, c, nullptr, 0,
+                                   nullptr, nullptr, static_cast<bf16_t*>(dz), scratch, s, BN_FINISH)
+                  : bn_bwd<float>(ctx, static_cast<const float*>(z), dy, gamma, scale, shift, mean, inv_std, rows, c, nullptr, 0,
+                                  nullptr, nullptr, static_cast<float*>(dz), scratch, s, BN_FINISH);
 }
 
 extern "C" size_t y3_bn_bwd_scratch_bytes(int c) { return y3_reduce_scratch_bytes(c) + (size_t)3 * (c > 0 ? c : 0) * sizeof(float); }

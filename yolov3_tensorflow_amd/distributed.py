@@ -88,6 +88,73 @@ class GradientExchange(object):
         self._works = []
 
 
+BN_SYNC_DOUBLES = 2 * 1024 + 1      # the widest BN layer's two column sums and the row count (include/yolo355.h)
+
+
+class BnSync(object):
+    """Synchronised batch norm for the data-parallel train step: the hook `y3_net_train_set_bn_sync` calls between the two
+    halves of every BN layer's finalize, and the float64 exchange tensor the halves share.
+
+        sync = BnSync(group, device=dev)
+        ... the train step writes this rank's (column sums, row count) of a BN layer into sync.buf[:doubles] on the current
+        stream and calls sync(layer, phase, doubles): all-reduce (SUM) of that slice; what the step enqueues afterwards
+        reads the sums and the count of the global batch ...
+
+    Two small collectives per BN layer and step (forward statistics, backward sums): 144 for the 72 BN layers.  On `nccl`
+    the collective is asynchronous and `wait()` orders the current stream behind it (no host synchronisation); on `gloo` it
+    is the plain blocking call.  With world == 1 (or no group) and `force` unset nothing is exchanged.
+
+    The order of the hook calls is the same on every rank as long as `update_vars` and the input size are: forward visits
+    the BN layers in layer order, backward in reverse down to the first trainable layer (the feeder's multi-scale draw is
+    seeded by the batch count, so every rank draws the same size).  The statistics are those of the global batch for ANY
+    split of it over the ranks, because the row count travels with the sums; the gradients equal those of the big-batch
+    step only when all ranks hold the same local batch size (each rank's loss is a mean over its own images)."""
+
+    def __init__(self, group=None, device=None):
+        self.group = group
+        self.world = 1
+        if group is not None or dist.is_initialized():
+            self.world = dist.get_world_size(group)
+        self.buf = torch.zeros(BN_SYNC_DOUBLES, dtype=torch.float64, device=device)
+        # test hooks, as GradientExchange's: `force` issues the collectives in a one-rank group too, `op` replaces SUM
+        self.force = False
+        self.op = dist.ReduceOp.SUM
+        self.calls = []         # (layer, phase) of every hook call since begin(), in order (introspection / tests)
+        self.error = None       # an exception raised inside the hook (the C caller only sees a nonzero status)
+
+    @property
+    def active(self):
+        return self.world > 1 or self.force
+
+    def begin(self):
+        self.calls = []
+        self.error = None
+
+    def exchange(self, doubles):
+        """Sum buf[:doubles] over the ranks, visible to what the current stream runs next."""
+        part = self.buf[:doubles]
+        if dist.get_backend(self.group) == 'nccl':
+            dist.all_reduce(part, op=self.op, group=self.group, async_op=True).wait()
+        else:
+            dist.all_reduce(part, op=self.op, group=self.group)
+
+    def __call__(self, layer, phase, doubles):
+        """The y3_bn_sync_fn body: 0, or nonzero with the exception kept in `error` (raise_error() re-raises it)."""
+        try:
+            self.calls.append((int(layer), int(phase)))
+            if self.active:
+                self.exchange(int(doubles))
+            return 0
+        except BaseException as e:      # (nothing may propagate through the C frames)
+            self.error = e
+            return 1
+
+    def raise_error(self):
+        e, self.error = self.error, None
+        if e is not None:
+            raise e
+
+
 def all_reduce_mean_(flat, segment_ends=None, group=None, bucket_bytes=DEFAULT_BUCKET_BYTES):
     """One-shot form (no overlap): SUM-all-reduce `flat` bucket by bucket and scale by 1/world in place."""
     ends = list(segment_ends) if segment_ends is not None else [flat.numel()]

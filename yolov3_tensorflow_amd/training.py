@@ -127,7 +127,32 @@ def _train_net(model, ctx, dev=None):
         _lib.check(L.y3_net_train_set_wgrad_stream(st['net'], ctypes.c_void_p(handle) if handle else None))
         st['wgrad_key'] = key
         st['ws_shape'] = None            # (the allocation sequence of backward changes with it)
+    # synchronised batch norm (include/yolo355.h: y3_net_train_set_bn_sync): the distributed.BnSync a Trainer(sync_bn=True)
+    # left on the model, installed while it is active
+    sync = getattr(model, 'bn_sync', None)
+    sync = sync if sync is not None and sync.active else None
+    key = (id(sync) if sync is not None else None, st['net'].value)
+    if st.get('bn_sync_key') != key:
+        if sync is None:
+            _lib.check(L.y3_net_train_set_bn_sync(st['net'], _lib.BnSyncFn(), None, None, 0))
+            st['bn_sync_cb'] = None
+        else:
+            if sync.buf.device.type != 'cuda':
+                sync.buf = sync.buf.to(dev if dev is not None else fw.default_device())
+            cb = _lib.BnSyncFn(lambda user, layer, phase, doubles: sync(layer, phase, doubles))
+            _lib.check(L.y3_net_train_set_bn_sync(st['net'], cb, None, fw.ptr(sync.buf),
+                                                  ctypes.c_size_t(sync.buf.numel() * sync.buf.element_size())))
+            st['bn_sync_cb'] = (cb, sync)        # (kept alive while the net may call it)
+        st['bn_sync_key'] = key
     return st['net']
+
+
+def _checked(model, rc):
+    """_lib.check for the train-step entries: an exception the batch-norm exchange hook caught comes first."""
+    sync = getattr(model, 'bn_sync', None)
+    if sync is not None:
+        sync.raise_error()
+    _lib.check(rc)
 
 
 def _var_table(layer_vars, offsets=None, layer_ends=None):
@@ -215,8 +240,10 @@ def forward_train(model, x):
     n, h, w, _ = x.shape
     opts, anc = _opts(model)
     fm = [ctypes.c_void_p() for _ in range(3)]
-    _lib.check(_lib.lib().y3_net_train_forward(net, st['vars_all'], fw.ptr(x), n, h, w, ctypes.byref(opts), fw.ptr(st['ws']),
-                                               ctypes.c_size_t(st['ws'].numel()), *[ctypes.byref(p) for p in fm]))
+    if getattr(model, 'bn_sync', None) is not None:
+        model.bn_sync.begin()
+    _checked(model, _lib.lib().y3_net_train_forward(net, st['vars_all'], fw.ptr(x), n, h, w, ctypes.byref(opts), fw.ptr(st['ws']),
+                                                    ctypes.c_size_t(st['ws'].numel()), *[ctypes.byref(p) for p in fm]))
     fms = _after_forward(model, st, [p.value for p in fm])
     return fms[0], fms[1], fms[2]
 
@@ -342,8 +369,18 @@ class Trainer(object):
     factor is folded into the clip/update kernel) before clipping."""
 
     def __init__(self, model, optimizer, update_vars=None, clip_norm=CLIP_NORM, process_group=None,
-                 global_step=0.0, bucket_bytes=distributed.DEFAULT_BUCKET_BYTES, wgrad_stream='auto'):
+                 global_step=0.0, bucket_bytes=distributed.DEFAULT_BUCKET_BYTES, wgrad_stream='auto', sync_bn=False):
         self.model, self.opt = model, optimizer
+        # Synchronised batch norm (distributed.BnSync; off by default): every BN layer normalises with the statistics of the
+        # GLOBAL batch and every rank keeps the same moving statistics, so an N-rank step is the single-GPU step at N times
+        # the batch (given equal local batch sizes).  Costs two small collectives per BN layer and step.  True, or a BnSync
+        # of the caller's; the hook is installed only while that object is active - a group of more than one rank, or its
+        # `force` test switch - and serves step() and the split forward(is_training=True) / compute_loss / backward() path.
+        self.bn_sync = None
+        if sync_bn:
+            self.bn_sync = sync_bn if isinstance(sync_bn, distributed.BnSync) else distributed.BnSync(process_group)
+        if self.bn_sync is not None or getattr(model, 'bn_sync', None) is not None:
+            model.bn_sync = self.bn_sync        # (where forward(is_training=True), which has no Trainer, finds it)
         # backward's weight gradients on a second stream (include/yolo355.h: y3_net_train_set_wgrad_stream): True / False /
         # a torch.cuda.Stream / 'auto'.  Every result is bit-identical either way; only the step time differs - and by how
         # much depends on which hardware queue the second stream lands on (with many streams alive in the process it can
@@ -422,7 +459,7 @@ class Trainer(object):
         net = _train_net(self.model, fw.context(dev), dev)         # (the mode may have changed since the forward)
         arr = self._vars(st['layer_vars'], dev)
         self.exchange.begin()
-        _lib.check(_lib.lib().y3_net_train_backward(net, arr, fw.ptr(self.flat), self._ready_cb(), None))
+        _checked(self.model, _lib.lib().y3_net_train_backward(net, arr, fw.ptr(self.flat), self._ready_cb(), None))
         if self.capture is not None:
             self._fill_capture(st)
 
@@ -509,9 +546,11 @@ class Trainer(object):
         opts, anc = _opts(self.model)
         loss5 = torch.empty(5, dtype=torch.float32, device=x.device)
         self.exchange.begin()
-        _lib.check(_lib.lib().y3_net_train_step(net, arr, fw.ptr(x), n, h, w, fw.ptr(yt[0]), fw.ptr(yt[1]), fw.ptr(yt[2]),
-                                                ctypes.byref(opts), fw.ptr(self.flat), fw.ptr(st['ws']),
-                                                ctypes.c_size_t(st['ws'].numel()), fw.ptr(loss5), self._ready_cb(), None))
+        if self.bn_sync is not None:
+            self.bn_sync.begin()
+        _checked(self.model, _lib.lib().y3_net_train_step(net, arr, fw.ptr(x), n, h, w, fw.ptr(yt[0]), fw.ptr(yt[1]), fw.ptr(yt[2]),
+                                                          ctypes.byref(opts), fw.ptr(self.flat), fw.ptr(st['ws']),
+                                                          ctypes.c_size_t(st['ws'].numel()), fw.ptr(loss5), self._ready_cb(), None))
         st.update(have_loss=True, fms=None, fm_ptrs=None)
         for wvar, bnv, bias in layer_vars:
             if bnv is not None:
