@@ -120,6 +120,24 @@ size_t y3_conv_workspace_bytes(const y3_conv_desc* d);
  * `local_worker`'s range of the remaining (b1 - b0 - R*G) * ksteps items, cut as above. */
 int y3_streamk_range(int kind, int units, int ksteps, int workers, int group, int local_worker, long long* begin,
                      long long* end);
+/* Image ranges.  The fp32 conv kernels form 32-bit byte offsets, so ONE launch takes tensors below 2^29
+ * elements.  Tensors are NHWC with the image index outermost: y3_conv2d_fwd[_stats], y3_conv2d_fwd_split,
+ * y3_conv2d_dgrad[_bn], y3_conv2d_dgrad_split and y3_conv_wgrad run a larger call as several launches of the same kernel
+ * over consecutive image ranges - nothing changes for the caller, and below the limit the call is the single launch it has
+ * always been.  Reductions keep one fixed order: the statistics / BN-backward partial rows of a range lie behind the
+ * previous range's (y3_conv_stats_blocks and y3_conv_dgrad_bn_blocks count them so), the weight gradient's split partials
+ * of all ranges are added by one sum kernel, range-major (y3_conv_wgrad_scratch_bytes holds them all).  A cut call never
+ * takes the stream-K schedule (y3_conv_schedule and y3_conv_workspace_bytes say so).  The Winograd, F(4x4,3x3) and bf16
+ * entries keep their own limits (2^29; bf16: 2^30) and refuse larger tensors.
+ * y3_conv_image_ranges is the planner all of them use (host arithmetic only): d is the FORWARD conv, its tensors are
+ * [n,h,w,cin] and [n,h/stride,w/stride,co] with co = dz_stride where dz_stride > 0 (a gradient's row stride), else cout.
+ * It writes begin[i], count[i] of the fewest ranges, of near-equal size, that keep both tensors below `limit` elements and
+ * returns their number (1 = not cut), or Y3_EINVAL when one image alone reaches the limit or more than max_ranges ranges
+ * would be needed.
+ * Test hook: y3_debug_conv_range_limit(elements) lowers the limit of the entries above (process-wide) so that small shapes
+ * are cut; 0 restores 2^29; values above 2^29 are ignored - it never raises any limit. */
+int y3_conv_image_ranges(const y3_conv_desc* d, int dz_stride, long long limit, int max_ranges, int* begin, int* count);
+void y3_debug_conv_range_limit(long long elements);
 int y3_conv2d_fwd(y3_ctx* ctx, const y3_conv_desc* d, const float* x, const float* x_up,
                   const float* w, const float* scale, const float* shift, const float* residual,
                   float* y, void* workspace, size_t workspace_bytes);

@@ -50,6 +50,8 @@ PROTOTYPES = {
     "y3_conv_workspace_bytes": (c_size_t, [POINTER(ConvDesc)]),
     "y3_streamk_range": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(ctypes.c_longlong),
                                  POINTER(ctypes.c_longlong)]),
+    "y3_conv_image_ranges": (c_int, [POINTER(ConvDesc), c_int, ctypes.c_longlong, c_int, POINTER(c_int), POINTER(c_int)]),
+    "y3_debug_conv_range_limit": (None, [ctypes.c_longlong]),
     "y3_conv2d_fwd": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_size_t]),
     "y3_conv_wino_eligible": (c_int, [POINTER(ConvDesc)]),

@@ -105,6 +105,47 @@ void y3_sk_debug_env(unsigned* spin_limit, int* fault) {
     *spin_limit = *fault ? (1u << 10) : (1u << 22);
 }
 
+// ---- image-range launches: the fp32 conv kernels form 32-bit byte offsets, so one launch takes tensors below
+// 2^29 elements.  Tensors are NHWC with the image index outermost: a larger launch runs as several launches of the same
+// kernel over consecutive image ranges, and this planner is the one place that cuts them - the launchers and the scratch /
+// block-count queries all ask it.  d is the FORWARD conv; its tensors are [n,h,w,cin] and [n,h/stride,w/stride,co] with
+// co = dz_stride where that is > 0 (a gradient's padded rows), else cout.  As few ranges as possible, of near-equal size
+// (the first n % ranges hold one image more).  Returns the number of ranges, or Y3_EINVAL: one image alone reaches the
+// limit, or more than max_ranges would be needed.
+static long long g_range_limit = 0;
+extern "C" void y3_debug_conv_range_limit(long long elements) {
+    if (elements < 0 || elements > Y3_CONV_RANGE_LIMIT) return;      // (never raises the limit)
+    __atomic_store_n(&g_range_limit, elements, __ATOMIC_RELAXED);
+}
+long long y3_conv_range_limit() {
+    const long long v = __atomic_load_n(&g_range_limit, __ATOMIC_RELAXED);
+    return v > 0 ? v : Y3_CONV_RANGE_LIMIT;
+}
+
+int y3_conv_image_ranges_impl(const y3_conv_desc* d, int dz_stride, long long limit, int max_ranges, int* begin, int* count) {
+    Y3_CHECK_ARG(d && begin && count && max_ranges > 0 && limit > 0 && dz_stride >= 0, "y3_conv_image_ranges: bad argument");
+    Y3_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0 && d->stride > 0,
+                 "y3_conv_image_ranges: non-positive dimension");
+    const long long in_img = (long long)d->h * d->w * d->cin;
+    const long long out_img = (long long)(d->h / d->stride) * (d->w / d->stride) * (dz_stride > 0 ? dz_stride : d->cout);
+    const long long img = in_img > out_img ? in_img : out_img;
+    Y3_CHECK_ARG(img < limit, "y3_conv_image_ranges: one image of this conv holds %lld elements, the limit of a launch is %lld "
+                 "(tensor exceeds 2^29 elements (32-bit byte offsets) and cannot be cut between images)", img, limit);
+    const long long per = (limit - 1) / img;                       // images a launch may take: per * img < limit
+    const long long nr = (d->n + per - 1) / per;
+    Y3_CHECK_ARG(nr <= max_ranges, "y3_conv_image_ranges: %lld image ranges needed, room for %d", nr, max_ranges);
+    const int q = d->n / (int)nr, r = d->n % (int)nr;
+    for (int i = 0, b = 0; i < (int)nr; ++i) {
+        begin[i] = b;
+        count[i] = q + (i < r ? 1 : 0);
+        b += count[i];
+    }
+    return (int)nr;
+}
+extern "C" int y3_conv_image_ranges(const y3_conv_desc* d, int dz_stride, long long limit, int max_ranges, int* begin, int* count) {
+    return y3_conv_image_ranges_impl(d, dz_stride, limit, max_ranges, begin, count);
+}
+
 static const char* kStreamKTimeout =
     "a stream-K hand-off timed out in an earlier launch on this context (a consumer workgroup gave up waiting for a "
     "partial sum): the output of that launch is INVALID; y3_ctx_check clears the condition";

@@ -413,10 +413,17 @@ int y3_conv_schedule_query(const y3_conv_desc* d, int tmode_taps, int with_works
         return 0;                                   // (the stem: one thread per pixel)
     if (tmode_taps != 0 && (d->k != 3 || d->stride != 1 || d->c_up > 0 || (tmode_taps != 1 && tmode_taps != 2 && tmode_taps != 4)))
         return 0;
+    // A cut launch (image ranges) answers for its first range, the largest, and never takes stream-K: the ranges run without
+    // a workspace.  The tensors of a parity class: the coarse gradient [n,h,w,cin] and the 2x finer output [n,2h,2w,cout].
+    y3_conv_desc whole = *d;
+    if (tmode_taps) { whole.h = 2 * d->h; whole.w = 2 * d->w; whole.cin = d->cout; whole.cout = d->cin; whole.stride = 2; }
+    const y3_image_ranges rg(&whole, 0);
+    if (rg.n < 0) return 0;
+    if (rg.n > 1) with_workspace = 0;
     ConvArgs a{};        // (value-initialised: use_streamk reads Cin, xu, tmode and ntaps too)
     a.Cin = d->cin;
     a.Cout = d->cout;
-    a.M = d->n * (d->h / d->stride) * (d->w / d->stride);
+    a.M = rg.count[0] * (d->h / d->stride) * (d->w / d->stride);
     a.tmode = tmode_taps ? 1 : 0;
     a.ntaps = tmode_taps;
     int s = 0;
@@ -442,6 +449,7 @@ int y3_streamk_range_impl(int kind, int units, int ksteps, int workers, int grou
 
 size_t y3_conv_workspace_bytes_impl(const y3_conv_desc* d) {
     if (!d || d->k != 3 || d->cout < 128 || d->c_up > 0) return 0;
+    if (d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->stride > 0 && y3_image_ranges(d, 0).n > 1) return 0;   // a cut launch: no stream-K
     return SK_WORKSPACE_BYTES;
 }
 
@@ -465,12 +473,32 @@ int y3_launch_conv(hipStream_t stream, const y3_conv_desc* d, const float* x, co
     a.Cout = d->cout; a.stride = d->stride; a.pad = d->k / 2; a.act = d->act;
     a.Ho = d->h / d->stride; a.Wo = d->w / d->stride;
     const long long M = (long long)d->n * a.Ho * a.Wo;
-    Y3_CHECK_ARG((long long)d->n * d->h * d->w * d->cin < (1LL << 29) && M * d->cout < (1LL << 29),
-                 "y3_conv2d_fwd: tensor exceeds 2^29 elements (32-bit byte offsets)");
-    a.M = (int)M;
     a.stats = sk ? sk->stats : nullptr;
     Y3_CHECK_ARG(!a.stats || (d->cin != 3 && !x_up && d->cout % 4 == 0),
                  "y3_conv2d_fwd_stats: statistics need Cin != 3, no fused upsample input and Cout %% 4 == 0");
+    const y3_image_ranges rg(d, 0);
+    if (rg.n < 0) return rg.n;
+    if (rg.n > 1) {
+        // A tensor of 2^29 elements or more: the same launch per image range, every pointer advanced by whole images, the
+        // statistics rows of a range behind the previous range's (y3_conv_stats_blocks counts them the same way).  A cut
+        // launch never takes the stream-K schedule - the ranges get no workspace: one set of flag words and accumulator
+        // slots serves one launch.
+        y3_sk_opts o;
+        if (sk) o = *sk;
+        o.flags = nullptr;
+        for (int i = 0; i < rg.n; ++i) {
+            y3_conv_desc dr = *d;
+            dr.n = rg.count[i];
+            const size_t b = (size_t)rg.begin[i];
+            const size_t out = b * a.Ho * a.Wo * d->cout;
+            if (int rc = y3_launch_conv(stream, &dr, x + b * d->h * d->w * a.Cx, x_up ? x_up + b * (d->h / 2) * (d->w / 2) * a.Cu : nullptr,
+                                        w, scale, shift, residual ? residual + out : nullptr, y + out, nullptr, 0, &o))
+                return rc;
+            if (o.stats) o.stats += (size_t)y3_conv_stats_blocks_impl(&dr, 0) * 2 * d->cout;
+        }
+        return Y3_OK;
+    }
+    a.M = (int)M;
 
     if (d->cin == 3) {
         Y3_CHECK_ARG(d->k == 3 && d->cout == 32 && !x_up && !residual,
@@ -511,16 +539,24 @@ int y3_conv_stats_blocks_impl(const y3_conv_desc* d, int wino) {
         return (int)((T + 63) / 64);
     }
     if (!((d->k == 1 && d->stride == 1) || d->k == 3) || (d->stride != 1 && d->stride != 2)) return 0;
-    const long long M = (long long)d->n * (d->h / d->stride) * (d->w / d->stride);
+    if (d->cin <= 0 || d->cout <= 0) return 0;
     const int bm = (d->k == 1 && d->cout > 64) ? 64 : 128;
-    return (int)((M + bm - 1) / bm);
+    // a cut launch (image ranges): every range starts a row block of its own, its rows behind the previous range's
+    const y3_image_ranges rg(d, 0);
+    long long nb = 0;
+    for (int i = 0; i < rg.n; ++i) nb += ((long long)rg.count[i] * (d->h / d->stride) * (d->w / d->stride) + bm - 1) / bm;
+    return (int)nb;                                  // (rg.n < 0, one image over the limit: 0, no such launch)
 }
 
+// (dz rows of Cout rounded up to the K-step: what y3_launch_conv_dgrad asks of a cut launch with the fused reduction)
 int y3_conv_dgrad_stats_blocks_impl(const y3_conv_desc* fwd) {
     if (!fwd || fwd->k != 1 || fwd->stride != 1 || fwd->c_up != 0 || fwd->cin % 4 != 0) return 0;
-    const long long M = (long long)fwd->n * fwd->h * fwd->w;
+    if (fwd->n <= 0 || fwd->h <= 0 || fwd->w <= 0 || fwd->cin <= 0 || fwd->cout <= 0) return 0;
     const int bm = fwd->cin > 64 ? 64 : 128;        // dispatch_bn's tile for Cout' = fwd->cin
-    return (int)((M + bm - 1) / bm);
+    const y3_image_ranges rg(fwd, (fwd->cout + BK - 1) / BK * BK);
+    long long nb = 0;
+    for (int i = 0; i < rg.n; ++i) nb += ((long long)rg.count[i] * fwd->h * fwd->w + bm - 1) / bm;
+    return (int)nb;
 }
 
 // Data gradient of a conv layer as a forward conv over dz:
@@ -549,8 +585,32 @@ int y3_launch_conv_dgrad(hipStream_t stream, const y3_conv_desc* fwd, const floa
     a.Cout = fwd->cin; a.stride = 1; a.pad = fwd->k / 2; a.act = 0;
     a.Ho = fwd->h; a.Wo = fwd->w;
     const long long M = (long long)fwd->n * fwd->h * fwd->w;
-    Y3_CHECK_ARG(M * fwd->cin < (1LL << 29) && (long long)fwd->n * Ho * Wo * dz_stride < (1LL << 29),
-                 "y3_conv2d_dgrad: tensor exceeds 2^29 elements (32-bit byte offsets)");
+    Y3_CHECK_ARG(fwd->n > 0 && fwd->h > 0 && fwd->w > 0 && fwd->cin > 0 && fwd->cout > 0, "y3_conv2d_dgrad: non-positive dimension");
+    const y3_image_ranges rg(fwd, dz_stride);
+    if (rg.n < 0) return rg.n;
+    if (rg.n > 1) {
+        // image ranges, as in y3_launch_conv: dz, dx (and the fused reduction's z) advance by whole images, the partial rows of
+        // a range lie behind the previous range's (y3_conv_dgrad_bn_blocks), and no range takes stream-K (no workspace)
+        y3_sk_opts o;
+        if (sk) o = *sk;
+        o.flags = nullptr;
+        Y3_CHECK_ARG(!o.bwd_z || dz_stride == (fwd->cout + BK - 1) / BK * BK,
+                     "y3_conv2d_dgrad: the fused BN reduction of a launch cut into image ranges needs dz rows of Cout rounded up to %d", BK);
+        for (int i = 0; i < rg.n; ++i) {
+            y3_conv_desc fr = *fwd;
+            fr.n = rg.count[i];
+            const size_t b = (size_t)rg.begin[i];
+            const size_t in = b * fwd->h * fwd->w * fwd->cin;
+            if (int rc = y3_launch_conv_dgrad(stream, &fr, dz + b * Ho * Wo * dz_stride, dz_stride, w_d, ones, zeros, accumulate,
+                                              dx + in, nullptr, 0, &o))
+                return rc;
+            if (o.bwd_z) {
+                o.bwd_z += (size_t)fr.n * fwd->h * fwd->w * fwd->cin;
+                o.stats += (size_t)y3_conv_dgrad_stats_blocks_impl(&fr) * 2 * fwd->cin;
+            }
+        }
+        return Y3_OK;
+    }
     a.M = (int)M;
     if (fwd->k == 1) {
         if (sk && sk->bwd_z) {

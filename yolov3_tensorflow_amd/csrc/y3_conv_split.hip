@@ -391,10 +391,7 @@ int check_desc(const y3_conv_desc* d, const void* x_up, const char* who) {
         Y3_CHECK_ARG(d->c_up % (2 * SBK) == 0 && d->c_up < d->cin && d->h % 2 == 0 && d->w % 2 == 0,
                      "%s: bad c_up=%d for cin=%d", who, d->c_up, d->cin);
     }
-    const long long M = (long long)d->n * (d->h / d->stride) * (d->w / d->stride);
-    Y3_CHECK_ARG((long long)d->n * d->h * d->w * d->cin < (1LL << 29) && M * d->cout < (1LL << 29),
-                 "%s: tensor exceeds 2^29 elements (32-bit byte offsets)", who);
-    return Y3_OK;
+    return Y3_OK;      // (the element limit: the launchers' image ranges)
 }
 
 void fill_args(ConvArgs& a, const y3_conv_desc* d) {
@@ -432,6 +429,25 @@ int y3_launch_conv_split(hipStream_t stream, const y3_conv_desc* d, int planes, 
         return y3_launch_conv(stream, d, x, x_up, static_cast<const float*>(w), scale, shift, residual, y,
                               workspace, workspace_bytes, sk);
     if (int rc = check_desc(d, x_up, "y3_conv2d_fwd_split")) return rc;
+    const y3_image_ranges rg(d, 0);
+    if (rg.n < 0) return rg.n;
+    if (rg.n > 1) {
+        // image ranges, as in y3_launch_conv: the pointers advance by whole images; no range takes stream-K
+        y3_sk_opts o;
+        if (sk) o = *sk;
+        o.flags = nullptr;
+        const size_t in_img = (size_t)d->h * d->w * (d->cin - d->c_up), up_img = (size_t)(d->h / 2) * (d->w / 2) * d->c_up;
+        const size_t out_img = (size_t)(d->h / d->stride) * (d->w / d->stride) * d->cout;
+        for (int i = 0; i < rg.n; ++i) {
+            y3_conv_desc dr = *d;
+            dr.n = rg.count[i];
+            const size_t b = (size_t)rg.begin[i];
+            if (int rc = y3_launch_conv_split(stream, &dr, planes, x + b * in_img, x_up ? x_up + b * up_img : nullptr, w, scale, shift,
+                                              residual ? residual + b * out_img : nullptr, y + b * out_img, nullptr, 0, &o))
+                return rc;
+        }
+        return Y3_OK;
+    }
     ConvArgs a;
     a.x = x; a.xu = x_up; a.w = static_cast<const float*>(w); a.scale = scale; a.shift = shift;
     a.resid = residual; a.y = y;
@@ -456,9 +472,25 @@ int y3_launch_conv_dgrad_split(hipStream_t stream, const y3_conv_desc* fwd, int 
                  "y3_conv2d_dgrad_split: Cin must be a multiple of 4");
     y3_conv_desc d = *fwd;              // the gradient conv: [n,h,w,dz_stride] -> [n,h,w,cin]
     d.cin = dz_stride; d.c_up = 0; d.cout = fwd->cin; d.act = 0;
-    const long long M = (long long)fwd->n * fwd->h * fwd->w;
-    Y3_CHECK_ARG(M * fwd->cin < (1LL << 29) && M * dz_stride < (1LL << 29),
-                 "y3_conv2d_dgrad_split: tensor exceeds 2^29 elements (32-bit byte offsets)");
+    Y3_CHECK_ARG(fwd->cin > 0 && fwd->cout > 0, "y3_conv2d_dgrad_split: non-positive dimension");
+    const y3_image_ranges rg(fwd, dz_stride);
+    if (rg.n < 0) return rg.n;
+    if (rg.n > 1) {
+        // image ranges, as in y3_launch_conv: dz and dx advance by whole images; no range takes stream-K
+        y3_sk_opts o;
+        if (sk) o = *sk;
+        o.flags = nullptr;
+        const size_t px = (size_t)fwd->h * fwd->w;
+        for (int i = 0; i < rg.n; ++i) {
+            y3_conv_desc fr = *fwd;
+            fr.n = rg.count[i];
+            const size_t b = (size_t)rg.begin[i];
+            if (int rc = y3_launch_conv_dgrad_split(stream, &fr, planes, dz + b * px * dz_stride, dz_stride, w, ones, zeros, accumulate,
+                                                    dx + b * px * fwd->cin, nullptr, 0, &o))
+                return rc;
+        }
+        return Y3_OK;
+    }
     ConvArgs a;
     a.x = dz; a.xu = nullptr; a.w = static_cast<const float*>(w); a.scale = ones; a.shift = zeros;
     a.resid = accumulate ? dx : nullptr; a.y = dx;

@@ -49,6 +49,20 @@ int y3_conv_dgrad_stats_blocks_impl(const y3_conv_desc* fwd);
 // the consumers give up after 2^10 polls, so the time-out path (error word -> Y3_EHIP) can be exercised.
 void y3_sk_debug_env(unsigned* spin_limit, int* fault);
 
+// Image-range launches (y3_abi.hip).  A launcher that implements ranges plans with the CURRENT limit (2^29 elements,
+// or what the test hook y3_debug_conv_range_limit lowered it to) and at most Y3_MAX_RANGES ranges.
+constexpr long long Y3_CONV_RANGE_LIMIT = 1LL << 29;
+constexpr int Y3_MAX_RANGES = 256;
+long long y3_conv_range_limit();
+int y3_conv_image_ranges_impl(const y3_conv_desc* d, int dz_stride, long long limit, int max_ranges, int* begin, int* count);
+struct y3_image_ranges {
+    int n = 0;                                       // ranges (1: the launch is not cut), or Y3_EINVAL
+    int begin[Y3_MAX_RANGES], count[Y3_MAX_RANGES];
+    y3_image_ranges(const y3_conv_desc* d, int dz_stride) {
+        n = y3_conv_image_ranges_impl(d, dz_stride, y3_conv_range_limit(), Y3_MAX_RANGES, begin, count);
+    }
+};
+
 // Experiment switches (A/B runs of tools/ and tests/test_conv_variants_gpu.py) exist only in a -DY3_EXPERIMENTS build
 // (csrc/libyolo355_exp.so, `python -m yolov3_tensorflow_amd.build --experiments`): in the product library no environment
 // variable changes which kernel runs.

@@ -370,12 +370,46 @@ static void wgrad_split(const y3_conv_desc* d, int* nsplit_out, int* chunk_out) 
     *nsplit_out = best_ns;
 }
 
+// The stem's work split over n images: pieces of 128 pixels of one image row; one round of co-resident workgroups (21 KB of
+// LDS each: six per CU)
+static void stem_split(const y3_conv_desc* d, int n, int* ppr_out, long long* pieces_out, int* nblk_out, int* chunk_out) {
+    const int ppr = (d->w + 127) / 128;
+    const long long pieces = (long long)n * d->h * ppr;
+    int nblk = (int)(pieces < 1536 ? pieces : 1536);
+    const int chunk = (int)((pieces + nblk - 1) / nblk);
+    nblk = (int)((pieces + chunk - 1) / chunk);
+    *ppr_out = ppr; *pieces_out = pieces; *nblk_out = nblk; *chunk_out = chunk;
+}
+
+// A launch cut into image ranges keeps the split partials of every range, range-major, and one sum kernel adds them
+// all: the scratch holds the SUM of the ranges' splits (the stem: never less than the 4096 blocks it has always reserved).
+static size_t wgrad_scratch_need(const y3_conv_desc* d, const y3_image_ranges& rg) {
+    long long total = 0;
+    for (int i = 0; i < rg.n; ++i) {
+        y3_conv_desc dr = *d;
+        dr.n = rg.count[i];
+        if (d->cin == 3) {
+            int ppr, nblk, chunk;
+            long long pieces;
+            stem_split(&dr, dr.n, &ppr, &pieces, &nblk, &chunk);
+            total += nblk;
+        } else {
+            int nsplit, chunk;
+            wgrad_split(&dr, &nsplit, &chunk);
+            total += nsplit;
+        }
+    }
+    if (d->cin == 3) return (size_t)(total > 4096 ? total : 4096) * 27 * 32 * sizeof(float);
+    return (size_t)total * d->k * d->k * d->cin * d->cout * sizeof(float) + 256;
+}
+
+// (sized for dz rows of Cout rounded up to 4 floats: the densest dz y3_conv_wgrad takes.  A caller with wider rows whose launch
+// is cut differently is told "scratch too small" before anything runs.)
 extern "C" size_t y3_conv_wgrad_scratch_bytes(const y3_conv_desc* d) {
-    if (!d || d->n <= 0 || d->cin <= 0 || d->cout <= 0 || d->stride <= 0) return 0;
-    if (d->cin == 3) return (size_t)4096 * 27 * 32 * sizeof(float);
-    int nsplit, chunk;
-    wgrad_split(d, &nsplit, &chunk);
-    return (size_t)nsplit * d->k * d->k * d->cin * d->cout * sizeof(float) + 256;
+    if (!d || d->n <= 0 || d->cin <= 0 || d->cout <= 0 || d->stride <= 0 || d->h <= 0 || d->w <= 0) return 0;
+    const y3_image_ranges rg(d, (d->cout + 3) / 4 * 4);
+    if (rg.n < 0) return 0;
+    return wgrad_scratch_need(d, rg);
 }
 
 extern "C" int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* d, const float* x, const float* dz, int dz_stride,
@@ -385,42 +419,35 @@ extern "C" int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* d, const float* x,
     Y3_CHECK_ARG(d->stride == 1 || d->stride == 2, "y3_conv_wgrad: stride must be 1 or 2");
     Y3_CHECK_ARG(d->c_up == 0, "y3_conv_wgrad: fused upsample+concat inputs are not supported (materialise the concat)");
     Y3_CHECK_ARG(dz_stride >= d->cout && dz_stride % 4 == 0, "y3_conv_wgrad: dz row stride must be >= Cout and a multiple of 4");
-    Y3_CHECK_ARG(scratch_bytes >= y3_conv_wgrad_scratch_bytes(d), "y3_conv_wgrad: scratch too small");
+    Y3_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0, "y3_conv_wgrad: non-positive dimension");
+    // image ranges: one range below 2^29 elements - then this is the single launch it has always been
+    const y3_image_ranges rg(d, dz_stride);
+    if (rg.n < 0) return rg.n;
+    Y3_CHECK_ARG(scratch_bytes >= wgrad_scratch_need(d, rg), "y3_conv_wgrad: scratch too small");
     Y3_CHECK_ARG((reinterpret_cast<size_t>(scratch) & 15) == 0, "y3_conv_wgrad: scratch must be 16-byte aligned");
     const int Ho = d->h / d->stride, Wo = d->w / d->stride;
-    const long long M = (long long)d->n * Ho * Wo;
-    Y3_CHECK_ARG((long long)d->n * d->h * d->w * d->cin < (1LL << 29) && M * dz_stride < (1LL << 29),
-                 "y3_conv_wgrad: tensor exceeds 2^29 elements (32-bit byte offsets)");
     hipStream_t st = ctx->stream;
     if (d->cin == 3) {
         Y3_CHECK_ARG(d->k == 3 && d->cout == 32 && d->stride == 1 && dz_stride == 32,
                      "y3_conv_wgrad: Cin=3 is supported only as the 3x3 3->32 stem conv");
-        // pieces of 128 pixels of one image row; one round of co-resident workgroups (21 KB of LDS each: six per CU)
-        const int ppr = (d->w + 127) / 128;
-        const long long pieces = (long long)d->n * d->h * ppr;
-        Y3_CHECK_ARG(pieces < (1LL << 30), "y3_conv_wgrad: too many pixels");
-        int nblk = (int)(pieces < 1536 ? pieces : 1536);
-        const int chunk = (int)((pieces + nblk - 1) / nblk);
-        nblk = (int)((pieces + chunk - 1) / chunk);
         float* part = static_cast<float*>(scratch);
-        hipLaunchKernelGGL(stem_wgrad_kernel, dim3(nblk), dim3(256), 0, st, x, dz, d->n, d->h, d->w, ppr, (int)pieces,
-                           chunk, part);
-        Y3_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(stem_sum_splits_kernel, dim3(27), dim3(256), 0, st, part, nblk, dw_hwio);
+        int total = 0;
+        for (int i = 0; i < rg.n; ++i) {
+            int ppr, nblk, chunk;
+            long long pieces;
+            stem_split(d, rg.count[i], &ppr, &pieces, &nblk, &chunk);
+            Y3_CHECK_ARG(pieces < (1LL << 30), "y3_conv_wgrad: too many pixels");
+            const size_t b = (size_t)rg.begin[i] * d->h * d->w;
+            hipLaunchKernelGGL(stem_wgrad_kernel, dim3(nblk), dim3(256), 0, st, x + b * 3, dz + b * 32, rg.count[i], d->h, d->w,
+                               ppr, (int)pieces, chunk, part + (size_t)total * 27 * 32);
+            Y3_CHECK_HIP(hipGetLastError());
+            total += nblk;
+        }
+        hipLaunchKernelGGL(stem_sum_splits_kernel, dim3(27), dim3(256), 0, st, part, total, dw_hwio);
         Y3_CHECK_HIP(hipGetLastError());
         return Y3_OK;
     }
     Y3_CHECK_ARG(d->cin % 4 == 0, "y3_conv_wgrad: Cin must be 3 or a multiple of 4");
-    WgradArgs a;
-    a.x = x; a.dz = dz;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Ho = Ho; a.Wo = Wo; a.Cout = d->cout; a.CoP = dz_stride;
-    a.k = d->k; a.stride = d->stride; a.pad = d->k / 2; a.M = (int)M; a.J = d->k * d->k * d->cin;
-    const int bnt = wgrad_co_tile(a.Cout);
-    const int tiles = ((a.J + 127) / 128) * ((a.Cout + bnt - 1) / bnt);
-    int nsplit;
-    wgrad_split(d, &nsplit, &a.chunk);
-    a.nsplit = nsplit;
-    a.out = nsplit == 1 ? dw_hwio : static_cast<float*>(scratch);
     static bool attr_set[Y3_MAX_DEVICES] = {};
     const int dev_ = y3_current_device();
     if (dev_ < 0 || !attr_set[dev_]) {
@@ -429,21 +456,42 @@ extern "C" int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* d, const float* x,
                                          (int)(2 * WBK * (WLD + 128) * sizeof(float))));
         if (dev_ >= 0) attr_set[dev_] = true;
     }
+    const int J = d->k * d->k * d->cin;
+    const int bnt = wgrad_co_tile(d->cout);
+    const int tiles = ((J + 127) / 128) * ((d->cout + bnt - 1) / bnt);
     const size_t lds = (size_t)2 * WBK * (WLD + bnt) * sizeof(float);
-    if (bnt == 128)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2>), dim3(tiles, nsplit), dim3(256), lds, st, a);
-    else if (bnt == 64)
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2>), dim3(tiles, nsplit), dim3(256), lds, st, a);
-    else
-        hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1>), dim3(tiles, nsplit), dim3(256), lds, st, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    if (nsplit > 1) {
-        const long long n4 = (long long)a.J * a.Cout / 4;     // J = k*k*Cin, Cin % 4 == 0
+    int total = 0;                                   // splits written so far, all ranges
+    for (int i = 0; i < rg.n; ++i) {
+        y3_conv_desc dr = *d;
+        dr.n = rg.count[i];
+        WgradArgs a;
+        a.x = x + (size_t)rg.begin[i] * d->h * d->w * d->cin;
+        a.dz = dz + (size_t)rg.begin[i] * Ho * Wo * dz_stride;
+        a.N = dr.n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Ho = Ho; a.Wo = Wo; a.Cout = d->cout; a.CoP = dz_stride;
+        a.k = d->k; a.stride = d->stride; a.pad = d->k / 2; a.M = dr.n * Ho * Wo; a.J = J;
+        int nsplit;
+        wgrad_split(&dr, &nsplit, &a.chunk);
+        a.nsplit = nsplit;
+        // one range of one split writes dw itself; with more ranges every split of every range goes to the scratch, so that
+        // the one sum below adds them in one fixed order
+        a.out = (rg.n == 1 && nsplit == 1) ? dw_hwio : static_cast<float*>(scratch) + (size_t)total * J * d->cout;
+        if (bnt == 128)
+            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2>), dim3(tiles, nsplit), dim3(256), lds, st, a);
+        else if (bnt == 64)
+            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2>), dim3(tiles, nsplit), dim3(256), lds, st, a);
+        else
+            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1>), dim3(tiles, nsplit), dim3(256), lds, st, a);
+        Y3_CHECK_HIP(hipGetLastError());
+        total += nsplit;
+    }
+    if (total > 1) {
+        const long long n4 = (long long)J * d->cout / 4;     // J = k*k*Cin, Cin % 4 == 0
         long long nb = (n4 + 63) / 64;
         if (nb > 8192) nb = 8192;
         hipLaunchKernelGGL(wgrad_sum_splits_kernel, dim3((int)nb), dim3(256), 0, st, static_cast<float*>(scratch),
-                           nsplit, n4, dw_hwio);
+                           total, n4, dw_hwio);
         Y3_CHECK_HIP(hipGetLastError());
     }
     return Y3_OK;
 }
+
