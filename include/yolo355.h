@@ -467,7 +467,7 @@ int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* fwd, const float* x, const fl
  * bn_apply_fwd_bf16: y bf16 = leaky(z*scale + shift) (+ residual bf16); z bf16, or fp32 when z_f32.
  * bn_train_bwd_bf16: y3_bn_train_bwd with z bf16 and dz bf16 (dy, dgamma, dbeta fp32); scratch y3_bn_bwd_scratch_bytes(c).
  * upsample_concat_bf16: out [n,h,w,cu+cx] = concat(upsample2x(up [n,h/2,w/2,cu]), x [n,h,w,cx]), bf16.
- * f32_to_bf16: count (a multiple of 4) values rounded to nearest even. */
+ * f32_to_bf16: count (a multiple of 4) values rounded to nearest even; +-Inf stay, every NaN stays a (quiet) NaN. */
 int y3_pack_conv_weights_bf16_train(y3_ctx* ctx, const float* w_hwio, int k, int cin, int cout, int dgrad_stride,
                                     void* w_packed);
 int y3_conv_train_stats_blocks_bf16(const y3_conv_desc* fwd);

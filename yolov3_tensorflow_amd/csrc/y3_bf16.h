@@ -13,6 +13,14 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
     return (bf16_t)(u >> 16);
 }
 
+// The same rounding for ANY input: in f32_to_bf16 the rounding increment carries a NaN whose low mantissa bits are set out of
+// the mantissa (0x7FFFFFFF -> -0.0, 0xFFFFFFFF -> +0.0, 0x7F800001 -> +Inf).  Here a NaN stays a NaN (quiet, sign and upper
+// payload kept).  For values that enter from outside (y3_f32_to_bf16); the conv epilogues keep f32_to_bf16.
+__device__ __forceinline__ bf16_t f32_to_bf16_any(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x7FFFFFFFu) > 0x7F800000u ? (bf16_t)((u >> 16) | 0x0040u) : f32_to_bf16(f);
+}
+
 // (a, b) -> a packed bf16 pair by the compiler's vector conversion.  Not f32_to_bf16 twice: other instructions (and another
 // answer for a NaN), and each kernel was measured with the one it uses.
 __device__ __forceinline__ unsigned cvt_pack_bf16(float a, float b) {

@@ -355,8 +355,13 @@ __global__ void __launch_bounds__(256) upsample_concat_bf16_kernel(const bf16_t*
 
 __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restrict__ src, long long total4,
                                                           bf16_t* __restrict__ dst) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256)
-        st_bf16x4(dst + 4 * i, reinterpret_cast<const f32x4*>(src)[i]);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        // (not st_bf16x4: src is d loss / d fm or a caller's tensor, and a NaN in it, whatever its payload, stays a NaN)
+        const f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
+        *reinterpret_cast<uint2*>(dst + 4 * i) =
+            uint2{(unsigned)f32_to_bf16_any(v[0]) | ((unsigned)f32_to_bf16_any(v[1]) << 16),
+                  (unsigned)f32_to_bf16_any(v[2]) | ((unsigned)f32_to_bf16_any(v[3]) << 16)};
+    }
 }
 
 // ---- backward routing ----------------------------------------------------------------------------------
