@@ -38,6 +38,8 @@ OPTIONS = (
     ('batch_size', int, 32, 'images per device batch (the reference evaluates one at a time)'),
     ('compute_dtype', str, 'f32_wino', 'f32_wino (exact fp32, Winograd 3x3 kernels) | f32 | f32_bf16x6 (docs/history_r01_r05.md 4.3-4.4)'),
     ('map_on_device', _flag, False, 'true: match detections and compute AP on the device (eval_utils.DeviceEval, DESIGN.md 4.5)'),
+    ('coco_metric', _flag, False, 'true: also report the twelve COCO numbers (AP@[.50:.95], AP50, AP75, AP / AR by size, AR@1/10/100); '
+                                  'on the device with --map_on_device true, else eval_utils.coco_eval on the host'),
 )
 
 
@@ -142,6 +144,14 @@ def main(argv=None):
     out = {'mAP': mAP, 'val_preds': val_preds, 'loss': [m.average for m in meters], 'gt_dict': gt_dict}
     if table is not None:
         out['table'] = table
+    if args.coco_metric:      # small / medium / large in original pixels: the boxes live in the network-input frame
+        area_scale = eval_utils.parse_gt_area_scale(args.eval_file, args.img_size, args.letterbox_resize)
+        if device_eval is not None:
+            out['coco'] = device_eval.finish_coco(area_scale)
+        else:
+            out['coco'] = eval_utils.coco_eval(gt_dict, val_preds, args.class_num, area_scale)
+        for line in eval_utils.coco_summary_lines(out['coco']['stats']):
+            print(line)
     return out
 
 

@@ -688,6 +688,67 @@ int y3_voc_ap(y3_ctx* ctx, const uint8_t* tp, const int32_t* seg_start, int rows
               int class_num, int use_07_metric, const double* thresholds_host11, void* scratch, size_t scratch_bytes,
               double* out);
 
+/* COCO bbox metrics on the device (AP@[.50:.95], AP50, AP75, AP by object size, AR@1/10/100, AR by size): what
+ * eval_utils.coco_eval computes on the host, on the arena y3_voc_append fills.  All entries are asynchronous on the
+ * context's stream; every index read from device memory is clamped to the extents passed here before it addresses
+ * anything.  Arithmetic is float64 in coco_eval's operation order, without contraction (csrc/y3_coco_px.h).
+ *
+ * The rule (bbox evaluation in the COCOeval style; the annotation format has no crowd objects).  T = 10 IoU thresholds and
+ * R = 101 recall thresholds come from the host as numpy makes them (np.linspace(.5, .95, 10), np.linspace(0., 1., 101): the
+ * ninth IoU threshold is 0.8999999999999999 and is never recomputed here); A = 4 area ranges (lo, hi): all (0, 1e10), small
+ * (0, 32^2), medium (32^2, 96^2), large (96^2, 1e10); M = 3 max-dets values 1, 10, 100.
+ *   iou(d, g): w = min(d.x1, g.x1) - max(d.x0, g.x0), h likewise; 0 if w <= 0 or h <= 0; else i = w * h and
+ *     i / ((d.x1 - d.x0) * (d.y1 - d.y0) + (g.x1 - g.x0) * (g.y1 - g.y0) - i).  No +1.
+ *   area = (x1 - x0) * (y1 - y0) * area_scale[image]; a box is outside a range when area < lo or area > hi.
+ *   matching, per (image, class, area range, threshold t): the group's detections by descending score, ties in arena order,
+ *     the first 100; the objects of the class in ground-truth order, one ignored when its area is outside the range.  Per
+ *     detection in order: best = min(t, 1 - 1e-10), m = none; walk the objects that are not ignored and not yet taken: an
+ *     object with iou < best is skipped, else best = iou and m = it (an IoU equal to the threshold matches; among equal IoUs
+ *     the later object wins); only if that found nothing, walk the ignored, not yet taken objects by the same rule.  A match
+ *     takes its object at this (t, range); the detection is ignored iff its object is.  An unmatched detection is ignored iff
+ *     its own area is outside the range.
+ *   accumulation, per (class k, range a, max-dets M): the detections of every group's first M, by score descending, image
+ *     index ascending, in-group rank ascending.  npig = the class's objects that are not ignored; npig == 0 leaves every entry
+ *     -1.  Per threshold, with running counts tp (matched, not ignored) and fp (not matched, not ignored): rc = tp / npig,
+ *     pr = tp / (fp + tp + 2.220446049250313e-16); recall[t,k,a,M] = the last rc (0 without detections); pr is replaced by its
+ *     running maximum from the right; precision[t,r,k,a,M] = pr at the first position with rc >= rec_thrs[r], 0 if none.
+ *   the twelve numbers, each the mean over the entries > -1 of a slice, -1 when there are none: AP, AP50 (t = 0), AP75
+ *     (t = 5), APs, APm, APl over precision[:, :, :, a, M=100]; AR@1, AR@10, AR@100 over recall[:, :, all, M]; ARs, ARm,
+ *     ARl over recall[:, :, a, M=100].  per_class[k] is the same over class k alone.
+ *
+ * y3_coco_match: order[r] = the arena row of rank r, the rows sorted by (image ascending, label ascending, score descending,
+ *   row ascending); the first *n_rows_dev ranks are detections (NULL: all `rows`).  Ground truth as y3_voc_match takes it;
+ *   area_scale f64 [num_images] or NULL (1.0); iou_thrs_host: a HOST array of ten doubles.  Per rank r it writes
+ *   matched[r] and ignored[r], uint64 words whose bit t * 4 + a is the detection's verdict at threshold t and area range a,
+ *   and group_rank[r], the detection's rank inside its (image, class) group saturating at 255; ranks >= 100 are not matched
+ *   (both words 0) and never counted.  npig int32 [class_num][4]: the objects per class inside each area range (integer
+ *   atomics).  One wavefront per group; "object taken" words live in the LDS for images of up to y3_coco_lds_objects()
+ *   objects, else in the scratch.  scratch: y3_coco_match_scratch_bytes(rows, num_gt).
+ * y3_coco_ap: order2[i] = a rank, the ranks sorted by (label ascending, score descending, image ascending, rank ascending);
+ *   rec_thrs_host: a HOST array of 101 doubles.  Writes precision f64 [10][101][class_num][4][3] and recall f64
+ *   [10][class_num][4][3].  One workgroup per (class, range, max-dets, threshold) visits its class's segment in passes of
+ *   y3_coco_ap_pass() ranks; all counts are integers.  scratch: y3_coco_ap_scratch_bytes(rows).
+ * y3_coco_summary: per_class f64 [class_num][12] and stats f64 [12] (the mean over the classes where the number is defined:
+ *   every such class has the same number of entries), summed in a fixed order: the same bits in every run, within n * 2^-52
+ *   of numpy's mean over the n entries.
+ * Y3_EINVAL before any launch: a null pointer, a non-positive size, a scratch too small, a misaligned pointer, an index
+ * product (num_images * class_num, 12120 * class_num) beyond 2^31 - 1. */
+size_t y3_coco_match_scratch_bytes(int rows, int num_gt);
+int y3_coco_match(y3_ctx* ctx, const double* arena_box, const int32_t* arena_label, const int32_t* arena_image,
+                  const int32_t* order, int rows, const int32_t* n_rows_dev, const int32_t* gt_start, const double* gt_box,
+                  const int32_t* gt_label, const double* area_scale, int num_images, int num_gt, int class_num,
+                  const double* iou_thrs_host, void* scratch, size_t scratch_bytes, uint64_t* matched, uint64_t* ignored,
+                  uint8_t* group_rank, int32_t* npig);
+int y3_coco_ap_pass(void);
+int y3_coco_lds_objects(void);
+size_t y3_coco_ap_scratch_bytes(int rows);
+int y3_coco_ap(y3_ctx* ctx, const uint64_t* matched, const uint64_t* ignored, const uint8_t* group_rank,
+               const int32_t* arena_label, const int32_t* order, const int32_t* order2, int rows, const int32_t* n_rows_dev,
+               const int32_t* npig, int class_num, const double* rec_thrs_host, void* scratch, size_t scratch_bytes,
+               double* precision, double* recall);
+int y3_coco_summary(y3_ctx* ctx, const double* precision, const double* recall, int class_num, double* per_class,
+                    double* stats);
+
 /* Recall / precision counts of one training batch on the device: utils/eval_utils.py:142-232 (`evaluate_on_gpu`), as
  * restated in yolov3_tensorflow_amd/utils/eval_utils.py:53-99, on the tensors y3_nms leaves in HBM (out_boxes f32
  * [n][cap][4], out_labels int32 [n][cap], out_counts int32 [n]) and the three y_true tensors of the batch

@@ -109,6 +109,9 @@ def build_parser():
     p.add_argument('--use_voc_07_metric', type=_bool, default=False)
     p.add_argument('--map_on_device', type=_bool, default=False,
                    help='validation: match detections and compute AP on the device (eval_utils.DeviceEval)')
+    p.add_argument('--coco_metric', type=_bool, default=False,
+                   help='validation: also report the twelve COCO numbers (eval_utils.coco_eval; on the device with '
+                        '--map_on_device true)')
     p.add_argument('--batch_eval_on_device', type=_bool, default=False,
                    help='training-batch recall / precision: NMS, matching and counts for the whole batch on the device '
                         '(eval_utils.evaluate_on_device)')
@@ -187,6 +190,10 @@ def validate(model, y3, args, lines):
                                                                           ap_total.average)
     info += 'EVAL: loss: total: {:.2f}, xy: {:.2f}, wh: {:.2f}, conf: {:.2f}, class: {:.2f}\n'.format(
         *[m.average for m in meters])
+    if getattr(args, 'coco_metric', False):
+        area_scale = eval_utils.parse_gt_area_scale(args.val_file, args.img_size, args.letterbox_resize)
+        coco = device_eval.finish_coco(area_scale) if on_device else eval_utils.coco_eval(gt, val_preds, args.class_num, area_scale)
+        info += ''.join('EVAL: ' + line + '\n' for line in eval_utils.coco_summary_lines(coco['stats']))
     return ap_total.average, rec_total.average, prec_total.average, [m.average for m in meters], info
 
 

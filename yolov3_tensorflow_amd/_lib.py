@@ -193,6 +193,16 @@ PROTOTYPES = {
     "y3_voc_ap_scratch_bytes": (c_size_t, [c_int]),
     "y3_voc_ap": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p,
                           c_size_t, c_void_p]),
+    "y3_coco_match_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "y3_coco_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+    "y3_coco_ap_pass": (c_int, []),
+    "y3_coco_lds_objects": (c_int, []),
+    "y3_coco_ap_scratch_bytes": (c_size_t, [c_int]),
+    "y3_coco_ap": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                           POINTER(c_double), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "y3_coco_summary": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "y3_batch_eval_scratch_bytes": (c_size_t, [c_int, c_int]),
     "y3_batch_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                               c_int, c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),

@@ -38,6 +38,7 @@ SOURCES = [
     ("y3_jpeg.hip", []),
     ("y3_voc.hip", ["-ffp-contract=off"]),
     ("y3_beval.hip", ["-ffp-contract=off"]),
+    ("y3_coco.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -99,6 +100,7 @@ def needs_build():
         os.path.join(CSRC, "y3_jpeg_px.h"),
         os.path.join(CSRC, "y3_voc_px.h"),
         os.path.join(CSRC, "y3_beval_px.h"),
+        os.path.join(CSRC, "y3_coco_px.h"),
         os.path.join(HERE, "..", "include", "yolo355_jpeg.h"),
         os.path.join(HERE, "..", "include", "yolo355_feed.h"),
         os.path.join(HERE, "..", "include", "yolo355.h"),

@@ -9,6 +9,7 @@ SURVEY.md §8(f) row 2.  Same function names, argument order and return values a
   get_preds_gpu       utils/eval_utils.py:235-261   [[image_id, x_min, y_min, x_max, y_max, score, label], ...]
   parse_gt_rec        utils/eval_utils.py:264-307   annotation file -> {img_id: [[x0, y0, x1, y1, label], ...]}
   voc_ap, voc_eval    utils/eval_utils.py:312-423   PASCAL VOC AP (area and 11-point) per class
+  coco_eval           (beyond the reference)        COCO bbox metrics: AP@[.50:.95], AP50, AP75, AP / AR by size, AR@1/10/100
 
 plus `get_preds_batch`, the MI355X-first form: N images per call, detections produced by `yolov3.detect`
 (forward -> decode -> batched per-class NMS on the device, one host transfer per batch instead of two
@@ -330,6 +331,170 @@ def voc_eval(gt_dict, val_preds, classidx, iou_thres=0.5, use_07_metric=False):
     return npos, nd, tp[-1] / float(npos), tp[-1] / float(nd), ap
 
 
+COCO_IOU_THRS = np.linspace(.5, .95, 10)          # (the ninth is 0.8999999999999999: the kernels take them from here)
+COCO_REC_THRS = np.linspace(0., 1., 101)
+COCO_AREA_RANGES = ((0., 1e10), (0., 32. ** 2), (32. ** 2, 96. ** 2), (96. ** 2, 1e10))      # all, small, medium, large
+COCO_MAX_DETS = (1, 10, 100)
+COCO_STAT_NAMES = ('AP', 'AP50', 'AP75', 'APs', 'APm', 'APl', 'AR1', 'AR10', 'AR100', 'ARs', 'ARm', 'ARl')
+
+
+def parse_gt_area_scale(gt_filename, target_img_size, letterbox_resize=True):
+    """{img_id: 1 / (sx * sy)} for parse_gt_rec's mapping of the same annotation lines: the factor that turns an area in the
+    network-input frame back into original pixels, so that coco_eval's small / medium / large are COCO's."""
+    new_width, new_height = target_img_size
+    out = {}
+    with open(gt_filename, 'r') as f:
+        for line in f:
+            img_id, _, _, _, ori_width, ori_height = parse_line(line)
+            if letterbox_resize:
+                sx = sy = min(new_width / ori_width, new_height / ori_height)
+            else:
+                sx, sy = new_width / ori_width, new_height / ori_height
+            out[img_id] = 1. / (sx * sy)
+    return out
+
+
+def _coco_mean(values):
+    values = np.asarray(values, np.float64)
+    values = values[values > -1]
+    return float(np.mean(values)) if values.size else -1.
+
+
+def _coco_twelve(precision, recall):
+    """The twelve numbers of precision [T,R,K',A,M] / recall [T,K',A,M] (K' = all classes, or one)."""
+    out = [_coco_mean(precision[:, :, :, 0, 2]), _coco_mean(precision[0, :, :, 0, 2]), _coco_mean(precision[5, :, :, 0, 2])]
+    out += [_coco_mean(precision[:, :, :, a, 2]) for a in (1, 2, 3)]
+    out += [_coco_mean(recall[:, :, 0, m]) for m in (0, 1, 2)]
+    out += [_coco_mean(recall[:, :, a, 2]) for a in (1, 2, 3)]
+    return np.array(out, np.float64)
+
+
+def coco_eval(gt_dict, val_preds, class_num, area_scale=None):
+    """
+    COCO bbox evaluation (the COCOeval rule, no crowd objects: the annotation format has none) of all classes.
+    gt_dict: parse_gt_rec's dict, whose order is the image order; val_preds: rows of get_preds_batch over the whole set;
+    area_scale: {img_id: factor} an object's or detection's area is multiplied by before the area-range test
+    (parse_gt_area_scale; default 1.0).
+    returns {'precision': f64 [10, 101, K, 4, 3], 'recall': f64 [10, K, 4, 3], 'stats': f64 [12], 'per_class': f64 [K, 12]}
+    (IoU threshold, recall threshold, class, area range all/small/medium/large, max-dets 1/10/100); stats and per_class are
+    COCO_STAT_NAMES, -1 where nothing is defined.  The rule is written out in include/yolo355.h (y3_coco_match).
+    """
+    K, T, R, A, M = int(class_num), len(COCO_IOU_THRS), len(COCO_REC_THRS), len(COCO_AREA_RANGES), len(COCO_MAX_DETS)
+    eps = np.spacing(1)
+    image_ids = list(gt_dict)
+    index = {img_id: i for i, img_id in enumerate(image_ids)}
+    scale = np.array([1. if area_scale is None else float(area_scale[i]) for i in image_ids], np.float64)
+
+    def outside(boxes, factor):      # [n, A] bool: the area is outside the range
+        ar = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]) * factor
+        return np.stack([(ar < lo) | (ar > hi) for lo, hi in COCO_AREA_RANGES], axis=1).reshape(-1, A)
+
+    # objects per (image, class) in ground-truth order, and the objects inside each range per class
+    gts, npig = {}, np.zeros((K, A), np.int64)
+    for img_id, objs in gt_dict.items():
+        for o in objs:
+            gts.setdefault((index[img_id], int(o[-1])), []).append([float(v) for v in o[:4]])
+    for (im, k), boxes in gts.items():
+        gts[(im, k)] = boxes = np.array(boxes, np.float64).reshape(-1, 4)
+        if 0 <= k < K:
+            npig[k] += (~outside(boxes, scale[im])).sum(axis=0)
+
+    # detections by (image, label, score descending, arrival)
+    P = len(val_preds)
+    d_img = np.array([index[p[0]] for p in val_preds], np.int64).reshape(P)
+    d_box = np.array([[float(v) for v in p[1:5]] for p in val_preds], np.float64).reshape(P, 4)
+    d_score = np.array([float(p[5]) for p in val_preds], np.float64).reshape(P)
+    d_label = np.array([int(p[6]) for p in val_preds], np.int64).reshape(P)
+    order = np.lexsort((np.arange(P), -d_score, d_label, d_img))
+    d_img, d_box, d_score, d_label = d_img[order], d_box[order], d_score[order], d_label[order]
+    key = d_img * max(K, 1) + d_label
+    heads = np.flatnonzero(np.concatenate(([True], key[1:] != key[:-1]))) if P else np.zeros(0, np.int64)
+    ends = np.concatenate((heads[1:], [P])).astype(np.int64)
+    grank = np.zeros(P, np.int64)
+    matched = np.zeros((P, T, A), bool)
+    ignored = np.zeros((P, T, A), bool)
+    for h, e in zip(heads, ends):
+        grank[h:e] = np.arange(e - h)
+        D = min(e - h, COCO_MAX_DETS[-1])
+        im, k = int(d_img[h]), int(d_label[h])
+        det = d_box[h:h + D]
+        d_out = outside(det, scale[im])
+        g = gts.get((im, k))
+        if g is None:
+            ignored[h:h + D] = d_out[:, None, :]
+            continue
+        G = len(g)
+        w = np.minimum(det[:, None, 2], g[None, :, 2]) - np.maximum(det[:, None, 0], g[None, :, 0])
+        hh = np.minimum(det[:, None, 3], g[None, :, 3]) - np.maximum(det[:, None, 1], g[None, :, 1])
+        inter = w * hh
+        with np.errstate(all='ignore'):
+            ious = inter / (((det[:, 2] - det[:, 0]) * (det[:, 3] - det[:, 1]))[:, None]
+                            + ((g[:, 2] - g[:, 0]) * (g[:, 3] - g[:, 1]))[None, :] - inter)
+        ious = np.where((w <= 0.) | (hh <= 0.), 0., ious).tolist()
+        g_out = outside(g, scale[im])
+        for a in range(A):
+            g_ig = g_out[:, a].tolist()
+            for ti, t in enumerate(COCO_IOU_THRS):
+                taken = [False] * G
+                floor = min(float(t), 1 - 1e-10)
+                for d in range(D):
+                    row, best, m = ious[d], floor, -1
+                    for j in range(G):                  # the objects that count
+                        if g_ig[j] or taken[j] or row[j] < best:
+                            continue
+                        best, m = row[j], j
+                    if m < 0:
+                        for j in range(G):              # only then the ignored ones
+                            if not g_ig[j] or taken[j] or row[j] < best:
+                                continue
+                            best, m = row[j], j
+                    if m >= 0:
+                        taken[m] = True
+                        matched[h + d, ti, a] = True
+                        ignored[h + d, ti, a] = g_ig[m]
+                    else:
+                        ignored[h + d, ti, a] = d_out[d, a]
+
+    precision = -np.ones((T, R, K, A, M), np.float64)
+    recall = -np.ones((T, K, A, M), np.float64)
+    for k in range(K):
+        of_class = np.flatnonzero(d_label == k)          # image ascending, in-group rank ascending
+        for mi, max_det in enumerate(COCO_MAX_DETS):
+            sel = of_class[grank[of_class] < max_det]
+            sel = sel[np.argsort(-d_score[sel], kind='mergesort')]
+            for a in range(A):
+                if npig[k, a] == 0:
+                    continue
+                dm, dig = matched[sel][:, :, a], ignored[sel][:, :, a]
+                tps = np.cumsum(dm & ~dig, axis=0).astype(np.float64)
+                fps = np.cumsum(~dm & ~dig, axis=0).astype(np.float64)
+                for ti in range(T):
+                    tp, fp = tps[:, ti], fps[:, ti]
+                    nd = len(tp)
+                    rc = tp / npig[k, a]
+                    pr = tp / (fp + tp + eps)
+                    recall[ti, k, a, mi] = rc[-1] if nd else 0.
+                    pr = np.maximum.accumulate(pr[::-1])[::-1]
+                    at = np.searchsorted(rc, COCO_REC_THRS, side='left')
+                    q = np.zeros(R)
+                    q[at < nd] = pr[at[at < nd]]
+                    precision[ti, :, k, a, mi] = q
+    per_class = np.stack([_coco_twelve(precision[:, :, k:k + 1], recall[:, k:k + 1]) for k in range(K)]).reshape(K, 12)
+    return {'precision': precision, 'recall': recall, 'stats': _coco_twelve(precision, recall), 'per_class': per_class}
+
+
+def coco_summary_lines(stats):
+    """The twelve report lines of coco_eval's / DeviceEval.finish_coco's `stats`, in COCOeval's layout."""
+    rows = [('Average Precision', '(AP)', '0.50:0.95', 'all', 100), ('Average Precision', '(AP)', '0.50', 'all', 100),
+            ('Average Precision', '(AP)', '0.75', 'all', 100), ('Average Precision', '(AP)', '0.50:0.95', 'small', 100),
+            ('Average Precision', '(AP)', '0.50:0.95', 'medium', 100), ('Average Precision', '(AP)', '0.50:0.95', 'large', 100),
+            ('Average Recall', '(AR)', '0.50:0.95', 'all', 1), ('Average Recall', '(AR)', '0.50:0.95', 'all', 10),
+            ('Average Recall', '(AR)', '0.50:0.95', 'all', 100), ('Average Recall', '(AR)', '0.50:0.95', 'small', 100),
+            ('Average Recall', '(AR)', '0.50:0.95', 'medium', 100), ('Average Recall', '(AR)', '0.50:0.95', 'large', 100)]
+    return ['{:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'.format(title, kind, iou, area, dets, float(v))
+            for (title, kind, iou, area, dets), v in zip(rows, stats)]
+
+
 class DeviceEval(object):
     """voc_eval for every class at once on the device (y3_voc_append / y3_voc_match / y3_voc_ap, include/yolo355.h):
     the detections stay where the NMS kernels left them, and one [class_num, 5] table comes back.
@@ -337,6 +502,7 @@ class DeviceEval(object):
         ev = DeviceEval(gt_dict, image_ids, class_num)
         ev.add(batch_image_ids, gpu_nms_batched(..., lazy=True))      # per batch; nothing waits for the host
         table = ev.finish(iou_thres=0.5, use_07_metric=False)         # rows (npos, nd, recall, precision, ap)
+        coco = ev.finish_coco(area_scale)                             # coco_eval's 'stats' and 'per_class' (either order)
 
     A row of the table is what voc_eval(gt_dict, val_preds, c, iou_thres, use_07_metric) returns for the rows
     get_preds_batch would have built, with two differences in the last bits' provenance:
@@ -467,3 +633,63 @@ class DeviceEval(object):
             raise _lib.Y3Error("DeviceEval: %d detections did not fit the arena's %d rows (%d kept): raise capacity_rows" % (
                 lost, R, rows))
         return table[:C].copy()
+
+    def finish_coco(self, area_scale=None, return_curves=False):
+        """coco_eval's numbers for the rows in the arena (y3_coco_match / y3_coco_ap / y3_coco_summary, include/yolo355.h):
+        {'stats': f64 [12], 'per_class': f64 [class_num, 12]}, and with return_curves also 'precision' [10, 101, class_num, 4, 3]
+        and 'recall' [10, class_num, 4, 3].  area_scale: {img_id: factor} as coco_eval takes it (default 1.0).  precision and
+        recall are coco_eval's float64 values bit for bit (its image order = this evaluator's image_ids order); stats and
+        per_class are summed in a fixed order of their own, within n * 2**-52 of numpy's mean over n entries, and are the same
+        bits in every run.  One device -> host copy (the numbers with the arena's two counters behind them); raises Y3Error when
+        rows were dropped for lack of capacity.  `finish` and `finish_coco` read the arena and leave it as it is."""
+        import ctypes
+        import torch
+        from .. import _lib, framework as fw
+        L, ctx, dev, R, C = _lib.lib(), fw.context(self._dev), self._dev, self.capacity_rows, self.class_num
+        N = len(self._index)
+        box, score, label, image = self._arena
+        # plumbing: stable sorts, the last key first.  order: (image, label, score descending, row); the rows past the arena's
+        # count take the image N and the label C and so rank behind every detection.  order2 sorts the RANKS of order by
+        # (label, score descending): equal keys keep (image, in-group rank) ascending.  Negating a float64 is exact.
+        live = torch.arange(R, device=dev, dtype=torch.int32) < self._state[0]
+        by_score = torch.sort(-score, stable=True).indices
+        by_label = by_score[torch.sort(torch.where(live, label, torch.full_like(label, C))[by_score], stable=True).indices]
+        order64 = by_label[torch.sort(torch.where(live, image, torch.full_like(image, N))[by_label], stable=True).indices]
+        order = order64.to(torch.int32).contiguous()
+        rank_score = torch.sort(-score[order64], stable=True).indices
+        rank_label = torch.where(live, label[order64], torch.full_like(label, C))      # (the live ranks are the first ones)
+        order2 = rank_score[torch.sort(rank_label[rank_score], stable=True).indices].to(torch.int32).contiguous()
+        scale = None
+        if area_scale is not None:
+            by_index = sorted(self._index, key=self._index.get)
+            scale = torch.from_numpy(np.array([float(area_scale[i]) for i in by_index], np.float64)).to(dev)
+        m_bytes, a_bytes = L.y3_coco_match_scratch_bytes(R, self.num_gt), L.y3_coco_ap_scratch_bytes(R)
+        scratch = torch.empty(max(m_bytes, a_bytes), dtype=torch.uint8, device=dev)
+        words = torch.empty((2, R), dtype=torch.int64, device=dev)
+        grank = torch.empty(R, dtype=torch.uint8, device=dev)
+        npig = torch.empty((C, 4), dtype=torch.int32, device=dev)
+        head, n_prec, n_rec = 12 + 12 * C + 2, 10 * 101 * C * 4 * 3, 10 * C * 4 * 3
+        out = torch.zeros(head + n_prec + n_rec, dtype=torch.float64, device=dev)
+        stats, per_class, precision, recall = out[:12], out[12:12 + 12 * C], out[head:head + n_prec], out[head + n_prec:]
+        iou_thrs = (ctypes.c_double * 10)(*COCO_IOU_THRS)
+        rec_thrs = (ctypes.c_double * 101)(*COCO_REC_THRS)
+        _lib.check(L.y3_coco_match(ctx, fw.ptr(box), fw.ptr(label), fw.ptr(image), fw.ptr(order), R, fw.ptr(self._state),
+                                   fw.ptr(self._gt_start), fw.ptr(self._gt_box), fw.ptr(self._gt_label),
+                                   fw.ptr(scale) if scale is not None else None, N, self.num_gt, C, iou_thrs, fw.ptr(scratch),
+                                   ctypes.c_size_t(m_bytes), fw.ptr(words[0]), fw.ptr(words[1]), fw.ptr(grank), fw.ptr(npig)))
+        _lib.check(L.y3_coco_ap(ctx, fw.ptr(words[0]), fw.ptr(words[1]), fw.ptr(grank), fw.ptr(label), fw.ptr(order), fw.ptr(order2),
+                                R, fw.ptr(self._state), fw.ptr(npig), C, rec_thrs, fw.ptr(scratch), ctypes.c_size_t(a_bytes),
+                                fw.ptr(precision), fw.ptr(recall)))
+        _lib.check(L.y3_coco_summary(ctx, fw.ptr(precision), fw.ptr(recall), C, fw.ptr(per_class), fw.ptr(stats)))
+        out[head - 2:head] = self._state.to(torch.float64)
+        host = (out if return_curves else out[:head]).cpu().numpy()
+        fw.check_context(dev)
+        rows, lost = int(host[head - 2]), int(host[head - 1])
+        if lost:
+            raise _lib.Y3Error("DeviceEval: %d detections did not fit the arena's %d rows (%d kept): raise capacity_rows" % (
+                lost, R, rows))
+        result = {'stats': host[:12].copy(), 'per_class': host[12:12 + 12 * C].reshape(C, 12).copy()}
+        if return_curves:
+            result['precision'] = host[head:head + n_prec].reshape(10, 101, C, 4, 3).copy()
+            result['recall'] = host[head + n_prec:].reshape(10, C, 4, 3).copy()
+        return result
