@@ -44,6 +44,7 @@ def test_abi_version_5_and_pure_host_entry_points(lib):
     # workspace sizing is host-only arithmetic
     assert lib.y3_nms_workspace_bytes(1, 10647, 80, 200) > 80 * 10647 * 4
     assert lib.y3_nms_workspace_bytes(0, 10647, 80, 200) == 0
+    assert lib.y3_nms_workspace_bytes(2, 1000, 3, 20) == 25088 and lib.y3_nms_workspace_bytes(1, 10647, 80, 200) == 3472128
     assert lib.y3_net_num_layers(None) == 0
 
 

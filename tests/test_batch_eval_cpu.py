@@ -63,6 +63,7 @@ def test_scratch_bytes_and_validation_before_launching():
     size = L.y3_batch_eval_scratch_bytes
     assert size(0, 8) == 0 and size(8, 0) == 0 and size(-1, 8) == 0 and size(8, -3) == 0
     assert size(1, 1) >= 32 + 4 + 4 + 4
+    assert size(2, 100) == 8704 and size(1, 1) == 1024 and size(5, 70) == 14592 and size(64, 4096) == 10486016
     for n, g in ((1, 1), (5, 70), (64, 4096)):
         assert size(n, g) >= n * g * (32 + 4) + n * 4
         assert size(n + 1, g) >= size(n, g) and size(n, g + 1) >= size(n, g)

@@ -66,6 +66,8 @@ def test_host_entry_points_validate_before_launching():
     assert L.y3_coco_ap_pass() >= 256 and L.y3_coco_ap_pass() % 64 == 0 and L.y3_coco_lds_objects() >= 64
     assert L.y3_coco_match_scratch_bytes(0, 5) == 0 and L.y3_coco_match_scratch_bytes(5, -1) == 0 and L.y3_coco_ap_scratch_bytes(0) == 0
     assert L.y3_coco_match_scratch_bytes(1000, 45) >= 45 * 8 and L.y3_coco_ap_scratch_bytes(1000) >= 1000 * 21
+    assert L.y3_coco_match_scratch_bytes(1000, 45) == 512 and L.y3_coco_ap_scratch_bytes(1000) == 21504
+    assert L.y3_coco_match_scratch_bytes(7, 0) == 256
     d = ctypes.c_void_p(4096)
     thr = (ctypes.c_double * 101)(*np.linspace(0., 1., 101))
     big = 1 << 30

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import coco_cases as cc
+from device_eval_helpers import eval_script_set, nms_like
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -29,25 +30,17 @@ def _from_rows(case, spare=7, **kw):
 def _through_append(case, batch=5, cap=None, **kw):
     """The case's detections through y3_voc_append in the layout y3_nms leaves them in (slots past an image's count hold
     poison), image batches in image_ids order.  Returns the evaluator and the rows in the arena's order."""
-    import torch
+    from collections import Counter
     from yolov3_tensorflow_amd import framework as fw
     from yolov3_tensorflow_amd.utils.eval_utils import DeviceEval
-    dev = fw.default_device()
-    per_image = {k: [p for p in case.preds if p[0] == k] for k in case.image_ids}
-    cap = cap or max(1, max(len(v) for v in per_image.values()))
+    cap = cap or max([1] + list(Counter(p[0] for p in case.preds if p[0] in case.image_ids).values()))
     ev = DeviceEval(case.gt_dict, case.image_ids, case.class_num, **kw)
     rows = []
     for b0 in range(0, len(case.image_ids), batch):
         ids = case.image_ids[b0:b0 + batch]
-        n = len(ids)
-        ob, osc = np.full((n, cap, 4), np.nan, np.float32), np.full((n, cap), np.nan, np.float32)
-        ol, cnt = np.full((n, cap), -5, np.int32), np.zeros(n, np.int32)
-        for i, k in enumerate(ids):
-            for p in per_image[k]:
-                ob[i, cnt[i]], osc[i, cnt[i]], ol[i, cnt[i]] = p[1:5], p[5], p[6]
-                cnt[i] += 1
-            rows += per_image[k]
-        ev.add(ids, tuple(torch.from_numpy(x).to(dev) for x in (ob, osc, ol, cnt)))
+        dets, r = nms_like(case.preds, ids, cap, fw.default_device())
+        ev.add(ids, dets)
+        rows += r
     return ev, rows
 
 
@@ -183,41 +176,10 @@ def test_eval_script_with_and_without_coco_metric(tmp_path, capsys, isolated_gra
     """eval.py end to end on a synthetic 6-image / 5-class set with random weights: with --coco_metric true the twelve numbers of
     --map_on_device true and false agree within the bound and twelve lines follow the VOC report; with the flag off the
     output is what it is without the option."""
-    from PIL import Image
-    import torch
     import yolov3_tensorflow_amd as y3
-    from yolov3_tensorflow_amd.utils import misc_utils
     sys.path.insert(0, os.path.dirname(HERE))
     import eval as eval_script
-    rng = np.random.RandomState(5)
-    names = tmp_path / 'names.txt'
-    names.write_text('\n'.join('c%d' % i for i in range(5)) + '\n')
-    lines, obj = [], 0
-    for i in range(6):
-        w, h = int(rng.randint(120, 400)), int(rng.randint(120, 400))
-        img = (rng.rand(h // 8 + 1, w // 8 + 1, 3) * 255).astype(np.uint8).repeat(8, 0).repeat(8, 1)[:h, :w]
-        path = tmp_path / ('im%d.png' % i)
-        Image.fromarray(img).save(str(path))
-        parts = ['%d' % i, str(path), '%d' % w, '%d' % h]
-        for _ in range(int(rng.randint(2, 4))):
-            x0, y0 = rng.uniform(0, w * 0.6), rng.uniform(0, h * 0.6)
-            obj += 1
-            parts += ['%d' % (obj % 5), '%.1f' % x0, '%.1f' % y0, '%.1f' % (x0 + rng.uniform(20, w * 0.35)),
-                      '%.1f' % (y0 + rng.uniform(20, h * 0.35))]
-        lines.append(' '.join(parts))
-    ann = tmp_path / 'val.txt'
-    ann.write_text('\n'.join(lines) + '\n')
-    anchors = os.path.join(os.path.dirname(HERE), 'data', 'yolo_anchors.txt')
-    y3.reset_default_graph()
-    y3.set_init_seed(3)
-    m = y3.yolov3(5, misc_utils.parse_anchors(anchors))
-    with y3.variable_scope('yolov3'):
-        m.forward(torch.zeros(1, 64, 64, 3))
-    wfile = str(tmp_path / 'rand.weights')
-    misc_utils.save_weights(y3.global_variables(scope='yolov3'), wfile)
-    common = ['--eval_file', str(ann), '--restore_path', wfile, '--anchor_path', anchors, '--class_name_path', str(names),
-              '--img_size', '224', '160', '--letterbox_resize', 'true', '--batch_size', '4', '--score_threshold', '0.1',
-              '--nms_topk', '20']
+    common = eval_script_set(tmp_path)
     results, texts = {}, {}
     for key, extra in (('host', ['--coco_metric', 'true']), ('device', ['--coco_metric', 'true', '--map_on_device', 'true']),
                        ('off', ['--coco_metric', 'false']), ('plain', [])):

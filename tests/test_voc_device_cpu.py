@@ -60,6 +60,8 @@ def test_host_entry_points_validate_before_launching():
     assert L.y3_voc_ap_pass() >= 256 and L.y3_voc_ap_pass() % 64 == 0
     assert L.y3_voc_match_scratch_bytes(0, 5) == 0 and L.y3_voc_ap_scratch_bytes(0) == 0
     assert L.y3_voc_match_scratch_bytes(1000, 45) >= 1000 * 4 + 45 * 4 and L.y3_voc_ap_scratch_bytes(1000) >= 4000
+    assert L.y3_voc_match_scratch_bytes(1000, 45) == 4352 and L.y3_voc_ap_scratch_bytes(1000) == 4096
+    assert L.y3_voc_match_scratch_bytes(7, 0) == 512
     d = ctypes.c_void_p(4096)
     assert L.y3_voc_append(None, d, d, d, d, d, 1, 1, d, d, d, d, 1, d) == _lib.Y3_EINVAL
     assert L.y3_voc_append(d, d, d, d, d, d, 0, 1, d, d, d, d, 1, d) == _lib.Y3_EINVAL

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import voc_cases as vc
+from device_eval_helpers import eval_script_set, nms_like
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,29 +50,13 @@ def _c_entries(case, iou_thres, use_07_metric, pad_rows=5):
     return out.cpu().numpy(), tp[:n], order.cpu().numpy()[:n]
 
 
-def _nms_like(case, image_ids, cap, dev):
-    """The detections of `image_ids` in the layout y3_nms leaves them in: (boxes [n,cap,4], scores [n,cap], labels [n,cap],
-    counts [n]); slots past an image's count hold poison.  Also returns the host concatenation of the live rows."""
-    import torch
-    n = len(image_ids)
-    ob, osc = np.full((n, cap, 4), np.nan, np.float32), np.full((n, cap), np.nan, np.float32)
-    ol, cnt, rows = np.full((n, cap), -5, np.int32), np.zeros(n, np.int32), []
-    for i, img in enumerate(image_ids):
-        for p in case.preds:
-            if p[0] == img:
-                ob[i, cnt[i]], osc[i, cnt[i]], ol[i, cnt[i]] = p[1:5], p[5], p[6]
-                cnt[i] += 1
-                rows.append(p)
-    return tuple(torch.from_numpy(x).to(dev) for x in (ob, osc, ol, cnt)), rows
-
-
 def _device_eval(case, batches=None, cap=64, **kw):
     from yolov3_tensorflow_amd import framework as fw
     from yolov3_tensorflow_amd.utils.eval_utils import DeviceEval
     ev = DeviceEval(case.gt_dict, case.image_ids, case.class_num, **kw)
     rows = []
     for ids in batches or [case.image_ids[i:i + 16] for i in range(0, len(case.image_ids), 16)]:
-        dets, r = _nms_like(case, ids, cap, fw.default_device())
+        dets, r = nms_like(case.preds, ids, cap, fw.default_device())
         ev.add(ids, dets)
         rows += r
     return ev, rows
@@ -146,7 +131,7 @@ def test_append_order_gaps_and_unknown_ids():
     by_arrival = vc.Case(case.gt_dict, ids, rows, 4)
     vc.assert_table(ev.finish(), vc.reference_table(by_arrival, 0.5, False), False, 'append')
     with pytest.raises(ValueError):
-        ev.add([ids[0], 'nowhere'], _nms_like(case, ids[:2], 300, ev._dev)[0])
+        ev.add([ids[0], 'nowhere'], nms_like(case.preds, ids[:2], 300, ev._dev)[0])
     with pytest.raises(ValueError):
         DeviceEval(case.gt_dict, ids + [12345], 4)
 
@@ -247,45 +232,15 @@ def test_capacity_overflow_raises_and_writes_nothing_past_the_arena():
 def test_eval_script_with_and_without_map_on_device(tmp_path, capsys, isolated_graph):
     """eval.py end to end on a synthetic 6-image / 5-class set with random weights, host bookkeeping against
     --map_on_device true: the same per-class npos, nd, recall and precision, AP within the bound, the same printed lines."""
-    from PIL import Image
-    import torch
     import yolov3_tensorflow_amd as y3
-    from yolov3_tensorflow_amd.utils import misc_utils, eval_utils
+    from yolov3_tensorflow_amd.utils import eval_utils
     sys.path.insert(0, os.path.dirname(HERE))
     import eval as eval_script
-    rng = np.random.RandomState(5)
-    names = tmp_path / 'names.txt'
-    names.write_text('\n'.join('c%d' % i for i in range(5)) + '\n')
-    lines, obj = [], 0
-    for i in range(6):
-        w, h = int(rng.randint(120, 400)), int(rng.randint(120, 400))
-        img = (rng.rand(h // 8 + 1, w // 8 + 1, 3) * 255).astype(np.uint8).repeat(8, 0).repeat(8, 1)[:h, :w]
-        path = tmp_path / ('im%d.png' % i)
-        Image.fromarray(img).save(str(path))
-        parts = ['%d' % i, str(path), '%d' % w, '%d' % h]
-        for _ in range(int(rng.randint(2, 4))):
-            x0, y0 = rng.uniform(0, w * 0.6), rng.uniform(0, h * 0.6)
-            obj += 1
-            parts += ['%d' % (obj % 5), '%.1f' % x0, '%.1f' % y0, '%.1f' % (x0 + rng.uniform(20, w * 0.35)),
-                      '%.1f' % (y0 + rng.uniform(20, h * 0.35))]
-        lines.append(' '.join(parts))
-    ann = tmp_path / 'val.txt'
-    ann.write_text('\n'.join(lines) + '\n')
-    anchors = os.path.join(os.path.dirname(HERE), 'data', 'yolo_anchors.txt')
-    y3.reset_default_graph()
-    y3.set_init_seed(3)
-    m = y3.yolov3(5, misc_utils.parse_anchors(anchors))
-    with y3.variable_scope('yolov3'):
-        m.forward(torch.zeros(1, 64, 64, 3))
-    wfile = str(tmp_path / 'rand.weights')
-    misc_utils.save_weights(y3.global_variables(scope='yolov3'), wfile)
+    common = eval_script_set(tmp_path)
     results, texts = {}, {}
     for on_device in ('false', 'true'):
         y3.reset_default_graph()
-        results[on_device] = eval_script.main(['--eval_file', str(ann), '--restore_path', wfile, '--anchor_path', anchors,
-                                               '--class_name_path', str(names), '--img_size', '224', '160',
-                                               '--letterbox_resize', 'true', '--batch_size', '4', '--score_threshold', '0.1',
-                                               '--nms_topk', '20', '--map_on_device', on_device])
+        results[on_device] = eval_script.main(common + ['--map_on_device', on_device])
         texts[on_device] = capsys.readouterr().out
     host, device = results['false'], results['true']
     assert len(host['val_preds']) > 50 and device['val_preds'] == [] and 'table' not in host

@@ -91,16 +91,8 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s, _ in SOURCES] + [
-        os.path.join(CSRC, "y3_internal.h"),
-        os.path.join(CSRC, "y3_conv_common.h"),
-        os.path.join(CSRC, "y3_bf16.h"),
-        os.path.join(CSRC, "y3_net.h"),
-        os.path.join(CSRC, "y3_feed_px.h"),
-        os.path.join(CSRC, "y3_jpeg_px.h"),
-        os.path.join(CSRC, "y3_voc_px.h"),
-        os.path.join(CSRC, "y3_beval_px.h"),
-        os.path.join(CSRC, "y3_coco_px.h"),
+    headers = sorted(n for n in os.listdir(CSRC) if n.endswith('.h'))         # every one, as in csrc_sha16
+    deps = [os.path.join(CSRC, s) for s, _ in SOURCES] + [os.path.join(CSRC, n) for n in headers] + [
         os.path.join(HERE, "..", "include", "yolo355_jpeg.h"),
         os.path.join(HERE, "..", "include", "yolo355_feed.h"),
         os.path.join(HERE, "..", "include", "yolo355.h"),

@@ -13,17 +13,17 @@
 // Counts go to the caller's int64 table with integer atomics (through an LDS histogram in match, where a workgroup's
 // detections share few labels).  Every index read from device memory (counts, labels) is clamped to the extents the host
 // passed before it addresses anything; every loop is bounded by those extents.  The arithmetic is y3_beval_px.h's.
-#include "y3_internal.h"
+#include "y3_eval_common.h"
 #include "y3_beval_px.h"
 
 namespace {
+
+using namespace y3ev;
 
 constexpr int kPass = 1024;         // cells per pass of the gather = its workgroup size
 constexpr int kWave = 64;
 constexpr int kThreads = 256;       // match and tally
 constexpr int kHist = 1024;         // labels below this are counted in LDS first
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct Scales {
     const float* y[3];
@@ -155,16 +155,21 @@ __global__ __launch_bounds__(kThreads) void beval_tally_kernel(int class_num, in
     if (gt_found[at] != 0) atomicAdd(&table[3 * (size_t)label + 0], 1ull);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// y3_batch_eval's scratch: gt_box f64 [n][gt_cap][4] | gt_label i32 [n][gt_cap] | found i32 [n][gt_cap] | gt_count i32 [n]
+struct Scratch {
+    Carve at;
+    int n, gt_cap;
+    size_t slots = (size_t)n * gt_cap;
+    double* gt_box = at.take<double>(4 * slots);
+    int32_t* gt_label = at.take<int32_t>(slots);
+    int32_t* gt_found = at.take<int32_t>(slots);
+    int32_t* gt_count = at.take<int32_t>(n);
+};
 
 }  // namespace
 
-// scratch: gt_box f64 [n][gt_cap][4] | gt_label i32 [n][gt_cap] | found i32 [n][gt_cap] | gt_count i32 [n]
 extern "C" size_t y3_batch_eval_scratch_bytes(int n, int gt_cap) {
-    if (n <= 0 || gt_cap <= 0) return 0;
-    const size_t slots = (size_t)n * gt_cap;
-    return align256(slots * 32) + 2 * align256(slots * 4) + align256((size_t)n * 4);
+    return n > 0 && gt_cap > 0 ? Scratch{nullptr, n, gt_cap}.at.bytes() : 0;
 }
 
 extern "C" int y3_batch_eval(y3_ctx* ctx, const float* out_boxes, const int32_t* out_labels, const int32_t* out_counts, int n,
@@ -193,25 +198,20 @@ extern "C" int y3_batch_eval(y3_ctx* ctx, const float* out_boxes, const int32_t*
     Y3_CHECK_ARG(aligned(scratch, 8) && aligned(table, 8) && aligned(out_labels, 4) && aligned(out_counts, 4) &&
                      aligned(y_true_1, 4) && aligned(y_true_2, 4) && aligned(y_true_3, 4) && aligned(state, 4),
                  "y3_batch_eval: misaligned pointer");
-    const size_t slots = (size_t)n * gt_cap;
-    char* p = static_cast<char*>(scratch);
-    double* gt_box = reinterpret_cast<double*>(p);
-    int32_t* gt_label = reinterpret_cast<int32_t*>(p + align256(slots * 32));
-    int32_t* gt_found = reinterpret_cast<int32_t*>(p + align256(slots * 32) + align256(slots * 4));
-    int32_t* gt_count = reinterpret_cast<int32_t*>(p + align256(slots * 32) + 2 * align256(slots * 4));
+    const Scratch ws{scratch, n, gt_cap};
     Scales sc;
     sc.y[0] = y_true_1, sc.y[1] = y_true_2, sc.y[2] = y_true_3;
     sc.cells[0] = 3 * (h / 32) * (w / 32), sc.cells[1] = 3 * (h / 16) * (w / 16), sc.cells[2] = 3 * (h / 8) * (w / 8);
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(table);
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(beval_gather_kernel, dim3(n), dim3(kPass), 0, st, sc, (int)channels, class_num, gt_cap, gt_box, gt_label,
-                       gt_found, gt_count, state);
+    hipLaunchKernelGGL(beval_gather_kernel, dim3(n), dim3(kPass), 0, st, sc, (int)channels, class_num, gt_cap, ws.gt_box,
+                       ws.gt_label, ws.gt_found, ws.gt_count, state);
     Y3_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(beval_match_kernel, dim3((cap + kThreads - 1) / kThreads, n), dim3(kThreads), 0, st, out_boxes, out_labels,
-                       out_counts, cap, class_num, iou_thresh, gt_cap, gt_box, gt_label, gt_found, gt_count, counts);
+                       out_counts, cap, class_num, iou_thresh, gt_cap, ws.gt_box, ws.gt_label, ws.gt_found, ws.gt_count, counts);
     Y3_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(beval_tally_kernel, dim3((gt_cap + kThreads - 1) / kThreads, n), dim3(kThreads), 0, st, class_num, gt_cap,
-                       gt_label, gt_found, gt_count, counts);
+                       ws.gt_label, ws.gt_found, ws.gt_count, counts);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }

@@ -18,11 +18,12 @@
 // No floating-point atomics, no hand-off between workgroups inside a kernel: stages that depend on each other are launches
 // on the one stream.  Every index read from device memory is clamped to the extents the host passed before it addresses
 // anything; every loop is bounded by those extents.  The arithmetic is y3_coco_px.h's.
-#include "y3_internal.h"
+#include "y3_eval_common.h"
 #include "y3_coco_px.h"
 
 namespace {
 
+using namespace y3ev;
 using namespace y3cpx;
 typedef unsigned long long u64;
 
@@ -38,12 +39,6 @@ struct IouThrs {
 struct RecThrs {
     double r[kRecThrs];
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int ranked_total(const int32_t* n_rows_dev, int rows) {
-    return n_rows_dev ? clampi(*n_rows_dev, 0, rows) : rows;
-}
 
 // lanes of one wave exchange data through the LDS: order the accesses for the compiler (the hardware runs a wave's LDS
 // instructions in order)
@@ -227,54 +222,6 @@ __global__ __launch_bounds__(kThreads) void coco_gather_kernel(const u64* __rest
     lab2[i] = clampi(label[clampi(order[r], 0, rows - 1)], 0, class_num - 1);
 }
 
-// exclusive prefix sum of one word per thread in thread order; *total = the block's sum
-__device__ u64 block_excl_sum(u64 v, u64* sh, u64* total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-        const u64 t = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const u64 incl = sh[tid];
-    *total = sh[kThreads - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// max over the threads to the right of this one (0. for the last), values >= 0; *all = the block's max
-__device__ double block_right_max(double v, double* sh, double* all) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-        const double t = tid + off < kThreads ? sh[tid + off] : 0.;
-        __syncthreads();
-        sh[tid] = dmax(sh[tid], t);
-        __syncthreads();
-    }
-    const double right = tid + 1 < kThreads ? sh[tid + 1] : 0.;
-    *all = sh[0];
-    __syncthreads();
-    return right;
-}
-
-// the block's sum by a fixed tree; the result in every thread
-__device__ double block_sum(double v, double* sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
-        __syncthreads();
-    }
-    const double out = sh[0];
-    __syncthreads();
-    return out;
-}
-
 // (true positive << 32) | false positive of one position at bit `bit`, among a group's first `max_dets`
 __device__ __forceinline__ u64 tp_fp(u64 mw, u64 iw, int grank, int bit, int max_dets) {
     if (grank >= max_dets || ((iw >> bit) & 1ull)) return 0;
@@ -321,7 +268,7 @@ __global__ __launch_bounds__(kThreads) void coco_ap_kernel(const u64* __restrict
     u64 part = 0;
     for (int i = tid; i < nd; i += kThreads) part += tp_fp(mw[i], iw[i], gr[i], bit, max_dets);
     u64 after;      // the counts behind the positions still to visit
-    block_excl_sum(part, s_u64, &after);
+    block_excl_sum<kThreads>(part, s_u64, &after);
     const int tp_all = (int)(after >> 32);
     if (tid == 0) recall[recall_index(t, k, a, m, class_num)] = recall_at(tp_all, np);
     // thresholds no position reaches: 0.
@@ -338,7 +285,7 @@ __global__ __launch_bounds__(kThreads) void coco_ap_kernel(const u64* __restrict
             sum += v[j];
         }
         u64 pass_total;
-        const u64 excl = block_excl_sum(sum, s_u64, &pass_total);
+        const u64 excl = block_excl_sum<kThreads>(sum, s_u64, &pass_total);
         const u64 before = after - pass_total;
         u64 run = before + excl;
         int tp_before = (int)(run >> 32), tp[kItems];
@@ -350,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void coco_ap_kernel(const u64* __restrict
             tmax = dmax(tmax, prec[j]);
         }
         double pass_max;
-        double env = dmax(env_right, block_right_max(tmax, s_dbl, &pass_max));
+        double env = dmax(env_right, block_right_max<kThreads>(tmax, s_dbl, &pass_max));
         double envs[kItems];
         for (int j = kItems - 1; j >= 0; --j) {
             env = dmax(env, prec[j]);
@@ -371,7 +318,24 @@ __global__ __launch_bounds__(kThreads) void coco_ap_kernel(const u64* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ summary
-// block k: per_class[k][0..12); a number is the mean of its slice's entries > -1, or -1 without any
+// the mean of the entries > -1 among value(0) .. value(n - 1), or -1 without any: every thread adds its strided share in
+// ascending order, the threads' sums meet in the fixed tree; the result in every thread
+template <class Value>
+__device__ double defined_mean(int n, Value value, double* sh) {
+    double sum = 0., cnt = 0.;
+    for (int i = threadIdx.x; i < n; i += kThreads) {
+        const double v = value(i);
+        if (v > -1.) {
+            sum = sum + v;
+            cnt = cnt + 1.;
+        }
+    }
+    sum = block_sum<kThreads>(sum, sh);
+    cnt = block_sum<kThreads>(cnt, sh);
+    return cnt > 0. ? sum / cnt : -1.;
+}
+
+// block k: per_class[k][0..12), each the defined_mean of its slice
 __global__ __launch_bounds__(kThreads) void coco_class_summary_kernel(const double* __restrict__ precision,
                                                                       const double* __restrict__ recall, int class_num,
                                                                       double* __restrict__ per_class) {
@@ -380,46 +344,45 @@ __global__ __launch_bounds__(kThreads) void coco_class_summary_kernel(const doub
     for (int j = 0; j < 12; ++j) {
         int t0, t1, a, m;
         stat_slice(j, &t0, &t1, &a, &m);
-        const int per_t = j < 6 ? kRecThrs : 1, n = (t1 - t0) * per_t;
-        double sum = 0., cnt = 0.;
-        for (int i = tid; i < n; i += kThreads) {
+        const int per_t = j < 6 ? kRecThrs : 1;
+        const double mean = defined_mean((t1 - t0) * per_t, [&](int i) {
             const int t = t0 + i / per_t, r = i % per_t;
-            const double v = j < 6 ? precision[precision_index(t, r, k, a, m, class_num)] : recall[recall_index(t, k, a, m, class_num)];
-            if (v > -1.) {
-                sum = sum + v;
-                cnt = cnt + 1.;
-            }
-        }
-        sum = block_sum(sum, s_dbl);
-        cnt = block_sum(cnt, s_dbl);
-        if (tid == 0) per_class[12 * (size_t)k + j] = cnt > 0. ? sum / cnt : -1.;
+            return j < 6 ? precision[precision_index(t, r, k, a, m, class_num)] : recall[recall_index(t, k, a, m, class_num)];
+        }, s_dbl);
+        if (tid == 0) per_class[12 * (size_t)k + j] = mean;
     }
 }
 
-// one block: stats[j] = the mean of per_class[.][j] over the classes where it is > -1, or -1 without any
+// one block: stats[j] = the defined_mean of per_class[.][j] over the classes
 __global__ __launch_bounds__(kThreads) void coco_stats_kernel(const double* __restrict__ per_class, int class_num,
                                                               double* __restrict__ stats) {
     __shared__ double s_dbl[kThreads];
-    const int tid = threadIdx.x;
     for (int j = 0; j < 12; ++j) {
-        double sum = 0., cnt = 0.;
-        for (int k = tid; k < class_num; k += kThreads) {
-            const double v = per_class[12 * (size_t)k + j];
-            if (v > -1.) {
-                sum = sum + v;
-                cnt = cnt + 1.;
-            }
-        }
-        sum = block_sum(sum, s_dbl);
-        cnt = block_sum(cnt, s_dbl);
-        if (tid == 0) stats[j] = cnt > 0. ? sum / cnt : -1.;
+        const double mean = defined_mean(class_num, [&](int k) { return per_class[12 * (size_t)k + j]; }, s_dbl);
+        if (threadIdx.x == 0) stats[j] = mean;
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 constexpr long long kIntMax = 0x7FFFFFFFLL;
 constexpr long long kCurveEntries = (long long)kIouThrs * kRecThrs * kAreas * kMaxDetKinds;      // precision entries per class
+
+// y3_coco_match's scratch: the "taken" word of every object (one for an empty set), for the images the LDS is too small for
+struct MatchScratch {
+    Carve at;
+    int num_gt;
+    size_t taken_words = num_gt > 0 ? num_gt : 1;
+    u64* taken_big = at.take<u64>(taken_words);
+};
+
+// y3_coco_ap's scratch: the gather into class order (order2) of the two words, the label and the in-group rank of a rank
+struct ApScratch {
+    Carve at;
+    int rows;
+    u64* mw2 = at.take<u64>(rows);
+    u64* iw2 = at.take<u64>(rows);
+    int32_t* lab2 = at.take<int32_t>(rows);
+    uint8_t* gr2 = at.take<uint8_t>(rows);
+};
 
 }  // namespace
 
@@ -427,8 +390,7 @@ extern "C" int y3_coco_ap_pass(void) { return kPass; }
 extern "C" int y3_coco_lds_objects(void) { return kLdsObjs; }
 
 extern "C" size_t y3_coco_match_scratch_bytes(int rows, int num_gt) {
-    if (rows <= 0 || num_gt < 0) return 0;
-    return align256((size_t)(num_gt > 0 ? num_gt : 1) * 8);
+    return rows > 0 && num_gt >= 0 ? MatchScratch{nullptr, num_gt}.at.bytes() : 0;
 }
 
 extern "C" int y3_coco_match(y3_ctx* ctx, const double* arena_box, const int32_t* arena_label, const int32_t* arena_image,
@@ -453,12 +415,12 @@ extern "C" int y3_coco_match(y3_ctx* ctx, const double* arena_box, const int32_t
     IouThrs thr;
     for (int t = 0; t < kIouThrs; ++t) thr.t[t] = iou_thrs_host[t];
     hipStream_t st = ctx->stream;
-    u64* taken_big = static_cast<u64*>(scratch);
-    Y3_CHECK_HIP(hipMemsetAsync(taken_big, 0, (size_t)(num_gt > 0 ? num_gt : 1) * 8, st));
+    const MatchScratch ws{scratch, num_gt};
+    Y3_CHECK_HIP(hipMemsetAsync(ws.taken_big, 0, ws.taken_words * 8, st));
     Y3_CHECK_HIP(hipMemsetAsync(npig, 0, (size_t)class_num * kAreas * 4, st));
     const unsigned blocks = (unsigned)(((long long)rows + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(coco_match_kernel, dim3(blocks), dim3(kThreads), 0, st, arena_box, arena_label, arena_image, order, rows,
-                       n_rows_dev, gt_start, gt_box, gt_label, area_scale, num_images, num_gt, class_num, thr, taken_big,
+                       n_rows_dev, gt_start, gt_box, gt_label, area_scale, num_images, num_gt, class_num, thr, ws.taken_big,
                        reinterpret_cast<u64*>(matched), reinterpret_cast<u64*>(ignored), group_rank);
     Y3_CHECK_HIP(hipGetLastError());
     if (num_gt > 0) {
@@ -470,8 +432,7 @@ extern "C" int y3_coco_match(y3_ctx* ctx, const double* arena_box, const int32_t
 }
 
 extern "C" size_t y3_coco_ap_scratch_bytes(int rows) {
-    if (rows <= 0) return 0;
-    return 2 * align256((size_t)rows * 8) + align256((size_t)rows * 4) + align256((size_t)rows);
+    return rows > 0 ? ApScratch{nullptr, rows}.at.bytes() : 0;
 }
 
 extern "C" int y3_coco_ap(y3_ctx* ctx, const uint64_t* matched, const uint64_t* ignored, const uint8_t* group_rank,
@@ -492,18 +453,14 @@ extern "C" int y3_coco_ap(y3_ctx* ctx, const uint64_t* matched, const uint64_t* 
                  "y3_coco_ap: misaligned pointer");
     RecThrs thr;
     for (int r = 0; r < kRecThrs; ++r) thr.r[r] = rec_thrs_host[r];
-    char* p = static_cast<char*>(scratch);
-    u64* mw2 = reinterpret_cast<u64*>(p);
-    u64* iw2 = reinterpret_cast<u64*>(p + align256((size_t)rows * 8));
-    int32_t* lab2 = reinterpret_cast<int32_t*>(p + 2 * align256((size_t)rows * 8));
-    uint8_t* gr2 = reinterpret_cast<uint8_t*>(p + 2 * align256((size_t)rows * 8) + align256((size_t)rows * 4));
+    const ApScratch ws{scratch, rows};
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(coco_gather_kernel, dim3((unsigned)(((long long)rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                        reinterpret_cast<const u64*>(matched), reinterpret_cast<const u64*>(ignored), group_rank, arena_label, order,
-                       order2, rows, n_rows_dev, class_num, mw2, iw2, lab2, gr2);
+                       order2, rows, n_rows_dev, class_num, ws.mw2, ws.iw2, ws.lab2, ws.gr2);
     Y3_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(coco_ap_kernel, dim3(class_num, kAreas * kMaxDetKinds, kIouThrs), dim3(kThreads), 0, st, mw2, iw2, lab2, gr2,
-                       rows, n_rows_dev, npig, class_num, thr, precision, recall);
+    hipLaunchKernelGGL(coco_ap_kernel, dim3(class_num, kAreas * kMaxDetKinds, kIouThrs), dim3(kThreads), 0, st, ws.mw2, ws.iw2,
+                       ws.lab2, ws.gr2, rows, n_rows_dev, npig, class_num, thr, precision, recall);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }

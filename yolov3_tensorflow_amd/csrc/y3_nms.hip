@@ -16,7 +16,7 @@
 // bit-exact against the CPU oracle.
 //
 // Pipeline: collect (threshold + per-class compaction, LDS-aggregated atomics) -> select -> gather.
-#include "y3_internal.h"
+#include "y3_eval_common.h"      // (the host part: the workspace layout)
 
 namespace {
 
@@ -384,14 +384,22 @@ __global__ void __launch_bounds__(256) nms_gather_kernel(const float* __restrict
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// y3_nms's workspace for nc = n * class_num classes: the regions of NmsWs in the order they lie in; returns their bytes
+size_t carve_workspace(void* base, size_t nc, int num_boxes, int max_boxes, NmsWs* ws) {
+    y3ev::Carve c(base);
+    ws->cand_count = c.take<int32_t>(nc);
+    ws->sel_count = c.take<int32_t>(nc);
+    ws->cand_idx = c.take<int32_t>(nc * num_boxes);
+    ws->sel_idx = c.take<int32_t>(nc * max_boxes);
+    return c.bytes();
+}
 
 }  // namespace
 
 extern "C" size_t y3_nms_workspace_bytes(int n, int num_boxes, int class_num, int max_boxes) {
     if (n <= 0 || num_boxes <= 0 || class_num <= 0 || max_boxes <= 0) return 0;
-    const size_t nc = (size_t)n * class_num;
-    return align256(nc * 4) * 2 + align256(nc * num_boxes * 4) + align256(nc * max_boxes * 4);
+    NmsWs ws;
+    return carve_workspace(nullptr, (size_t)n * class_num, num_boxes, max_boxes, &ws);
 }
 
 extern "C" int y3_nms(y3_ctx* ctx, int mode, const float* boxes, const float* scores, int n, int num_boxes,
@@ -408,12 +416,8 @@ extern "C" int y3_nms(y3_ctx* ctx, int mode, const float* boxes, const float* sc
     Y3_CHECK_ARG(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0,
                  "y3_nms: boxes/out_boxes must be 16-byte aligned");
     const size_t nc = (size_t)n * class_num;
-    char* p = static_cast<char*>(workspace);
     NmsWs ws;
-    ws.cand_count = reinterpret_cast<int32_t*>(p); p += align256(nc * 4);
-    ws.sel_count = reinterpret_cast<int32_t*>(p);  p += align256(nc * 4);
-    ws.cand_idx = reinterpret_cast<int32_t*>(p);   p += align256(nc * num_boxes * 4);
-    ws.sel_idx = reinterpret_cast<int32_t*>(p);
+    carve_workspace(workspace, nc, num_boxes, max_boxes, &ws);
     // the sorted forms keep a class's keys AND its selected boxes in the LDS: beyond ~1,600 boxes per class the arg-max form
     // takes every class
     const bool sorted_ok = (size_t)16384 * 8 + (size_t)max_boxes * 20 + 16 <= (size_t)160 * 1024;

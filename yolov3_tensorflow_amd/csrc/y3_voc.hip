@@ -10,16 +10,16 @@
 //
 // Every index read from device memory (counts, image indices, CSR offsets, order, labels) is clamped to the extents the
 // host passed before it addresses anything; every loop is bounded by those extents.  The arithmetic is y3_voc_px.h's.
-#include "y3_internal.h"
+#include "y3_eval_common.h"
 #include "y3_voc_px.h"
 
 namespace {
 
+using namespace y3ev;
+
 constexpr int kThreads = 256;
 constexpr int kItems = 4;
 constexpr int kPass = kThreads * kItems;      // ranks of a class one pass of voc_ap_kernel covers (y3_voc_ap_pass)
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ------------------------------------------------------------------------------------------------ append
 // block (i, y): rows of batch image i.  Its first arena row = the running total + the exclusive scan of the counts at i.
@@ -33,13 +33,7 @@ __global__ __launch_bounds__(kThreads) void voc_append_kernel(const float* __res
     const int i = blockIdx.x, tid = threadIdx.x;
     long long part = 0;
     for (int j = tid; j < i; j += kThreads) part += clampi(cnt[j], 0, cap);
-    s_part[tid] = part;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) s_part[tid] += s_part[tid + s];
-        __syncthreads();
-    }
-    const long long base = (long long)clampi(state[0], 0, capacity) + s_part[0];
+    const long long base = (long long)clampi(state[0], 0, capacity) + block_sum<kThreads>(part, s_part);
     const int k_i = clampi(cnt[i], 0, cap);
     const int image_index = img[i];
     for (int k = blockIdx.y * kThreads + tid; k < k_i; k += gridDim.y * kThreads) {
@@ -65,15 +59,10 @@ __global__ __launch_bounds__(kThreads) void voc_append_total_kernel(const int32_
     const int tid = threadIdx.x;
     long long part = 0;
     for (int j = tid; j < n; j += kThreads) part += clampi(cnt[j], 0, cap);
-    s_part[tid] = part;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) s_part[tid] += s_part[tid + s];
-        __syncthreads();
-    }
+    const long long added = block_sum<kThreads>(part, s_part);
     if (tid == 0) {
         const long long before = clampi(state[0], 0, capacity);
-        const long long want = before + s_part[0];
+        const long long want = before + added;
         const long long now = want < capacity ? want : capacity;
         const long long lost = (long long)clampi(state[1], 0, 0x7FFFFFFF) + (want - now);
         state[0] = (int32_t)now;
@@ -82,10 +71,6 @@ __global__ __launch_bounds__(kThreads) void voc_append_total_kernel(const int32_
 }
 
 // ------------------------------------------------------------------------------------------------ match
-__device__ __forceinline__ int ranked_total(const int32_t* n_rows_dev, int rows) {
-    return n_rows_dev ? clampi(*n_rows_dev, 0, rows) : rows;
-}
-
 __global__ __launch_bounds__(kThreads) void voc_match_kernel(const double* __restrict__ box, const int32_t* __restrict__ label,
                                                              const int32_t* __restrict__ image, const int32_t* __restrict__ order,
                                                              int rows, const int32_t* __restrict__ n_rows_dev,
@@ -141,66 +126,6 @@ struct Thresholds {
     double t[11];
 };
 
-// exclusive prefix sum of one int per thread in thread order; *total = the block's sum
-__device__ int block_excl_sum(int v, int* sh, int* total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-        const int t = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const int incl = sh[tid];
-    *total = sh[kThreads - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// max over the threads to the right of this one (0. for the last), values >= 0; *all = the block's max
-__device__ double block_right_max(double v, double* sh, double* all) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-        const double t = tid + off < kThreads ? sh[tid + off] : 0.;
-        __syncthreads();
-        sh[tid] = y3vpx::dmax(sh[tid], t);
-        __syncthreads();
-    }
-    const double right = tid + 1 < kThreads ? sh[tid + 1] : 0.;
-    *all = sh[0];
-    __syncthreads();
-    return right;
-}
-
-// the block's sum by a fixed tree / the block's max; the result in every thread
-__device__ double block_sum(double v, double* sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
-        __syncthreads();
-    }
-    const double out = sh[0];
-    __syncthreads();
-    return out;
-}
-__device__ double block_max(double v, double* sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] = y3vpx::dmax(sh[tid], sh[tid + s]);
-        __syncthreads();
-    }
-    const double out = sh[0];
-    __syncthreads();
-    return out;
-}
-
 // block c: class c's row of out = (npos, nd, recall, precision, ap), eval_utils.py:207-217 and 238-244
 __global__ __launch_bounds__(kThreads) void voc_ap_kernel(const uint8_t* __restrict__ tp, const int32_t* __restrict__ seg_start, int rows,
                                                           const int32_t* __restrict__ gt_label, int num_gt, int use_07_metric,
@@ -210,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void voc_ap_kernel(const uint8_t* __restr
     const int c = blockIdx.x, tid = threadIdx.x;
     int mine = 0, npos = 0;
     for (int g = tid; g < num_gt; g += kThreads) mine += gt_label[g] == c;
-    block_excl_sum(mine, s_int, &npos);
+    block_excl_sum<kThreads>(mine, s_int, &npos);
     const int s = clampi(seg_start[c], 0, rows), e = clampi(seg_start[c + 1], s, rows), nd = e - s;
     double* o = out + 5 * (size_t)c;
     if (nd == 0) {      // 'no box, ignore'
@@ -237,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void voc_ap_kernel(const uint8_t* __restr
             sum += v[k];
         }
         int pass_total;
-        int run = carry + block_excl_sum(sum, s_int, &pass_total);
+        int run = carry + block_excl_sum<kThreads>(sum, s_int, &pass_total);
         for (int k = 0; k < kItems; ++k) {
             const int i = i0 + k;
             if (i >= nd) break;
@@ -254,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void voc_ap_kernel(const uint8_t* __restr
     __syncthreads();      // every ctp of the class is written before the backward passes read a neighbour's
     double ap;
     if (use_07_metric) {
-        for (int t = 0; t < 11; ++t) best[t] = block_max(best[t], s_dbl);
+        for (int t = 0; t < 11; ++t) best[t] = block_max<kThreads>(best[t], s_dbl);
         ap = y3vpx::eleven_point(best);
     } else {
         // backwards: the envelope at rank i = max(prec[i..nd-1], 0.); each thread adds the area terms of its ranks in
@@ -272,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void voc_ap_kernel(const uint8_t* __restr
                 tmax = y3vpx::dmax(tmax, prec[k]);
             }
             double pass_max;
-            double env = y3vpx::dmax(env_right, block_right_max(tmax, s_dbl, &pass_max));
+            double env = y3vpx::dmax(env_right, block_right_max<kThreads>(tmax, s_dbl, &pass_max));
             for (int k = kItems - 1; k >= 0; --k) {
                 const int i = i0 + k;
                 if (i >= nd) continue;
@@ -285,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void voc_ap_kernel(const uint8_t* __restr
             }
             env_right = y3vpx::dmax(env_right, pass_max);
         }
-        ap = block_sum(acc, s_dbl);
+        ap = block_sum<kThreads>(acc, s_dbl);
         bool take;      // the closing position of the padded arrays: mrec 1., mpre 0.
         const double term = y3vpx::area_term(y3vpx::recall_at(carry, npos), 1., 0., &take);
         if (take) ap = ap + term;
@@ -299,8 +224,21 @@ __global__ __launch_bounds__(kThreads) void voc_ap_kernel(const uint8_t* __restr
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// y3_voc_match's scratch: the best object of every rank | the claim word of every object (one for an empty set)
+struct MatchScratch {
+    Carve at;
+    int rows, num_gt;
+    size_t claim_words = num_gt > 0 ? num_gt : 1;
+    int32_t* jstar = at.take<int32_t>(rows);
+    unsigned* claim = at.take<unsigned>(claim_words);
+};
+
+// y3_voc_ap's scratch: the running true-positive count of every rank
+struct ApScratch {
+    Carve at;
+    int rows;
+    int32_t* ctp = at.take<int32_t>(rows);
+};
 
 }  // namespace
 
@@ -331,8 +269,7 @@ extern "C" int y3_voc_append(y3_ctx* ctx, const float* out_boxes, const float* o
 }
 
 extern "C" size_t y3_voc_match_scratch_bytes(int rows, int num_gt) {
-    if (rows <= 0 || num_gt < 0) return 0;
-    return align256((size_t)rows * 4) + align256((size_t)(num_gt > 0 ? num_gt : 1) * 4);
+    return rows > 0 && num_gt >= 0 ? MatchScratch{nullptr, rows, num_gt}.at.bytes() : 0;
 }
 
 extern "C" int y3_voc_match(y3_ctx* ctx, const double* arena_box, const int32_t* arena_label, const int32_t* arena_image,
@@ -350,23 +287,21 @@ extern "C" int y3_voc_match(y3_ctx* ctx, const double* arena_box, const int32_t*
                      aligned(arena_image, 4) && aligned(order, 4) && aligned(gt_start, 4) && aligned(gt_label, 4) &&
                      aligned(seg_start, 4) && (!n_rows_dev || aligned(n_rows_dev, 4)),
                  "y3_voc_match: misaligned pointer");
-    char* p = static_cast<char*>(scratch);
-    int32_t* jstar = reinterpret_cast<int32_t*>(p);
-    unsigned* claim = reinterpret_cast<unsigned*>(p + align256((size_t)rows * 4));
+    const MatchScratch ws{scratch, rows, num_gt};
     hipStream_t st = ctx->stream;
-    Y3_CHECK_HIP(hipMemsetAsync(claim, 0xFF, (size_t)(num_gt > 0 ? num_gt : 1) * 4, st));      // y3vpx::kUnclaimed
+    Y3_CHECK_HIP(hipMemsetAsync(ws.claim, 0xFF, ws.claim_words * 4, st));      // y3vpx::kUnclaimed
     Y3_CHECK_HIP(hipMemsetAsync(seg_start, 0, (size_t)(class_num + 1) * 4, st));
     const unsigned blocks = (unsigned)(((long long)rows + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(voc_match_kernel, dim3(blocks), dim3(kThreads), 0, st, arena_box, arena_label, arena_image, order, rows,
-                       n_rows_dev, gt_start, gt_box, gt_label, num_images, num_gt, iou_thres, jstar, claim);
+                       n_rows_dev, gt_start, gt_box, gt_label, num_images, num_gt, iou_thres, ws.jstar, ws.claim);
     Y3_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(voc_tp_kernel, dim3(blocks), dim3(kThreads), 0, st, jstar, claim, arena_label, order, rows, n_rows_dev, num_gt,
+    hipLaunchKernelGGL(voc_tp_kernel, dim3(blocks), dim3(kThreads), 0, st, ws.jstar, ws.claim, arena_label, order, rows, n_rows_dev, num_gt,
                        class_num, tp, seg_start);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }
 
-extern "C" size_t y3_voc_ap_scratch_bytes(int rows) { return rows > 0 ? align256((size_t)rows * 4) : 0; }
+extern "C" size_t y3_voc_ap_scratch_bytes(int rows) { return rows > 0 ? ApScratch{nullptr, rows}.at.bytes() : 0; }
 
 extern "C" int y3_voc_ap(y3_ctx* ctx, const uint8_t* tp, const int32_t* seg_start, int rows, const int32_t* gt_label, int num_gt,
                          int class_num, int use_07_metric, const double* thresholds_host11, void* scratch, size_t scratch_bytes,
@@ -382,7 +317,7 @@ extern "C" int y3_voc_ap(y3_ctx* ctx, const uint8_t* tp, const int32_t* seg_star
     Thresholds thr;
     for (int k = 0; k < 11; ++k) thr.t[k] = use_07_metric ? thresholds_host11[k] : 0.;
     hipLaunchKernelGGL(voc_ap_kernel, dim3(class_num), dim3(kThreads), 0, ctx->stream, tp, seg_start, rows, gt_label, num_gt,
-                       use_07_metric ? 1 : 0, thr, static_cast<int32_t*>(scratch), out);
+                       use_07_metric ? 1 : 0, thr, ApScratch{scratch, rows}.ctp, out);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }

@@ -53,18 +53,9 @@ def prepare_conv_params(w_var, bn_vars=None, bias_var=None):
     return w_dev, scale, shift
 
 
-_scratch = {}
-
-
 def _conv_scratch(device, nbytes):
-    """Per-(device, stream) scratch for the stream-K schedule (kernels on one stream are ordered, so one
-    buffer per stream is enough)."""
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    t = _scratch.get(key)
-    if t is None or t.numel() < nbytes:
-        t = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _scratch[key] = t
-    return t
+    """Scratch for the stream-K schedule."""
+    return fw.stream_scratch('conv', device, nbytes)
 
 
 def conv2d_fwd(x, w_dev, scale, shift, k, stride, cout, act, residual=None, x_up=None, use_workspace=True,

@@ -224,6 +224,21 @@ def check_context(device=None):
     _lib.check(_lib.lib().y3_ctx_check(context(device)))
 
 
+_scratch_cache = {}      # (user tag, device index, stream) -> uint8 tensor
+
+
+def stream_scratch(tag, device, nbytes):
+    """Scratch of one library call of the user `tag` on (a torch.device, torch's current stream on it): one uint8 buffer per
+    key, grown on demand.  Calls on a stream are ordered, so the next call may overwrite what the previous one used (results
+    live in tensors of their own); users with different tags never share a buffer."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (tag, idx, torch.cuda.current_stream(device).cuda_stream)
+    t = _scratch_cache.get(key)
+    if t is None or t.numel() < nbytes:
+        t = _scratch_cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
 def ptr(t):
     """Raw device pointer of a contiguous fp32/int32 tensor (None -> NULL)."""
     if t is None:

@@ -122,19 +122,6 @@ def evaluate_on_gpu(sess, gpu_nms_op, pred_boxes_flag, pred_scores_flag, y_pred,
     return _evaluate(y_pred, y_true, num_classes, gpu_nms_op, iou_thresh, calc_now)
 
 
-_BEVAL_WS = {}      # (device index, stream) -> uint8 tensor: y3_batch_eval's scratch, reused by every call on that stream
-
-
-def _beval_workspace(dev, nbytes):
-    """Scratch of one y3_batch_eval call: one buffer per (device, stream), grown on demand, like nms_utils._workspace."""
-    import torch
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _BEVAL_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _BEVAL_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    return ws
-
-
 def batch_eval_counts(detections, y_true, num_classes, iou_thresh=0.5, gt_cap=None, table=None):
     """y3_batch_eval (include/yolo355.h) on device tensors: `detections` is what gpu_nms_batched(..., lazy=True) returned, or
     its (boxes [n,cap,4] f32, scores, labels [n,cap] i32, counts [n] i32) device tensors; y_true the batch's three
@@ -164,7 +151,7 @@ def batch_eval_counts(detections, y_true, num_classes, iou_thresh=0.5, gt_cap=No
     nbytes = L.y3_batch_eval_scratch_bytes(n, gt_cap)
     if nbytes == 0:
         raise ValueError("batch_eval_counts: non-positive dimension (n=%d, gt_cap=%d)" % (n, gt_cap))
-    ws = _beval_workspace(dev, nbytes)
+    ws = fw.stream_scratch('batch_eval', dev, nbytes)
     if table is None:
         table = torch.zeros((C + 1, 3), dtype=torch.int64, device=dev)
     ob, ol, cnt = ob.contiguous(), ol.contiguous(), cnt.contiguous()
@@ -599,6 +586,33 @@ class DeviceEval(object):
         image[at:at + k] = torch.from_numpy(np.asarray(self._indices(image_ids), np.int32)).to(self._dev)
         self._state[0] += k
 
+    def _rank(self, *keys):
+        """Plumbing: the int32 order of the arena's rows (or of their ranks) by stable sorts, the last key first.  Each key is
+        (tensor [R], fill): rows at or past the arena's count take `fill` (None: the value as it is), which ranks them behind
+        every detection."""
+        import torch
+        live = torch.arange(self.capacity_rows, device=self._dev, dtype=torch.int32) < self._state[0]
+        order = None
+        for key, fill in keys:
+            if fill is not None:
+                key = torch.where(live, key, torch.full_like(key, fill))
+            order = torch.sort(key, stable=True).indices if order is None else order[torch.sort(key[order], stable=True).indices]
+        return order.to(torch.int32).contiguous()
+
+    def _read_back(self, out, at, upto):
+        """out[:upto] on the host, with the arena's two counters in out[at:at + 2]: the one device -> host copy of a finish.
+        Raises Y3Error when rows were dropped for lack of capacity."""
+        import torch
+        from .. import _lib, framework as fw
+        out[at:at + 2] = self._state.to(torch.float64)
+        host = out[:upto].cpu().numpy()
+        fw.check_context(self._dev)
+        rows, lost = int(host[at]), int(host[at + 1])
+        if lost:
+            raise _lib.Y3Error("DeviceEval: %d detections did not fit the arena's %d rows (%d kept): raise capacity_rows" % (
+                lost, self.capacity_rows, rows))
+        return host
+
     def finish(self, iou_thres=0.5, use_07_metric=False):
         """The [class_num, 5] float64 table of (npos, nd, recall, precision, ap).  One device -> host copy (the table with the
         arena's two counters behind it); raises Y3Error when rows were dropped for lack of capacity."""
@@ -607,17 +621,13 @@ class DeviceEval(object):
         from .. import _lib, framework as fw
         L, ctx, dev, R, C = _lib.lib(), fw.context(self._dev), self._dev, self.capacity_rows, self.class_num
         box, score, label, image = self._arena
-        # plumbing: rank order (label ascending, score descending, row ascending) from two stable sorts; the rows past the
-        # arena's count take the label C and so rank behind every detection.  Negating a float64 is exact.
-        live = torch.arange(R, device=dev, dtype=torch.int32) < self._state[0]
-        by_score = torch.sort(-score, stable=True).indices
-        key = torch.where(live, label, torch.full_like(label, C))[by_score]
-        order = by_score[torch.sort(key, stable=True).indices].to(torch.int32).contiguous()
+        # rank order: label ascending, score descending, row ascending.  Negating a float64 is exact.
+        order = self._rank((-score, None), (label, C))
         m_bytes, a_bytes = L.y3_voc_match_scratch_bytes(R, self.num_gt), L.y3_voc_ap_scratch_bytes(R)
         scratch = torch.empty(max(m_bytes, a_bytes), dtype=torch.uint8, device=dev)
         tp = torch.empty(R, dtype=torch.uint8, device=dev)
         seg = torch.empty(C + 1, dtype=torch.int32, device=dev)
-        out = torch.zeros((C + 1, 5), dtype=torch.float64, device=dev)
+        out = torch.zeros(5 * C + 2, dtype=torch.float64, device=dev)
         _lib.check(L.y3_voc_match(ctx, fw.ptr(box), fw.ptr(label), fw.ptr(image), fw.ptr(order), R, fw.ptr(self._state),
                                   fw.ptr(self._gt_start), fw.ptr(self._gt_box), fw.ptr(self._gt_label), len(self._index),
                                   self.num_gt, C, ctypes.c_double(iou_thres), fw.ptr(scratch), ctypes.c_size_t(m_bytes), fw.ptr(tp),
@@ -625,14 +635,7 @@ class DeviceEval(object):
         thresholds = (ctypes.c_double * 11)(*np.arange(0., 1.1, 0.1))
         _lib.check(L.y3_voc_ap(ctx, fw.ptr(tp), fw.ptr(seg), R, fw.ptr(self._gt_label), self.num_gt, C, int(bool(use_07_metric)),
                                thresholds, fw.ptr(scratch), ctypes.c_size_t(a_bytes), fw.ptr(out)))
-        out[C, 0:2] = self._state.to(torch.float64)
-        table = out.cpu().numpy()
-        fw.check_context(dev)
-        rows, lost = int(table[C, 0]), int(table[C, 1])
-        if lost:
-            raise _lib.Y3Error("DeviceEval: %d detections did not fit the arena's %d rows (%d kept): raise capacity_rows" % (
-                lost, R, rows))
-        return table[:C].copy()
+        return self._read_back(out, 5 * C, 5 * C + 2)[:5 * C].reshape(C, 5).copy()
 
     def finish_coco(self, area_scale=None, return_curves=False):
         """coco_eval's numbers for the rows in the arena (y3_coco_match / y3_coco_ap / y3_coco_summary, include/yolo355.h):
@@ -648,17 +651,11 @@ class DeviceEval(object):
         L, ctx, dev, R, C = _lib.lib(), fw.context(self._dev), self._dev, self.capacity_rows, self.class_num
         N = len(self._index)
         box, score, label, image = self._arena
-        # plumbing: stable sorts, the last key first.  order: (image, label, score descending, row); the rows past the arena's
-        # count take the image N and the label C and so rank behind every detection.  order2 sorts the RANKS of order by
-        # (label, score descending): equal keys keep (image, in-group rank) ascending.  Negating a float64 is exact.
-        live = torch.arange(R, device=dev, dtype=torch.int32) < self._state[0]
-        by_score = torch.sort(-score, stable=True).indices
-        by_label = by_score[torch.sort(torch.where(live, label, torch.full_like(label, C))[by_score], stable=True).indices]
-        order64 = by_label[torch.sort(torch.where(live, image, torch.full_like(image, N))[by_label], stable=True).indices]
-        order = order64.to(torch.int32).contiguous()
-        rank_score = torch.sort(-score[order64], stable=True).indices
-        rank_label = torch.where(live, label[order64], torch.full_like(label, C))      # (the live ranks are the first ones)
-        order2 = rank_score[torch.sort(rank_label[rank_score], stable=True).indices].to(torch.int32).contiguous()
+        # order: (image, label, score descending, row).  order2 sorts the RANKS of order by (label, score descending): equal
+        # keys keep (image, in-group rank) ascending, and the live ranks are the first ones.  Negating a float64 is exact.
+        order = self._rank((-score, None), (label, C), (image, N))
+        at = order.long()
+        order2 = self._rank((-score[at], None), (label[at], C))
         scale = None
         if area_scale is not None:
             by_index = sorted(self._index, key=self._index.get)
@@ -681,13 +678,7 @@ class DeviceEval(object):
                                 R, fw.ptr(self._state), fw.ptr(npig), C, rec_thrs, fw.ptr(scratch), ctypes.c_size_t(a_bytes),
                                 fw.ptr(precision), fw.ptr(recall)))
         _lib.check(L.y3_coco_summary(ctx, fw.ptr(precision), fw.ptr(recall), C, fw.ptr(per_class), fw.ptr(stats)))
-        out[head - 2:head] = self._state.to(torch.float64)
-        host = (out if return_curves else out[:head]).cpu().numpy()
-        fw.check_context(dev)
-        rows, lost = int(host[head - 2]), int(host[head - 1])
-        if lost:
-            raise _lib.Y3Error("DeviceEval: %d detections did not fit the arena's %d rows (%d kept): raise capacity_rows" % (
-                lost, R, rows))
+        host = self._read_back(out, head - 2, out.numel() if return_curves else head)
         result = {'stats': host[:12].copy(), 'per_class': host[12:12 + 12 * C].reshape(C, 12).copy()}
         if return_curves:
             result['precision'] = host[head:head + n_prec].reshape(10, 101, C, 4, 3).copy()

@@ -19,19 +19,6 @@ from .. import _lib
 from .. import framework as fw
 
 
-_WS_CACHE = {}      # (device index, stream) -> uint8 tensor: y3_nms's scratch, reused by every call on that stream
-
-
-def _workspace(dev, nbytes):
-    """The library's scratch for one y3_nms call.  One buffer per (device, stream), grown on demand: calls on a stream are
-    ordered, so the next call may overwrite what the previous one used (the results live in tensors of their own)."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WS_CACHE.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _WS_CACHE[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    return ws
-
-
 class LazyDetections(object):
     """What gpu_nms_batched(lazy=True) / yolov3.detect return: behaves like the list of per-image (boxes, scores, labels[,
     index]) tuples, but the per-image counts travel to the host asynchronously (pinned buffer + event) and the list is built
@@ -86,7 +73,7 @@ def _run_nms(mode, boxes, scores, num_classes, max_boxes, score_thresh, iou_thre
     if wsb == 0:
         raise ValueError("nms: non-positive dimension (n=%d, boxes=%d, classes=%d, max_boxes=%d)" %
                          (n, B, C, max_boxes))
-    ws = _workspace(dev, wsb)
+    ws = fw.stream_scratch('nms', dev, wsb)
     ob = torch.empty((n, cap, 4), dtype=torch.float32, device=dev)
     osc = torch.empty((n, cap), dtype=torch.float32, device=dev)
     ol = torch.empty((n, cap), dtype=torch.int32, device=dev)
