@@ -15,6 +15,15 @@
  *   - the caller owns every device buffer; the library allocates no device memory
  *     and keeps no pointer beyond the call, except the parameter buffer bound to a
  *     y3_net (which the caller must keep alive);
+ *   - the other half of that ownership: the library reads no byte that can change a result, and writes no byte, outside the
+ *     extents its arguments describe (a tensor's shape and row stride, a count, a *_bytes size).  Where a kernel's loads
+ *     run past an extent (ragged tiles, prologues that issue ahead), a range check or a mask discards what they return;
+ *     no store ever does.  Every *_bytes function (*_workspace_bytes, *_scratch_bytes, y3_net_params_bytes) is an exact
+ *     upper bound on what the call touches in that buffer: a buffer of exactly that many bytes, not rounded up, is enough,
+ *     and its contents on entry never matter.  tests/test_guard_bands_gpu.py holds every entry point to this;
+ *   - device pointers need 16-byte alignment unless the entry says otherwise (the net's parameter buffer and workspaces:
+ *     256; the evaluators' tables: the alignment of their element type; dw_hwio of the weight gradients and the
+ *     optimizer's tensors with n %% 4 != 0: 4).  An entry that checks alignment refuses with Y3_EINVAL before any launch;
  *   - activations are NHWC fp32 contiguous; conv kernels in TF layout are HWIO
  *     (utils/misc_utils.py:117-120) and are re-packed once by y3_pack_conv_weights;
  *   - every launch goes to the hipStream_t bound to the context; no call synchronises
@@ -255,7 +264,9 @@ int y3_conv2d_fwd_split(y3_ctx* ctx, const y3_conv_desc* d, int planes, const fl
  * y3_concat_channels  : tf.concat([a, b], axis=3) on NHWC with `rows` = N*H*W (model.py:62,72)
  * y3_add              : net + shortcut (utils/layer_utils.py:30)
  * y3_reorg_boxes      : box part of reorg_layer for one scale (model.py:96-131):
- *                       boxes [N,gh,gw,3,4] = (cx,cy,w,h) in input pixels; anchors3 = the 3 (w,h) pairs. */
+ *                       boxes [N,gh,gw,3,4] = (cx,cy,w,h) in input pixels; anchors3 = the 3 (w,h) pairs.
+ * The first three move 16 bytes per lane: c, ca, cb and count must be multiples of 4 (every channel count of the network
+ * is), anything else is Y3_EINVAL before any launch. */
 int y3_upsample_nearest(y3_ctx* ctx, const float* x, int n, int h, int w, int c, int out_h, int out_w,
                         float* y);
 int y3_concat_channels(y3_ctx* ctx, const float* a, int ca, const float* b, int cb, long long rows, float* y);
@@ -268,7 +279,10 @@ int y3_reorg_boxes(y3_ctx* ctx, const float* fm, int n, int gh, int gw, int clas
  * fm_s: [N, H/stride_s, W/stride_s, 3*(5+C)] for strides 32,16,8 (in that order).
  * anchors: 9 (w,h) pairs in data/yolo_anchors.txt order; scale s uses anchors[6-3s .. 8-3s].
  * boxes [N,B,4] = (x_min,y_min,x_max,y_max); confs [N,B,1]; probs [N,B,C]; scores [N,B,C] or NULL.
- * B = 3*(g1^2+g2^2+g3^2), box order = scale (13,26,52), then y, x, anchor (model.py:155-180). */
+ * B = 3*(g1^2+g2^2+g3^2), box order = scale (13,26,52), then y, x, anchor (model.py:155-180).
+ * Alignment: any 4-byte boundary is accepted for every pointer.  With fm1..3, boxes, probs and scores (where given) all
+ * 16-byte aligned, class_num %% 4 == 0 and class_num <= 248 the LDS-staged kernel runs (16-byte accesses); otherwise the
+ * 4-byte-per-lane kernel does, with the same results and more memory transactions - a slower path, not an error. */
 int y3_decode(y3_ctx* ctx, const float* fm1, const float* fm2, const float* fm3, int n, int h, int w,
               int class_num, const float* anchors_host18, float* boxes, float* confs, float* probs,
               float* scores);
@@ -385,8 +399,11 @@ int y3_bias_grad(y3_ctx* ctx, const float* dy, long long rows, int c, float* dbi
  * dgrad: dx [n,h,w,cin] (+)= data gradient.  dz is [n,h/s,w/s] x dz_stride channels (dz_stride >= cout,
  *        multiple of 32: the 3*(5+C) detection convs pad to the next multiple), w_d = the HWIO kernel with
  *        its last axis padded to dz_stride ([k*k][cin][dz_stride]); `ones`/`zeros` are [cin] device vectors.
+ *        workspace (NULL is allowed): that of the conv as launched, [n,h/s,w/s,dz_stride] -> cin at stride 1:
+ *        y3_conv_workspace_bytes of that conv (the Winograd forms below: their own size function of it).
  * wgrad: dw_hwio [k][k][cin][cout] = weight gradient; scratch: y3_conv_wgrad_scratch_bytes(fwd), 16-byte aligned
- *        (dw_hwio itself: any 4-byte boundary). */
+ *        (dw_hwio itself: any 4-byte boundary - also for y3_conv_wgrad_wino and y3_conv_wgrad_bf16 below: the train step
+ *        writes every weight gradient at flat_grad + its element offset).  The Cin = 3 stem: dz_stride = cout = 32 only. */
 int y3_conv2d_dgrad(y3_ctx* ctx, const y3_conv_desc* fwd, const float* dz, int dz_stride, const float* w_d,
                     const float* ones, const float* zeros, int accumulate, float* dx, void* workspace,
                     size_t workspace_bytes);
