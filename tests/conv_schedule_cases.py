@@ -74,3 +74,149 @@ DGRAD_BN = [
     (2, 128, 65, 256, 128, 128, 64, RESIDENT),       # 260 x 4 tiles on the resident walk
     (3, 20, 28, 128, 255, 256, 64, ONE_PER_TILE),    # a detection conv reading a BN layer: dz row stride 256
 ]
+
+
+# ---- 5. the host answers every launcher, planner and buffer size depends on --------------------------------------------------
+# (query, (n, h, w, cin, c_up, cout, k, stride), further arguments, y3_debug_conv_range_limit in force or 0, answer).  The
+# answers were recorded from the library as it stood BEFORE the conv launchers were moved onto one host path and one tile table
+# per kernel family; they are not derived from that code.  Every branch of every ladder: the statistics rows of the fp32 forward
+# (k = 1 and 3, Cout 32 / 64 / 128, stride 1 and 2, a ragged last block: 3 x 20 x 28 = 13 x 128 + 16 rows), the fused BN-backward
+# rows (Cin 64 and 128), the Winograd counts on an odd map, the bf16 training rows at M = 128 and 129, the schedule of each
+# shape with and without a workspace, the four parity classes of a stride-2 data gradient (y3_conv_schedule's conv is the one
+# launched: [n, h/2, w/2, fwd cout] -> fwd cin), the workspace size, and four launches cut in two by a lowered range limit.
+HOST_ANSWERS = [
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 32, 1, 1), (0,), 0, 14),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 1, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 1, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 32, 1, 2), (0,), 0, 0),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 32, 1, 2), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 1, 2), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 1, 2), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 64, 1, 1), (0,), 0, 14),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 1, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 1, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 64, 1, 2), (0,), 0, 0),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 64, 1, 2), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 1, 2), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 1, 2), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 128, 1, 1), (0,), 0, 27),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 128, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 1, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 1, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 128, 1, 2), (0,), 0, 0),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 128, 1, 2), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 1, 2), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 1, 2), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 32, 3, 1), (0,), 0, 14),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 32, 3, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 3, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 32, 3, 2), (0,), 0, 4),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 32, 3, 2), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 3, 2), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 32, 3, 2), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 64, 3, 1), (0,), 0, 14),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 64, 3, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 3, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 64, 3, 2), (0,), 0, 4),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 64, 3, 2), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 3, 2), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 64, 3, 2), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 128, 3, 1), (0,), 0, 14),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 128, 3, 1), (), 0, 33556480),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 3, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 64, 0, 128, 3, 2), (0,), 0, 4),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 64, 0, 128, 3, 2), (), 0, 33556480),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 3, 2), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 64, 0, 128, 3, 2), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 128, 0, 64, 1, 1), (0,), 0, 14),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 128, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 128, 0, 64, 1, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 128, 0, 64, 1, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 20, 28, 128, 0, 128, 1, 1), (0,), 0, 27),
+    ('y3_conv_workspace_bytes', (3, 20, 28, 128, 0, 128, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 128, 0, 128, 1, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 20, 28, 128, 0, 128, 1, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 13, 13, 64, 0, 128, 3, 1), (0,), 0, 4),
+    ('y3_conv_workspace_bytes', (3, 13, 13, 64, 0, 128, 3, 1), (), 0, 33556480),
+    ('y3_conv_schedule', (3, 13, 13, 64, 0, 128, 3, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (3, 13, 13, 64, 0, 128, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (2, 8, 8, 64, 0, 128, 3, 1), (0,), 0, 1),
+    ('y3_conv_workspace_bytes', (2, 8, 8, 64, 0, 128, 3, 1), (), 0, 33556480),
+    ('y3_conv_schedule', (2, 8, 8, 64, 0, 128, 3, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (2, 8, 8, 64, 0, 128, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (1, 3, 43, 64, 0, 128, 3, 1), (0,), 0, 2),
+    ('y3_conv_workspace_bytes', (1, 3, 43, 64, 0, 128, 3, 1), (), 0, 33556480),
+    ('y3_conv_schedule', (1, 3, 43, 64, 0, 128, 3, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (1, 3, 43, 64, 0, 128, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (8, 52, 52, 128, 0, 256, 3, 1), (0,), 0, 169),
+    ('y3_conv_workspace_bytes', (8, 52, 52, 128, 0, 256, 3, 1), (), 0, 33556480),
+    ('y3_conv_schedule', (8, 52, 52, 128, 0, 256, 3, 1), (0, 1), 0, 1),
+    ('y3_conv_schedule', (8, 52, 52, 128, 0, 256, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 37, 37, 64, 0, 128, 3, 1), (0,), 0, 33),
+    ('y3_conv_workspace_bytes', (3, 37, 37, 64, 0, 128, 3, 1), (), 0, 33556480),
+    ('y3_conv_schedule', (3, 37, 37, 64, 0, 128, 3, 1), (0, 1), 0, 1),
+    ('y3_conv_schedule', (3, 37, 37, 64, 0, 128, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (2, 90, 92, 256, 0, 128, 3, 2), (0,), 0, 33),
+    ('y3_conv_workspace_bytes', (2, 90, 92, 256, 0, 128, 3, 2), (), 0, 33556480),
+    ('y3_conv_schedule', (2, 90, 92, 256, 0, 128, 3, 2), (0, 1), 0, 1),
+    ('y3_conv_schedule', (2, 90, 92, 256, 0, 128, 3, 2), (0, 0), 0, 0),
+    ('y3_conv_stats_blocks', (3, 27, 51, 32, 0, 1024, 1, 1), (0,), 0, 65),
+    ('y3_conv_workspace_bytes', (3, 27, 51, 32, 0, 1024, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (3, 27, 51, 32, 0, 1024, 1, 1), (0, 1), 0, 2),
+    ('y3_conv_schedule', (3, 27, 51, 32, 0, 1024, 1, 1), (0, 0), 0, 2),
+    ('y3_conv_stats_blocks', (2, 128, 130, 64, 32, 128, 1, 1), (0,), 0, 0),
+    ('y3_conv_workspace_bytes', (2, 128, 130, 64, 32, 128, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (2, 128, 130, 64, 32, 128, 1, 1), (0, 1), 0, 2),
+    ('y3_conv_schedule', (2, 128, 130, 64, 32, 128, 1, 1), (0, 0), 0, 2),
+    ('y3_conv_stats_blocks', (4, 64, 65, 32, 0, 255, 1, 1), (0,), 0, 0),
+    ('y3_conv_workspace_bytes', (4, 64, 65, 32, 0, 255, 1, 1), (), 0, 0),
+    ('y3_conv_schedule', (4, 64, 65, 32, 0, 255, 1, 1), (0, 1), 0, 2),
+    ('y3_conv_schedule', (4, 64, 65, 32, 0, 255, 1, 1), (0, 0), 0, 2),
+    ('y3_conv_stats_blocks', (32, 52, 52, 3, 0, 32, 3, 1), (0,), 0, 0),
+    ('y3_conv_workspace_bytes', (32, 52, 52, 3, 0, 32, 3, 1), (), 0, 0),
+    ('y3_conv_schedule', (32, 52, 52, 3, 0, 32, 3, 1), (0, 1), 0, 0),
+    ('y3_conv_schedule', (32, 52, 52, 3, 0, 32, 3, 1), (0, 0), 0, 0),
+    ('y3_conv_dgrad_bn_blocks', (3, 20, 28, 128, 0, 64, 1, 1), (), 0, 27),
+    ('y3_conv_dgrad_bn_blocks', (3, 20, 28, 128, 0, 128, 1, 1), (), 0, 27),
+    ('y3_conv_dgrad_bn_blocks', (3, 20, 28, 64, 0, 128, 1, 1), (), 0, 14),
+    ('y3_conv_dgrad_bn_blocks', (3, 20, 28, 32, 0, 64, 1, 1), (), 0, 14),
+    ('y3_conv_stats_blocks', (3, 13, 13, 64, 0, 128, 3, 1), (1,), 0, 3),
+    ('y3_conv_stats_blocks', (3, 13, 13, 64, 0, 128, 3, 1), (2,), 0, 3),
+    ('y3_conv_train_stats_blocks_bf16', (2, 8, 8, 64, 0, 128, 3, 1), (), 0, 1),
+    ('y3_conv_train_stats_blocks_bf16', (1, 3, 43, 64, 0, 128, 3, 1), (), 0, 2),
+    ('y3_conv_train_stats_blocks_bf16', (2, 8, 8, 64, 0, 128, 1, 1), (), 0, 1),
+    ('y3_conv_train_stats_blocks_bf16', (1, 3, 43, 64, 0, 32, 1, 1), (), 0, 2),
+    ('y3_conv_schedule', (2, 45, 46, 256, 0, 128, 3, 1), (1, 1), 0, 0),
+    ('y3_conv_schedule', (2, 45, 46, 256, 0, 128, 3, 1), (1, 0), 0, 0),
+    ('y3_conv_schedule', (2, 45, 46, 256, 0, 128, 3, 1), (2, 1), 0, 1),
+    ('y3_conv_schedule', (2, 45, 46, 256, 0, 128, 3, 1), (2, 0), 0, 0),
+    ('y3_conv_schedule', (2, 45, 46, 256, 0, 128, 3, 1), (4, 1), 0, 1),
+    ('y3_conv_schedule', (2, 45, 46, 256, 0, 128, 3, 1), (4, 0), 0, 0),
+    ('y3_conv_schedule', (4, 45, 46, 256, 0, 128, 3, 1), (1, 1), 0, 1),
+    ('y3_conv_schedule', (4, 45, 46, 256, 0, 128, 3, 1), (1, 0), 0, 0),
+    ('y3_conv_schedule', (4, 45, 46, 256, 0, 128, 3, 1), (2, 1), 0, 1),
+    ('y3_conv_schedule', (4, 45, 46, 256, 0, 128, 3, 1), (2, 0), 0, 0),
+    ('y3_conv_schedule', (4, 45, 46, 256, 0, 128, 3, 1), (4, 1), 0, 1),
+    ('y3_conv_schedule', (4, 45, 46, 256, 0, 128, 3, 1), (4, 0), 0, 0),
+    ('y3_conv_schedule', (2, 6, 6, 256, 0, 64, 3, 1), (1, 1), 0, 0),
+    ('y3_conv_schedule', (2, 6, 6, 256, 0, 64, 3, 1), (1, 0), 0, 0),
+    ('y3_conv_schedule', (2, 6, 6, 256, 0, 64, 3, 1), (2, 1), 0, 0),
+    ('y3_conv_schedule', (2, 6, 6, 256, 0, 64, 3, 1), (2, 0), 0, 0),
+    ('y3_conv_schedule', (2, 6, 6, 256, 0, 64, 3, 1), (4, 1), 0, 0),
+    ('y3_conv_schedule', (2, 6, 6, 256, 0, 64, 3, 1), (4, 0), 0, 0),
+    ('y3_conv_stats_blocks', (8, 52, 52, 128, 0, 256, 3, 1), (0,), 2768897, 170),
+    ('y3_conv_schedule', (8, 52, 52, 128, 0, 256, 3, 1), (0, 1), 2768897, 0),
+    ('y3_conv_workspace_bytes', (8, 52, 52, 128, 0, 256, 3, 1), (), 2768897, 0),
+    ('y3_conv_stats_blocks', (4, 20, 28, 64, 0, 128, 1, 1), (0,), 143361, 36),
+    ('y3_conv_schedule', (4, 20, 28, 64, 0, 128, 1, 1), (0, 1), 143361, 0),
+    ('y3_conv_workspace_bytes', (4, 20, 28, 64, 0, 128, 1, 1), (), 143361, 0),
+    ('y3_conv_stats_blocks', (4, 20, 28, 64, 0, 64, 3, 2), (0,), 71681, 6),
+    ('y3_conv_schedule', (4, 20, 28, 64, 0, 64, 3, 2), (0, 1), 71681, 0),
+    ('y3_conv_workspace_bytes', (4, 20, 28, 64, 0, 64, 3, 2), (), 71681, 0),
+    ('y3_conv_dgrad_bn_blocks', (4, 20, 28, 128, 0, 64, 1, 1), (), 143361, 36),
+]

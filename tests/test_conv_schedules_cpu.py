@@ -76,3 +76,22 @@ def test_schedule_query_rejects_what_no_launcher_takes(L):
     # the forward 3x3 convs of the 52 grid at batch 8 and 32 (what y3_net_layer_is_streamk reports per layer)
     assert C.schedule(L, 8, 52, 52, 128, 0, 256, 3, 1, 0, 1) == C.STREAMK
     assert C.schedule(L, 8, 52, 52, 128, 0, 256, 3, 1, 0, 0) == C.ONE_PER_TILE
+
+
+def test_host_answers_are_the_recorded_ones(L):
+    """The row-block counts, schedules and workspace sizes the net sizes its buffers by, against the table recorded ahead of
+    the one-tile-table refactor (conv_schedule_cases.HOST_ANSWERS): a retile that changes a launcher and not the count that
+    goes with it, or the other way round, shows up here at every branch of the ladders, without a device."""
+    wrong = []
+    for fn, shape, extra, limit, want in C.HOST_ANSWERS:
+        if limit:
+            L.y3_debug_conv_range_limit(limit)
+        try:
+            got = getattr(L, fn)(ctypes.byref(C.desc(*shape)), *extra)
+        finally:
+            if limit:
+                L.y3_debug_conv_range_limit(0)
+        if got != want:
+            wrong.append((fn, shape, extra, limit, want, got))
+    assert not wrong, wrong
+    assert len(C.HOST_ANSWERS) == 134

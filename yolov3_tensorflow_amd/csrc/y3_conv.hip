@@ -26,7 +26,7 @@
 //     divide the 512 co-resident workgroups (tail quantisation cost 12-33 % there).  Split tiles are
 //     combined in a fixed order by a second small kernel, so results are deterministic.
 #include <cstdlib>
-#include "y3_conv_common.h"
+#include "y3_conv_host.h"
 
 namespace {
 using namespace y3conv;
@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(256, 2) conv_mfma_f32_kernel(const ConvArgs p)
     } else {
         // workgroup b runs on XCD b%8 (observed): give each XCD a contiguous eighth of the tile ids, and each of the XCD's
         // workgroups a contiguous, balanced run of WHOLE tiles of it - one tile when the grid has a workgroup per tile; with
-        // fewer workgroups than tiles (the resident-grid launch of the 1x1 convs, launch_data_parallel) a workgroup walks
+        // fewer workgroups than tiles (the resident-grid launch of the 1x1 convs, data_parallel_grid) a workgroup walks
         // its tiles, the next tile's first loads issued under the current tile's epilogue
         const int nt = gridDim.x;
         const int x = blockIdx.x & 7, k = blockIdx.x >> 3;
@@ -337,101 +337,67 @@ __global__ void __launch_bounds__(256, 2) conv_mfma_f32_kernel(const ConvArgs p)
     }
 }
 
+// The exact kernel's tile table: the launches, y3_conv_schedule and the row-block counts of the statistics outputs
+// (y3_conv_stats_blocks mode 0, y3_conv_dgrad_bn_blocks) all ask here.
+constexpr Tile direct_tile(int ks, bool tmode, int cout) {
+    if (cout <= 32) return {128, 32, 4, 1};
+    if (cout <= 64) return {128, 64, 4, 1};
+    // 1x1 layers have 8-32 K-steps per tile: 64x64 tiles (37 KB of LDS, 72 VGPRs -> 4 workgroups per CU) hide one
+    // tile's prologue/epilogue under its neighbours' MFMAs and quantise the 172-1352-tile grids of the network 4x
+    // finer (measured, batch 32: 52x52 -10 %, 26x26 -19 %, 13x13 -21 % against the 128x128 tile)
+    if (ks == 1 && !tmode) return {64, 64, 2, 2};
+    return {128, 128, 2, 2};
+}
+
 constexpr int RESIDENT_64 = 1024;      // 64x64-tile workgroups resident at once: four per CU (37 KB of LDS, 72 VGPRs)
 
-// Grid of a data-parallel launch over `tiles` BM x BN tiles: one workgroup per tile, or the resident walk below.
-inline int data_parallel_grid(int bm, int bn, int tiles) {
+// Grid of a data-parallel launch over `tiles` tiles: one workgroup per tile, or the resident walk below.
+inline int data_parallel_grid(const Tile& t, int tiles) {
     // 64x64 tiles (the 1x1 convs), more tiles than the 1,024 resident workgroups but only a few rounds of them: a RESIDENT
     // grid whose workgroups walk balanced runs of whole tiles.  The hardware dispatcher hands the tiles of a partly filled
     // last round to the first slots that come free - four per CU on a quarter of the CUs while the rest idle (measured on
     // the F(4x4) kernel: 1.5 rounds cost 2, tools/wino44_quant.py); a resident grid spreads them one or two per CU, and
     // a workgroup fetches its next tile under the current one's store tail.
-    if (bm == 64 && bn == 64 && tiles > RESIDENT_64 && tiles < 8 * RESIDENT_64 && y3_exp_env("Y3_CONV_RESIDENT_OFF") == nullptr)
+    if (t.bm == 64 && t.bn == 64 && tiles > RESIDENT_64 && tiles < 8 * RESIDENT_64 && y3_exp_env("Y3_CONV_RESIDENT_OFF") == nullptr)
         return RESIDENT_64;
     return tiles;
 }
 
-// query != nullptr: nothing is launched; *query = the schedule this launch would take (y3_conv_schedule: 0 or 2)
-template <int BM, int BN, int WGM, int WGN, int KS, bool UPCAT, bool TMODE = false, bool STATS = false, bool BSTATS = false>
-int launch_data_parallel(hipStream_t stream, const ConvArgs& a, int* query = nullptr) {
-    using G = Geo<BM, BN, WGM, WGN>;
-    const int nbm = (a.M + BM - 1) / BM;
-    const int nbn = (a.Cout + BN - 1) / BN;
-    const int grid = data_parallel_grid(BM, BN, nbm * nbn);
-    if (query) {
-        *query = grid != nbm * nbn ? 2 : 0;
-        return Y3_OK;
+struct DirectFamily {
+    static constexpr int KDIV = BK;
+    static constexpr bool FORMS = true, TILE_64 = true;
+    static constexpr Tile tile(int ks, bool tmode, int cout) { return direct_tile(ks, tmode, cout); }
+    static int grid(const Tile& t, int tiles) { return data_parallel_grid(t, tiles); }
+    template <int BM, int BN, int WGM, int WGN, int KS, bool UPCAT, bool STREAMK, bool TMODE, bool STATS, bool BSTATS>
+    static int launch(hipStream_t stream, int grid, const ConvArgs& a) {
+        return y3_launch_lds<conv_mfma_f32_kernel<BM, BN, WGM, WGN, KS, UPCAT, STREAMK, TMODE, STATS, BSTATS>>(
+            stream, dim3(grid), dim3(256), Geo<BM, BN, WGM, WGN>::LDS_BYTES, a);
     }
-    auto kern = conv_mfma_f32_kernel<BM, BN, WGM, WGN, KS, UPCAT, false, TMODE, STATS, BSTATS>;
-    static bool attr_set[Y3_MAX_DEVICES] = {};  // per instantiation; benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        if (int rc = set_lds_attr(kern, G::LDS_BYTES)) return rc;
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), G::LDS_BYTES, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
-}
-
-template <int KS, bool TMODE = false, bool STATS = false>
-int launch_streamk(hipStream_t stream, const ConvArgs& a) {
-    constexpr int BM = 128, BN = 128, WGM = 2, WGN = 2;
-    using G = Geo<BM, BN, WGM, WGN>;
-    auto kern = conv_mfma_f32_kernel<BM, BN, WGM, WGN, KS, false, true, TMODE, STATS>;
-    static bool attr_set[Y3_MAX_DEVICES] = {};
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        if (int rc = set_lds_attr(kern, G::LDS_BYTES)) return rc;
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.workers), dim3(256), G::LDS_BYTES, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
-}
-
-template <int KS, bool UPCAT, bool TMODE = false, bool STATS = false, bool BSTATS = false>
-int dispatch_bn(hipStream_t stream, const ConvArgs& a, int* query = nullptr) {
-    if (a.Cout <= 32) return launch_data_parallel<128, 32, 4, 1, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
-    if (a.Cout <= 64) return launch_data_parallel<128, 64, 4, 1, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
-    // 1x1 layers have 8-32 K-steps per tile: 64x64 tiles (37 KB of LDS, 72 VGPRs -> 4 workgroups per CU) hide one
-    // tile's prologue/epilogue under its neighbours' MFMAs and quantise the 172-1352-tile grids of the network 4x
-    // finer (measured, batch 32: 52x52 -10 %, 26x26 -19 %, 13x13 -21 % against the 128x128 tile)
-    if (KS == 1 && !TMODE) return launch_data_parallel<64, 64, 2, 2, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
-    static_assert(!BSTATS || KS == 1, "the fused BN backward reduction exists on the small tiles of the 1x1 data gradient only");
-    return launch_data_parallel<128, 128, 2, 2, KS, UPCAT, TMODE, STATS, BSTATS>(stream, a, query);
-}
+};
 
 }  // namespace
 
 // The schedule a launch of `conv` takes: 0 = one workgroup per tile, 1 = stream-K, 2 = the resident walk.  `conv` is the conv
 // as launched (a data gradient: [n,h,w,dz_stride] -> fwd cin at stride 1); tmode_taps = 1/2/4: one parity class of a stride-2
-// data gradient.  Host arithmetic only: use_streamk and the launchers' own grid choice, asked without launching.
+// data gradient.  Host arithmetic only: use_streamk, the tile table and the launcher's own grid choice.
 int y3_conv_schedule_query(const y3_conv_desc* d, int tmode_taps, int with_workspace) {
     if (!d || (d->k != 1 && d->k != 3) || (d->stride != 1 && d->stride != 2) || d->n <= 0 || d->h <= 0 || d->w <= 0 ||
         d->cin <= 0 || d->cout <= 0 || d->cin == 3)
         return 0;                                   // (the stem: one thread per pixel)
     if (tmode_taps != 0 && (d->k != 3 || d->stride != 1 || d->c_up > 0 || (tmode_taps != 1 && tmode_taps != 2 && tmode_taps != 4)))
         return 0;
+    if (d->c_up > 0 && d->k != 1) return 0;
     // A cut launch (image ranges) answers for its first range, the largest, and never takes stream-K: the ranges run without
     // a workspace.  The tensors of a parity class: the coarse gradient [n,h,w,cin] and the 2x finer output [n,2h,2w,cout].
     y3_conv_desc whole = *d;
     if (tmode_taps) { whole.h = 2 * d->h; whole.w = 2 * d->w; whole.cin = d->cout; whole.cout = d->cin; whole.stride = 2; }
     const y3_image_ranges rg(&whole, 0);
     if (rg.n < 0) return 0;
-    if (rg.n > 1) with_workspace = 0;
-    ConvArgs a{};        // (value-initialised: use_streamk reads Cin, xu, tmode and ntaps too)
-    a.Cin = d->cin;
-    a.Cout = d->cout;
-    a.M = rg.count[0] * (d->h / d->stride) * (d->w / d->stride);
-    a.tmode = tmode_taps ? 1 : 0;
-    a.ntaps = tmode_taps;
-    int s = 0;
-    if (d->c_up > 0) return d->k == 1 && dispatch_bn<1, true>(nullptr, a, &s) == Y3_OK ? s : 0;
-    if (d->k == 1) return dispatch_bn<1, false>(nullptr, a, &s) == Y3_OK ? s : 0;
-    if (use_streamk(a, 3, with_workspace != 0)) return 1;
-    const int rc = tmode_taps ? dispatch_bn<3, false, true>(nullptr, a, &s) : dispatch_bn<3, false>(nullptr, a, &s);
-    return rc == Y3_OK ? s : 0;
+    const int M = rg.count[0] * (d->h / d->stride) * (d->w / d->stride);
+    if (d->k == 3 && use_streamk(M, d->cin, d->cout, tmode_taps ? tmode_taps : 9, with_workspace != 0 && rg.n == 1)) return 1;
+    const Tile t = direct_tile(d->k, tmode_taps != 0, d->cout);
+    const int tiles = tile_count(t, M, d->cout);
+    return data_parallel_grid(t, tiles) != tiles ? 2 : 0;
 }
 
 // 1 if y3_launch_conv would pick the stream-K schedule for this conv when given a workspace.
@@ -457,106 +423,42 @@ int y3_launch_conv(hipStream_t stream, const y3_conv_desc* d, const float* x, co
                    const float* w, const float* scale, const float* shift, const float* residual,
                    float* y, void* workspace, size_t workspace_bytes, const y3_sk_opts* sk) {
     Y3_CHECK_ARG(d && x && w && scale && shift && y, "y3_conv2d_fwd: null pointer argument");
-    Y3_CHECK_ARG(d->k == 1 || d->k == 3, "y3_conv2d_fwd: kernel_size must be 1 or 3 (got %d)", d->k);
-    Y3_CHECK_ARG(d->stride == 1 || d->stride == 2, "y3_conv2d_fwd: stride must be 1 or 2 (got %d)",
-                 d->stride);
-    Y3_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0,
-                 "y3_conv2d_fwd: non-positive dimension");
-    Y3_CHECK_ARG(!(d->stride == 2 && (d->h % 2 || d->w % 2)),
-                 "y3_conv2d_fwd: stride-2 conv needs even H,W (got %dx%d)", d->h, d->w);
-    Y3_CHECK_ARG((x_up != nullptr) == (d->c_up > 0), "y3_conv2d_fwd: x_up and c_up must agree");
-    ConvArgs a;
-    a.x = x; a.xu = x_up; a.w = w; a.scale = scale; a.shift = shift; a.resid = residual; a.y = y;
-    a.partial = nullptr; a.flags = nullptr; a.workers = 0; a.wrev = 0; a.tmode = 0; a.cy = a.cx = 0; a.ntaps = 0;
-    a.err = nullptr; a.spin_limit = 0; a.fault = 0; a.stats = nullptr; a.bz = nullptr; a.bvec = nullptr;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Cu = d->c_up; a.Cx = d->cin - d->c_up;
-    a.Cout = d->cout; a.stride = d->stride; a.pad = d->k / 2; a.act = d->act;
-    a.Ho = d->h / d->stride; a.Wo = d->w / d->stride;
-    const long long M = (long long)d->n * a.Ho * a.Wo;
+    if (int rc = check_conv_desc(d, x_up, "y3_conv2d_fwd", DirectFamily::KDIV)) return rc;
+    ConvArgs a = conv_args(d, x, x_up, w, scale, shift, residual, y);
     a.stats = sk ? sk->stats : nullptr;
     Y3_CHECK_ARG(!a.stats || (d->cin != 3 && !x_up && d->cout % 4 == 0),
                  "y3_conv2d_fwd_stats: statistics need Cin != 3, no fused upsample input and Cout %% 4 == 0");
-    const y3_image_ranges rg(d, 0);
-    if (rg.n < 0) return rg.n;
-    if (rg.n > 1) {
-        // A tensor of 2^29 elements or more: the same launch per image range, every pointer advanced by whole images, the
-        // statistics rows of a range behind the previous range's (y3_conv_stats_blocks counts them the same way).  A cut
-        // launch never takes the stream-K schedule - the ranges get no workspace: one set of flag words and accumulator
-        // slots serves one launch.
-        y3_sk_opts o;
-        if (sk) o = *sk;
-        o.flags = nullptr;
-        for (int i = 0; i < rg.n; ++i) {
-            y3_conv_desc dr = *d;
-            dr.n = rg.count[i];
-            const size_t b = (size_t)rg.begin[i];
-            const size_t out = b * a.Ho * a.Wo * d->cout;
-            if (int rc = y3_launch_conv(stream, &dr, x + b * d->h * d->w * a.Cx, x_up ? x_up + b * (d->h / 2) * (d->w / 2) * a.Cu : nullptr,
-                                        w, scale, shift, residual ? residual + out : nullptr, y + out, nullptr, 0, &o))
-                return rc;
-            if (o.stats) o.stats += (size_t)y3_conv_stats_blocks_impl(&dr, 0) * 2 * d->cout;
+    const int k = d->k;
+    return walk_image_ranges(y3_image_ranges(d, 0), a, direct_tile(k, false, d->cout).bm, [&](ConvArgs& r, bool whole) -> int {
+        if (r.Cin == 3) {
+            Y3_CHECK_ARG(k == 3 && r.Cout == 32 && !r.xu && !r.resid,
+                         "y3_conv2d_fwd: Cin=3 is supported only as the 3x3 3->32 stem conv");
+            auto stem = conv_stem_kernel<32>;
+            hipLaunchKernelGGL(stem, dim3((r.M + 255) / 256), dim3(256), 0, stream, r);
+            Y3_CHECK_HIP(hipGetLastError());
+            return Y3_OK;
         }
-        return Y3_OK;
-    }
-    a.M = (int)M;
-
-    if (d->cin == 3) {
-        Y3_CHECK_ARG(d->k == 3 && d->cout == 32 && !x_up && !residual,
-                     "y3_conv2d_fwd: Cin=3 is supported only as the 3x3 3->32 stem conv");
-        auto stem = conv_stem_kernel<32>;
-        hipLaunchKernelGGL(stem, dim3((a.M + 255) / 256), dim3(256), 0, stream, a);
-        Y3_CHECK_HIP(hipGetLastError());
-        return Y3_OK;
-    }
-    Y3_CHECK_ARG(d->cin % BK == 0, "y3_conv2d_fwd: Cin must be 3 or a multiple of %d (got %d)", BK,
-                 d->cin);
-    if (x_up) {
-        Y3_CHECK_ARG(d->k == 1 && d->stride == 1, "y3_conv2d_fwd: fused upsample+concat needs a 1x1 s1 conv");
-        Y3_CHECK_ARG(d->c_up % BK == 0 && d->c_up < d->cin && d->h % 2 == 0 && d->w % 2 == 0,
-                     "y3_conv2d_fwd: bad c_up=%d for cin=%d", d->c_up, d->cin);
-        return dispatch_bn<1, true>(stream, a);
-    }
-    if (d->k == 1) {
-        Y3_CHECK_ARG(d->stride == 1, "y3_conv2d_fwd: 1x1 conv must have stride 1");
-        return a.stats ? dispatch_bn<1, false, false, true>(stream, a) : dispatch_bn<1, false>(stream, a);
-    }
-    const bool has_ws = workspace != nullptr && workspace_bytes >= y3_conv_workspace_bytes_impl(d) &&
-                        ((uintptr_t)workspace & 15) == 0;
-    if (use_streamk(a, d->k, has_ws)) {
-        if (int rc = sk_prepare(stream, a, workspace, sk)) return rc;
-        return a.stats ? launch_streamk<3, false, true>(stream, a) : launch_streamk<3>(stream, a);
-    }
-    return a.stats ? dispatch_bn<3, false, false, true>(stream, a) : dispatch_bn<3, false>(stream, a);
+        return launch_conv_family<DirectFamily>(stream, r, k, whole ? workspace : nullptr, workspace_bytes, sk);
+    });
 }
 
-// Row blocks of the `stats` output (= output rows / the BM the dispatch above picks); the Winograd kernel: 64-tile blocks.
+// Row blocks of the `stats` output (= output rows / the BM of the tile table); wino = 1 / 2: the Winograd kernels' own counts.
 int y3_conv_stats_blocks_impl(const y3_conv_desc* d, int wino) {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cout % 4 != 0 || d->cin == 3 || d->c_up > 0) return 0;
     if (wino == 2) return y3_conv_wino44_stats_blocks_impl(d);
-    if (wino) {
-        if (!y3_conv_wino_eligible_impl(d)) return 0;
-        const long long T = (long long)d->n * ((d->h + 1) / 2) * ((d->w + 1) / 2);
-        return (int)((T + 63) / 64);
-    }
+    if (wino) return y3_conv_wino_stats_blocks_impl(d);
     if (!((d->k == 1 && d->stride == 1) || d->k == 3) || (d->stride != 1 && d->stride != 2)) return 0;
     if (d->cin <= 0 || d->cout <= 0) return 0;
-    const int bm = (d->k == 1 && d->cout > 64) ? 64 : 128;
-    // a cut launch (image ranges): every range starts a row block of its own, its rows behind the previous range's
-    const y3_image_ranges rg(d, 0);
-    long long nb = 0;
-    for (int i = 0; i < rg.n; ++i) nb += ((long long)rg.count[i] * (d->h / d->stride) * (d->w / d->stride) + bm - 1) / bm;
-    return (int)nb;                                  // (rg.n < 0, one image over the limit: 0, no such launch)
+    return range_row_blocks(y3_image_ranges(d, 0), (long long)(d->h / d->stride) * (d->w / d->stride),
+                            direct_tile(d->k, false, d->cout).bm);
 }
 
 // (dz rows of Cout rounded up to the K-step: what y3_launch_conv_dgrad asks of a cut launch with the fused reduction)
 int y3_conv_dgrad_stats_blocks_impl(const y3_conv_desc* fwd) {
     if (!fwd || fwd->k != 1 || fwd->stride != 1 || fwd->c_up != 0 || fwd->cin % 4 != 0) return 0;
     if (fwd->n <= 0 || fwd->h <= 0 || fwd->w <= 0 || fwd->cin <= 0 || fwd->cout <= 0) return 0;
-    const int bm = fwd->cin > 64 ? 64 : 128;        // dispatch_bn's tile for Cout' = fwd->cin
-    const y3_image_ranges rg(fwd, (fwd->cout + BK - 1) / BK * BK);
-    long long nb = 0;
-    for (int i = 0; i < rg.n; ++i) nb += ((long long)rg.count[i] * fwd->h * fwd->w + bm - 1) / bm;
-    return (int)nb;
+    return range_row_blocks(y3_image_ranges(fwd, (fwd->cout + BK - 1) / BK * BK), (long long)fwd->h * fwd->w,
+                            direct_tile(1, false, fwd->cin).bm);
 }
 
 // Data gradient of a conv layer as a forward conv over dz:
@@ -575,79 +477,23 @@ int y3_launch_conv_dgrad(hipStream_t stream, const y3_conv_desc* fwd, const floa
     Y3_CHECK_ARG(fwd->c_up == 0, "y3_conv2d_dgrad: fused upsample+concat inputs are not supported");
     Y3_CHECK_ARG(dz_stride >= fwd->cout && dz_stride % BK == 0, "y3_conv2d_dgrad: dz stride must be a multiple of %d", BK);
     Y3_CHECK_ARG(fwd->cin % 4 == 0, "y3_conv2d_dgrad: Cin must be a multiple of 4");
-    const int Ho = fwd->h / fwd->stride, Wo = fwd->w / fwd->stride;
-    ConvArgs a;
-    a.x = dz; a.xu = nullptr; a.w = w_d; a.scale = ones; a.shift = zeros;
-    a.resid = accumulate ? dx : nullptr; a.y = dx; a.partial = nullptr; a.flags = nullptr; a.workers = 0;
-    a.err = nullptr; a.spin_limit = 0; a.fault = 0; a.stats = nullptr; a.bz = nullptr; a.bvec = nullptr;
-    a.wrev = 1; a.tmode = 0; a.cy = a.cx = 0; a.ntaps = 0;
-    a.N = fwd->n; a.H = Ho; a.W = Wo; a.Cin = dz_stride; a.Cu = 0; a.Cx = dz_stride;
-    a.Cout = fwd->cin; a.stride = 1; a.pad = fwd->k / 2; a.act = 0;
-    a.Ho = fwd->h; a.Wo = fwd->w;
-    const long long M = (long long)fwd->n * fwd->h * fwd->w;
     Y3_CHECK_ARG(fwd->n > 0 && fwd->h > 0 && fwd->w > 0 && fwd->cin > 0 && fwd->cout > 0, "y3_conv2d_dgrad: non-positive dimension");
+    const y3_conv_desc g = dgrad_desc(fwd, dz_stride);
+    ConvArgs a = conv_args(&g, dz, nullptr, w_d, ones, zeros, accumulate ? dx : nullptr, dx);
+    a.wrev = 1;
+    if (fwd->stride == 2) { a.tmode = 1; a.Ho = fwd->h; a.Wo = fwd->w; }
     const y3_image_ranges rg(fwd, dz_stride);
     if (rg.n < 0) return rg.n;
-    if (rg.n > 1) {
-        // image ranges, as in y3_launch_conv: dz, dx (and the fused reduction's z) advance by whole images, the partial rows of
-        // a range lie behind the previous range's (y3_conv_dgrad_bn_blocks), and no range takes stream-K (no workspace)
-        y3_sk_opts o;
-        if (sk) o = *sk;
-        o.flags = nullptr;
-        Y3_CHECK_ARG(!o.bwd_z || dz_stride == (fwd->cout + BK - 1) / BK * BK,
-                     "y3_conv2d_dgrad: the fused BN reduction of a launch cut into image ranges needs dz rows of Cout rounded up to %d", BK);
-        for (int i = 0; i < rg.n; ++i) {
-            y3_conv_desc fr = *fwd;
-            fr.n = rg.count[i];
-            const size_t b = (size_t)rg.begin[i];
-            const size_t in = b * fwd->h * fwd->w * fwd->cin;
-            if (int rc = y3_launch_conv_dgrad(stream, &fr, dz + b * Ho * Wo * dz_stride, dz_stride, w_d, ones, zeros, accumulate,
-                                              dx + in, nullptr, 0, &o))
-                return rc;
-            if (o.bwd_z) {
-                o.bwd_z += (size_t)fr.n * fwd->h * fwd->w * fwd->cin;
-                o.stats += (size_t)y3_conv_dgrad_stats_blocks_impl(&fr) * 2 * fwd->cin;
-            }
-        }
-        return Y3_OK;
+    // (a cut launch: the partial rows of a range lie behind the previous range's, as y3_conv_dgrad_bn_blocks counts them)
+    Y3_CHECK_ARG(rg.n == 1 || !sk || !sk->bwd_z || dz_stride == (fwd->cout + BK - 1) / BK * BK,
+                 "y3_conv2d_dgrad: the fused BN reduction of a launch cut into image ranges needs dz rows of Cout rounded up to %d", BK);
+    if (fwd->k == 1 && sk && sk->bwd_z) {
+        // this gradient is the dy of a BN layer: its backward reduction rides in the epilogue (y3_sk_opts::bwd_*)
+        Y3_CHECK_ARG(sk->bwd_vec && sk->stats, "y3_conv2d_dgrad: the fused BN reduction needs z, the layer's vectors and the partial rows");
+        a.bz = sk->bwd_z; a.bvec = sk->bwd_vec; a.stats = sk->stats;
     }
-    a.M = (int)M;
-    if (fwd->k == 1) {
-        if (sk && sk->bwd_z) {
-            // this gradient is the dy of a BN layer: its backward reduction rides in the epilogue (y3_sk_opts::bwd_*)
-            Y3_CHECK_ARG(sk->bwd_vec && sk->stats, "y3_conv2d_dgrad: the fused BN reduction needs z, the layer's vectors and the partial rows");
-            a.bz = sk->bwd_z; a.bvec = sk->bwd_vec; a.stats = sk->stats;
-            return dispatch_bn<1, false, false, false, true>(stream, a);
-        }
-        return dispatch_bn<1, false>(stream, a);
-    }
-    const bool has_ws = workspace != nullptr && workspace_bytes >= SK_WORKSPACE_BYTES &&
-                        ((uintptr_t)workspace & 15) == 0;
-    if (fwd->stride == 2) {
-        // four output parity classes, each a dense conv over N*Ho*Wo rows with 1/2/2/4 taps
-        a.tmode = 1;
-        a.M = (int)((long long)fwd->n * Ho * Wo);
-        for (int cls = 0; cls < 4; ++cls) {
-            a.cy = cls >> 1; a.cx = cls & 1;
-            a.ntaps = (a.cy ? 2 : 1) * (a.cx ? 2 : 1);
-            a.partial = nullptr; a.workers = 0;
-            int rc;
-            if (use_streamk(a, 3, has_ws)) {
-                // (the four parity-class launches share the workspace's own flag words: zeroed ahead of each)
-                y3_sk_opts o;
-                o.err = sk ? sk->err : nullptr;
-                rc = sk_prepare(stream, a, workspace, &o);
-                if (rc == Y3_OK) rc = launch_streamk<3, true>(stream, a);
-            } else {
-                rc = dispatch_bn<3, false, true>(stream, a);
-            }
-            if (rc != Y3_OK) return rc;
-        }
-        return Y3_OK;
-    }
-    if (use_streamk(a, 3, has_ws)) {
-        if (int rc = sk_prepare(stream, a, workspace, sk)) return rc;
-        return launch_streamk<3>(stream, a);
-    }
-    return dispatch_bn<3, false>(stream, a);
+    const int k = fwd->k;
+    return walk_image_ranges(rg, a, direct_tile(1, false, fwd->cin).bm, [&](ConvArgs& r, bool whole) -> int {
+        return launch_conv_family<DirectFamily>(stream, r, k, whole ? workspace : nullptr, workspace_bytes, sk);
+    });
 }

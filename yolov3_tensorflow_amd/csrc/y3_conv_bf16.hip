@@ -19,12 +19,9 @@
 #include <cstring>
 #include <type_traits>
 #include "y3_bf16.h"
+#include "y3_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct ConvArgsB {
     const bf16_t* x;     // [N,H,W,Cx]
@@ -65,7 +62,6 @@ __device__ __forceinline__ TrainFields train_fields(const ConvArgsT& p) {
 
 constexpr int BKB = 32;            // K elements per step
 constexpr int LDB = 64;            // LDS row stride in bytes (unpadded; 16-byte slots swizzled, see lds_off)
-constexpr unsigned OOB = 0x80000000u;
 
 // LDS byte offset of 16-byte slot `slot` (0..3) of row `row`: four rows share one 256-byte bank row, so the slot is
 // flipped by (row/4)%4 and 16 consecutive rows of one logical slot land on 16 different bank groups.
@@ -682,49 +678,39 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w_hwio, bf16_
     }
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, bool UPCAT>
-int launch_b(hipStream_t stream, const ConvArgsB& a) {
-    auto kern = conv_mfma_bf16_kernel<BM, BN, WGM, WGN, KS, UPCAT>;
+// One workgroup per BM x BN tile, for the inference (ConvArgsB) and the training (ConvArgsT) instantiations alike
+template <auto Kern, int BM, int BN, typename Args>
+int launch_tiles(hipStream_t stream, const Args& a) {
     constexpr size_t tiles = (size_t)2 * (BM + BN) * LDB, stage = (size_t)64 * (BN + 4) * 4;
     constexpr size_t lds = tiles > stage ? tiles : stage;
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(Kern, dim3(nbm * nbn), dim3(256), lds, stream, a);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }
 
 template <int KS, bool UPCAT>
 int dispatch_b(hipStream_t stream, const ConvArgsB& a) {
-    if (a.Cout <= 32) return launch_b<128, 32, 4, 1, KS, UPCAT>(stream, a);
-    if (a.Cout <= 64) return launch_b<128, 64, 4, 1, KS, UPCAT>(stream, a);
+    if (a.Cout <= 32) return launch_tiles<conv_mfma_bf16_kernel<128, 32, 4, 1, KS, UPCAT>, 128, 32>(stream, a);
+    if (a.Cout <= 64) return launch_tiles<conv_mfma_bf16_kernel<128, 64, 4, 1, KS, UPCAT>, 128, 64>(stream, a);
     if (KS == 1) {
         // 1x1 convs whose 128x128 tiles would not fill two rounds of the 256 CUs (the 19-grid layers and the two route
         // convs at bs=16, 608x608: 184 / 46 tiles): 64x64 tiles, three workgroups per CU - 26.5 -> 21.9 us and 18.9 ->
         // 12.0 us per launch; from 512 tiles up the wide tile wins again (measured, tools/layer_profile.py)
         const long long tiles = (long long)((a.M + 127) / 128) * ((a.Cout + 127) / 128);
-        if (tiles < 512) return launch_b<64, 64, 2, 2, KS, UPCAT>(stream, a);
+        if (tiles < 512) return launch_tiles<conv_mfma_bf16_kernel<64, 64, 2, 2, KS, UPCAT>, 64, 64>(stream, a);
     }
-    return launch_b<128, 128, 2, 2, KS, UPCAT>(stream, a);
+    return launch_tiles<conv_mfma_bf16_kernel<128, 128, 2, 2, KS, UPCAT>, 128, 128>(stream, a);
 }
 
-// The training forms (RouteKind::Bf16Train): the register-staged kernel at every shape, M tiles of 128 rows
-template <int BN, int WGM, int WGN, int KS, int EPI, bool TMODE>
-int launch_t(hipStream_t stream, const ConvArgsT& a) {
-    constexpr int BM = 128;
-    auto kern = conv_train_bf16_kernel<BM, BN, WGM, WGN, KS, EPI, TMODE>;
-    constexpr size_t tiles = (size_t)2 * (BM + BN) * LDB, stage = (size_t)64 * (BN + 4) * 4;
-    constexpr size_t lds = tiles > stage ? tiles : stage;
-    const int nbm = (a.M + BM - 1) / BM, nbn = (a.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(256), lds, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
-}
-
+// The training forms (RouteKind::Bf16Train): the register-staged kernel at every shape, M tiles of TRAIN_BM rows - the row
+// blocks of the forward's statistics (y3_conv_bf16_train_stats_blocks)
+constexpr int TRAIN_BM = 128;
 template <int KS, int EPI, bool TMODE>
 int dispatch_t(hipStream_t stream, const ConvArgsT& a) {
-    if (a.Cout <= 32) return launch_t<32, 4, 1, KS, EPI, TMODE>(stream, a);
-    if (a.Cout <= 64) return launch_t<64, 4, 1, KS, EPI, TMODE>(stream, a);
-    return launch_t<128, 2, 2, KS, EPI, TMODE>(stream, a);
+    if (a.Cout <= 32) return launch_tiles<conv_train_bf16_kernel<TRAIN_BM, 32, 4, 1, KS, EPI, TMODE>, TRAIN_BM, 32>(stream, a);
+    if (a.Cout <= 64) return launch_tiles<conv_train_bf16_kernel<TRAIN_BM, 64, 4, 1, KS, EPI, TMODE>, TRAIN_BM, 64>(stream, a);
+    return launch_tiles<conv_train_bf16_kernel<TRAIN_BM, 128, 2, 2, KS, EPI, TMODE>, TRAIN_BM, 128>(stream, a);
 }
 
 ConvArgsT args_t(const void* x, const void* w, void* y, int n, int h, int w_, int cin, int cout, int k, int stride, int pad,
@@ -760,7 +746,7 @@ __global__ void pack_weights_bf16_dgrad_kernel(const float* __restrict__ w_hwio,
 
 int y3_conv_bf16_train_stats_blocks(const y3_conv_desc* d) {
     const long long m = (long long)d->n * (d->h / d->stride) * (d->w / d->stride);
-    return (int)((m + 127) / 128);
+    return (int)((m + TRAIN_BM - 1) / TRAIN_BM);
 }
 
 // cin / cout: the channels the launch reads / writes (dgrad: it reads dz [n*ho*wo][cin], writes dx [n*h*w][cout])
@@ -824,7 +810,7 @@ int y3_pack_conv_weights_bf16_reg(y3_ctx* ctx, const float* w_hwio, int k, int c
     Y3_CHECK_ARG(k > 0 && cin > 0 && cout > 0 && red % BKB == 0 && (!dgrad_stride || dgrad_stride >= cout),
                  "y3_pack_conv_weights_bf16_reg: the reduction must be a positive multiple of %d", BKB);
     const size_t total = (size_t)k * k * red * (dgrad_stride ? cin : cout);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = y3_blocks_for(total);
     if (dgrad_stride)
         hipLaunchKernelGGL(pack_weights_bf16_dgrad_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w_hwio,
                            static_cast<bf16_t*>(w_packed), k * k, cin, cout, dgrad_stride);
@@ -890,7 +876,7 @@ extern "C" int y3_pack_conv_weights_bf16(y3_ctx* ctx, const float* w_hwio, int k
     if (y3_conv_bf16x_takes(k, cin) || y3_conv_bf16r_takes(k, cin))      // [tap][Cin/64][Cout][64]
         return y3_launch_pack_bf16x(ctx->stream, w_hwio, k, cin, cout, w_packed);
     const size_t total = (size_t)k * k * cin * cout;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = y3_blocks_for(total);
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w_hwio,
                        static_cast<bf16_t*>(w_packed), k * k, cin, cout);
     Y3_CHECK_HIP(hipGetLastError());

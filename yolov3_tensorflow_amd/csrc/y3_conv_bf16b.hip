@@ -20,19 +20,9 @@
 //            reused to stage the output, so that an output pixel's 128 bytes leave as eight 16-byte pieces of one line.
 #include <cstdlib>
 #include "y3_bf16.h"
+#include "y3_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds_base, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_base, 16, voff, soff, 0, 0);
-#endif
-}
 
 struct ResBlockArgs {
     const bf16_t* x;      // [N,H,W,64] bf16: input and shortcut
@@ -47,8 +37,7 @@ struct ResBlockArgs {
     int tiles_y, tiles_x, ntiles;
 };
 
-constexpr unsigned OOB = 0x80000000u;
-constexpr int TS = 16;                          // output tile side
+constexpr int TS = 16;                         // output tile side
 constexpr int PS = TS + 2;                      // patch side (18)
 constexpr int NPIX = PS * PS;                   // 324
 constexpr int NDMA = (NPIX + 7) / 8;            // DMA instructions per patch (8 pixels x 128 B each): 41
@@ -281,17 +270,8 @@ int y3_launch_conv_bf16_resblock64(hipStream_t stream, int n, int h, int w, cons
     a.N = n; a.H = h; a.W = w; a.act2 = act2; a.act3 = act3;
     a.tiles_y = (h + TS - 1) / TS; a.tiles_x = (w + TS - 1) / TS;
     a.ntiles = n * a.tiles_y * a.tiles_x;
-    static bool attr_set[Y3_MAX_DEVICES] = {};     // benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_resblock64_bf16_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
     const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    hipLaunchKernelGGL(conv_resblock64_bf16_kernel, dim3(grid), dim3(NTHR), LDS_BYTES, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return y3_launch_lds<conv_resblock64_bf16_kernel>(stream, dim3(grid), dim3(NTHR), LDS_BYTES, a);
 }
 
 extern "C" int y3_resblock64_fwd_bf16(y3_ctx* ctx, int n, int h, int w, const void* x, const void* w2_packed, const float* scale2,

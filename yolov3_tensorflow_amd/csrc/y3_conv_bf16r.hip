@@ -26,18 +26,9 @@
 //     on loads and stores retiring in order relative to each other).
 #include <cstdlib>
 #include "y3_bf16.h"
+#include "y3_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds_base, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_base, 16, voff, soff, 0, 0);
-#endif
-}
 
 struct ConvArgsR {
     const bf16_t* x;     // [N,H,W,Cx]
@@ -51,8 +42,6 @@ struct ConvArgsR {
     int act, out_f32;
     int M;
 };
-
-constexpr unsigned OOB = 0x80000000u;
 
 // slot of a 128-byte row that holds logical 16-byte chunk c: c ^ swz(row)
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
@@ -375,22 +364,13 @@ constexpr RTile rtile() {
 
 template <int MI, int NI, int WM, int WN, int NSTAGE, bool UPCAT>
 int launch_r(hipStream_t stream, const ConvArgsR& a) {
-    auto kern = conv1x1_bf16r_kernel<MI, NI, WM, WN, NSTAGE, UPCAT>;
     constexpr RTile t = rtile<MI, NI, WM, WN, NSTAGE>();
-    static bool attr_set[Y3_MAX_DEVICES] = {};     // per instantiation; benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, t.lds));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
     const int nbm = (a.M + t.bm - 1) / t.bm, nbn = (a.Cout + t.bn - 1) / t.bn;
     const long long ntiles = (long long)nbm * nbn;
     const int per_cu = 163840 / t.lds < 1 ? 1 : (163840 / t.lds > 4 ? 4 : 163840 / t.lds);
     const long long slots = 256LL * per_cu;
     const int grid = (int)(ntiles < slots ? ntiles : slots);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), t.lds, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return y3_launch_lds<conv1x1_bf16r_kernel<MI, NI, WM, WN, NSTAGE, UPCAT>>(stream, dim3(grid), dim3(256), t.lds, a);
 }
 
 int forced_rtile() {

@@ -29,12 +29,9 @@
 //            (now idle) stem-pixel LDS so that an output pixel's 128 bytes leave as eight 16-byte pieces of one line.
 #include <cstdlib>
 #include "y3_bf16.h"
+#include "y3_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct StemS2Args {
     const float* x;       // [N,H,W,3] fp32 image
@@ -301,17 +298,8 @@ int y3_launch_conv_bf16_stem_s2(hipStream_t stream, int n, int h, int w, const f
     a.N = n; a.H = h; a.W = w; a.act0 = act0; a.act1 = act1;
     a.tiles_y = (h / 2 + TS - 1) / TS; a.tiles_x = (w / 2 + TS - 1) / TS;
     a.ntiles = n * a.tiles_y * a.tiles_x;
-    static bool attr_set[Y3_MAX_DEVICES] = {};     // benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_s2_bf16_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
     const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    hipLaunchKernelGGL(conv_stem_s2_bf16_kernel, dim3(grid), dim3(NTHR), LDS_BYTES, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return y3_launch_lds<conv_stem_s2_bf16_kernel>(stream, dim3(grid), dim3(NTHR), LDS_BYTES, a);
 }
 
 extern "C" int y3_conv2d_fwd_bf16_stem_s2(y3_ctx* ctx, int n, int h, int w, const float* x, const float* w0_hwio,

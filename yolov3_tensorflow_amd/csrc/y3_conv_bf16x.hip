@@ -19,22 +19,9 @@
 #include <cstdlib>
 #include <type_traits>
 #include "y3_bf16.h"
+#include "y3_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-// 16 bytes per lane, global -> LDS without a register round trip: lane l's bytes land at lds_base + 16*l (lds_base is
-// wave-uniform), an out-of-range `voff` writes zeros.  (The builtin exists in the device pass only; hipcc's host pass
-// instantiates the kernel templates too and silently drops their launch stubs if it meets it there.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds_base, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_base, 16, voff, soff, 0, 0);
-#endif
-}
 
 struct ConvArgsX {
     const bf16_t* x;     // [N,H,W,Cx]
@@ -49,8 +36,6 @@ struct ConvArgsX {
     int stride, pad, act, out_f32;
     int M;
 };
-
-constexpr unsigned OOB = 0x80000000u;
 
 template <int BK>
 struct Swz {
@@ -679,37 +664,17 @@ __global__ void pack_weights_bf16x_kernel(const float* __restrict__ w_hwio, bf16
 
 template <int BM, int BN, int WM, int WN, int BK, int KS, bool UPCAT>
 int launch_x(hipStream_t stream, const ConvArgsX& a) {
-    auto kern = conv_bf16x_kernel<BM, BN, WM, WN, BK, KS, UPCAT>;
     constexpr size_t lds = (size_t)2 * (BM + BN) * BK * 2;
-    static bool attr_set[Y3_MAX_DEVICES] = {};     // per instantiation; benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(64 * WM * WN), lds, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return y3_launch_lds<conv_bf16x_kernel<BM, BN, WM, WN, BK, KS, UPCAT>>(stream, dim3(nbm * nbn), dim3(64 * WM * WN), lds, a);
 }
 
 template <int MI, int NI, int WM, int WN, int KS, bool UPCAT>
 int launch_p(hipStream_t stream, const ConvArgsX& a) {
-    auto kern = conv_bf16p_kernel<MI, NI, WM, WN, KS, UPCAT>;
     constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
     constexpr size_t lds = (size_t)2 * (BM + BN) * 128;
-    static bool attr_set[Y3_MAX_DEVICES] = {};     // per instantiation; benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(512), lds, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return y3_launch_lds<conv_bf16p_kernel<MI, NI, WM, WN, KS, UPCAT>>(stream, dim3(nbm * nbn), dim3(512), lds, a);
 }
 
 // Tile choice.  Candidates: A = 256x256, D = 192x256, B = 256x128, E = 192x128 (the pipelined kernel: eight waves, one
@@ -823,8 +788,7 @@ extern "C" int y3_conv_bf16_tile(const y3_conv_desc* d) {
 int y3_launch_pack_bf16x(hipStream_t stream, const float* w_hwio, int k, int cin, int cout, void* w_packed) {
     const int bk = cin % 64 == 0 ? 64 : 32;
     const size_t total = (size_t)k * k * cin * cout;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_weights_bf16x_kernel, dim3(blocks), dim3(256), 0, stream, w_hwio,
+    hipLaunchKernelGGL(pack_weights_bf16x_kernel, dim3(y3_blocks_for(total)), dim3(256), 0, stream, w_hwio,
                        static_cast<bf16_t*>(w_packed), k * k, cin, cout, bk);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;

@@ -3,7 +3,7 @@
 // in-kernel hand-off of cut tiles.
 #pragma once
 #include <cstdlib>
-#include "y3_internal.h"
+#include "y3_lds.h"
 
 namespace y3conv {
 
@@ -40,7 +40,6 @@ struct ConvArgs {
 
 constexpr int BK = 32;
 constexpr int LDK = BK + 4;
-constexpr unsigned OOB = 0x80000000u;  // any offset >= num_records reads as 0 through a buffer load
 
 template <int BM, int BN, int WGM, int WGN>
 struct Geo {
@@ -52,9 +51,6 @@ struct Geo {
     static_assert(MI >= 1 && NI >= 1, "wave tile must hold at least one 32x32 MFMA tile");
     static_assert((size_t)BM * LDC * sizeof(float) <= LDS_BYTES, "accumulator tile must fit in the LDS");
 };
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // four fp32 values -> NP planes of four bf16 values (8 bytes per plane).  Truncating split: every remainder is
 // exactly representable, so x1 + x2 + x3 == x for NP = 3; the last plane of NP = 2 rounds to nearest even.
@@ -380,7 +376,6 @@ __device__ __forceinline__ SkWorker sk_worker(int b, int tiles, int S, int worke
 }
 
 typedef __attribute__((address_space(1))) unsigned gu32;   // flags: agent-scope global atomics only
-typedef unsigned int sk_u32x4 __attribute__((ext_vector_type(4)));
 
 // Producer: this worker's accumulators of a cut tile's later K-range -> its slot, 16 B per lane write-through
 // (sc1: no release fence needed), every storing wave drains, then ONE lane raises the flag.
@@ -400,7 +395,7 @@ __device__ __forceinline__ void sk_publish(const ConvArgs& p, int worker,
             for (int g = 0; g < 4; ++g) {   // 16 bytes per lane: registers 4g..4g+3
                 const f32x4 v = {acc[mi][ni][4 * g], acc[mi][ni][4 * g + 1], acc[mi][ni][4 * g + 2],
                                  acc[mi][ni][4 * g + 3]};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sk_u32x4, v), rs,
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs,
                                                        (unsigned)((((mi * G::NI + ni) * 4 + g) * 256 + tid) * 16),
                                                        base, 16);   // aux 16 = sc1
             }
@@ -562,16 +557,16 @@ __global__ void __launch_bounds__(256) conv_stem_kernel(const ConvArgs p) {
     }
 }
 
-template <typename K>
-inline int set_lds_attr(K kern, size_t lds) {
-    Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return Y3_OK;
-}
+// A tile of a kernel family's ladder: BM x BN outputs, WGM x WGN waves.  Each family has ONE tile table (direct_tile in
+// y3_conv.hip, split_tile in y3_conv_split.hip): the launchers switch on its answer, and every count of row blocks that a
+// caller sizes a buffer by (statistics rows, the fused BN-backward partials) derives from the same function.
+struct Tile { int bm, bn, wgm, wgn; };
+constexpr int tile_count(const Tile& t, int M, int cout) { return ((M + t.bm - 1) / t.bm) * ((cout + t.bn - 1) / t.bn); }
+constexpr Tile SK_TILE = {128, 128, 2, 2};   // the stream-K instantiations of both families
 
 constexpr int SK_WORKERS = 512;  // 256 CUs x 2 co-resident 128x128 workgroups (73.7 KB LDS, 176 VGPRs)
 // stream-K scratch: one accumulator slot per worker, then one flag word per worker
-constexpr size_t SK_SLOT_BYTES = (size_t)128 * 128 * sizeof(float);
+constexpr size_t SK_SLOT_BYTES = (size_t)SK_TILE.bm * SK_TILE.bn * sizeof(float);
 constexpr size_t SK_FLAGS_OFFSET = (size_t)SK_WORKERS * SK_SLOT_BYTES;
 constexpr size_t SK_WORKSPACE_BYTES = SK_FLAGS_OFFSET + (size_t)SK_WORKERS * sizeof(unsigned);
 
@@ -591,20 +586,21 @@ inline int sk_prepare(hipStream_t stream, ConvArgs& a, void* workspace, const y3
     return Y3_OK;
 }
 
-// Schedule choice: stream-K for 3x3 convs on 128x128 tiles whose tile count is within a few multiples
-// of the co-resident workgroup count (tail quantisation dominates there); Y3_CONV_STREAMK=0/1 overrides
-// (experiment hook for tools/conv_bench.py).
-inline bool use_streamk(const ConvArgs& a, int k, bool has_ws) {
-    if (!has_ws || k != 3 || a.Cout < 128 || a.xu) return false;
+// Schedule choice for a 3x3 conv without a fused upsample input (the launchers ask for no other): stream-K on the SK_TILE
+// tiles where the tile count is within a few multiples of the co-resident workgroup count (tail quantisation dominates
+// there); `taps` = 9, or the taps of a stride-2 data gradient's parity class.  Y3_CONV_STREAMK=0/1 overrides (experiment hook
+// for tools/conv_bench.py).
+inline bool use_streamk(int M, int cin, int cout, int taps, bool has_ws) {
+    if (!has_ws || cout < 128) return false;
     static int force = -2;
     if (force == -2) {
         const char* e = y3_exp_env("Y3_CONV_STREAMK");
         force = e ? atoi(e) : -1;
     }
     if (force == 0) return false;
-    const int tiles = ((a.M + 127) / 128) * ((a.Cout + 127) / 128);
+    const int tiles = tile_count(SK_TILE, M, cout);
     // every worker of every XCD group gets at least one (tile, K-step) item, and a tile is cut into < 32 ranges
-    const long long S = (long long)(a.tmode ? a.ntaps : k * k) * (a.Cin / 32);
+    const long long S = (long long)taps * (cin / 32);
     if (tiles < 32 || (tiles / 8) * S < SK_WORKERS / 8) return false;   // (tiles/8 >= 4: a tile spans <= 18 ranges)
     if ((long long)tiles * S >= (1LL << 31)) return false;
     if (force == 1) return true;

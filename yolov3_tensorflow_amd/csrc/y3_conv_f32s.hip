@@ -24,11 +24,9 @@
 //            wave-private patch of the (now idle) stem-pixel LDS so that an output pixel's 128-byte half row leaves as
 //            eight 16-byte pieces.
 #include <cstdlib>
-#include "y3_internal.h"
+#include "y3_lds.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct StemS2F32Args {
     const float* x;       // [N,H,W,3] image
@@ -261,17 +259,8 @@ int y3_launch_conv_f32_stem_s2(hipStream_t stream, int n, int h, int w, const fl
     a.N = n; a.H = h; a.W = w; a.act0 = act0; a.act1 = act1;
     a.tiles_y = (h / 2 + TSY - 1) / TSY; a.tiles_x = (w / 2 + TSX - 1) / TSX;
     a.ntiles = n * a.tiles_y * a.tiles_x;
-    static bool attr_set[Y3_MAX_DEVICES] = {};     // benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_s2_f32_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
     const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    hipLaunchKernelGGL(conv_stem_s2_f32_kernel, dim3(grid), dim3(NTHR), LDS_BYTES, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return y3_launch_lds<conv_stem_s2_f32_kernel>(stream, dim3(grid), dim3(NTHR), LDS_BYTES, a);
 }
 
 extern "C" int y3_conv2d_fwd_stem_s2(y3_ctx* ctx, int n, int h, int w, const float* x, const float* w0_hwio, const float* scale0,

@@ -16,12 +16,10 @@
 // The same kernel computes the stride-1 data gradients of training (wrev: flipped kernel, transposed weight
 // packing).  Design notes, measurements and rejected variants: docs/history_r01_r05.md 4.3.
 #include <type_traits>
-#include "y3_conv_common.h"
+#include "y3_conv_host.h"
 
 namespace {
 using namespace y3conv;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int SBK = 16;    // K elements per K-step
 constexpr int SROW = 32;   // LDS bytes per tile row and plane: 16 bf16, the two 16-byte halves XOR-swizzled
@@ -298,59 +296,26 @@ __global__ void __launch_bounds__(256, 2) conv_mfma_split_kernel(const ConvArgs 
     }
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, bool UPCAT, int NP>
-int launch_dp(hipStream_t stream, const ConvArgs& a) {
-    auto kern = conv_mfma_split_kernel<BM, BN, WGM, WGN, KS, UPCAT, false, NP>;
-    constexpr size_t lds = split_lds_bytes<BM, BN, NP>();
-    static bool attr_set[Y3_MAX_DEVICES] = {};
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        if (int rc = set_lds_attr(kern, lds)) return rc;
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
-    const int nbm = (a.M + BM - 1) / BM;
-    const int nbn = (a.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(256), lds, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
-}
-
-template <int KS, int NP>
-int launch_sk(hipStream_t stream, const ConvArgs& a) {
-    constexpr int BM = 128, BN = 128, WGM = 2, WGN = 2;
-    auto kern = conv_mfma_split_kernel<BM, BN, WGM, WGN, KS, false, true, NP>;
-    constexpr size_t lds = split_lds_bytes<BM, BN, NP>();
-    static bool attr_set[Y3_MAX_DEVICES] = {};
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        if (int rc = set_lds_attr(kern, lds)) return rc;
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.workers), dim3(256), lds, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
-}
-
-template <int KS, bool UPCAT, int NP>
-int dispatch_bn(hipStream_t stream, const ConvArgs& a) {
-    if (a.Cout <= 32) return launch_dp<128, 32, 4, 1, KS, UPCAT, NP>(stream, a);
-    if (a.Cout <= 64) return launch_dp<128, 64, 4, 1, KS, UPCAT, NP>(stream, a);
-    return launch_dp<128, 128, 2, 2, KS, UPCAT, NP>(stream, a);
+// The split kernel's tile table: 128 rows, the column block by Cout (no 64x64 tile, no training forms)
+constexpr Tile split_tile(int cout) {
+    if (cout <= 32) return {128, 32, 4, 1};
+    if (cout <= 64) return {128, 64, 4, 1};
+    return {128, 128, 2, 2};
 }
 
 template <int NP>
-int launch_np(hipStream_t stream, const y3_conv_desc* d, ConvArgs& a, void* workspace, size_t workspace_bytes,
-              const y3_sk_opts* sk) {
-    if (a.xu) return dispatch_bn<1, true, NP>(stream, a);
-    if (d->k == 1) return dispatch_bn<1, false, NP>(stream, a);
-    const bool has_ws = workspace != nullptr && workspace_bytes >= y3_conv_workspace_bytes_impl(d) &&
-                        ((uintptr_t)workspace & 15) == 0;
-    if (use_streamk(a, d->k, has_ws)) {
-        if (int rc = sk_prepare(stream, a, workspace, sk)) return rc;
-        return launch_sk<3, NP>(stream, a);
+struct SplitFamily {
+    static constexpr int KDIV = 2 * SBK;       // a work item is a PAIR of K-steps
+    static constexpr bool FORMS = false, TILE_64 = false;
+    static constexpr Tile tile(int, bool, int cout) { return split_tile(cout); }
+    static int grid(const Tile&, int tiles) { return tiles; }
+    template <int BM, int BN, int WGM, int WGN, int KS, bool UPCAT, bool STREAMK, bool TMODE, bool STATS, bool BSTATS>
+    static int launch(hipStream_t stream, int grid, const ConvArgs& a) {
+        static_assert(!TMODE && !STATS && !BSTATS, "the split kernel has no training forms");
+        return y3_launch_lds<conv_mfma_split_kernel<BM, BN, WGM, WGN, KS, UPCAT, STREAMK, NP>>(
+            stream, dim3(grid), dim3(256), split_lds_bytes<BM, BN, NP>(), a);
     }
-    return dispatch_bn<3, false, NP>(stream, a);
-}
+};
 
 __global__ void pack_weights_split_kernel(const float* __restrict__ w_hwio, unsigned short* __restrict__ out,
                                           int taps, int cin, int cout, int planes, int s_ci, int s_co) {
@@ -377,32 +342,6 @@ __global__ void pack_weights_split_kernel(const float* __restrict__ w_hwio, unsi
     }
 }
 
-int check_desc(const y3_conv_desc* d, const void* x_up, const char* who) {
-    Y3_CHECK_ARG(d->k == 1 || d->k == 3, "%s: kernel_size must be 1 or 3 (got %d)", who, d->k);
-    Y3_CHECK_ARG(d->stride == 1 || d->stride == 2, "%s: stride must be 1 or 2 (got %d)", who, d->stride);
-    Y3_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0, "%s: non-positive dimension", who);
-    Y3_CHECK_ARG(!(d->stride == 2 && (d->h % 2 || d->w % 2)), "%s: stride-2 conv needs even H,W (got %dx%d)", who,
-                 d->h, d->w);
-    Y3_CHECK_ARG(!(d->k == 1 && d->stride != 1), "%s: 1x1 conv must have stride 1", who);
-    Y3_CHECK_ARG((x_up != nullptr) == (d->c_up > 0), "%s: x_up and c_up must agree", who);
-    Y3_CHECK_ARG(d->cin % (2 * SBK) == 0, "%s: Cin must be 3 or a multiple of %d (got %d)", who, 2 * SBK, d->cin);
-    if (x_up) {
-        Y3_CHECK_ARG(d->k == 1 && d->stride == 1, "%s: fused upsample+concat needs a 1x1 s1 conv", who);
-        Y3_CHECK_ARG(d->c_up % (2 * SBK) == 0 && d->c_up < d->cin && d->h % 2 == 0 && d->w % 2 == 0,
-                     "%s: bad c_up=%d for cin=%d", who, d->c_up, d->cin);
-    }
-    return Y3_OK;      // (the element limit: the launchers' image ranges)
-}
-
-void fill_args(ConvArgs& a, const y3_conv_desc* d) {
-    a.partial = nullptr; a.flags = nullptr; a.workers = 0; a.wrev = 0; a.tmode = 0; a.cy = a.cx = 0; a.ntaps = 0;
-    a.err = nullptr; a.spin_limit = 0; a.fault = 0; a.stats = nullptr; a.bz = nullptr; a.bvec = nullptr;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Cu = d->c_up; a.Cx = d->cin - d->c_up;
-    a.Cout = d->cout; a.stride = d->stride; a.pad = d->k / 2; a.act = d->act;
-    a.Ho = d->h / d->stride; a.Wo = d->w / d->stride;
-    a.M = d->n * a.Ho * a.Wo;
-}
-
 }  // namespace
 
 // transposed == 0: w is HWIO [k*k][cin][cout].  transposed != 0: w is [k*k][cout][cin] (what the data gradient of a
@@ -410,7 +349,7 @@ void fill_args(ConvArgs& a, const y3_conv_desc* d) {
 int y3_launch_pack_split(hipStream_t stream, const float* w_hwio, int k, int cin, int cout, int planes, void* out,
                          int transposed) {
     const size_t total = (size_t)k * k * cin * cout;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = y3_blocks_for(total);
     hipLaunchKernelGGL(pack_weights_split_kernel, dim3(blocks), dim3(256), 0, stream, w_hwio,
                        static_cast<unsigned short*>(out), k * k, cin, cout, planes, transposed ? 1 : cout,
                        transposed ? cin : 1);
@@ -428,32 +367,14 @@ int y3_launch_conv_split(hipStream_t stream, const y3_conv_desc* d, int planes, 
     if (d->cin == 3)
         return y3_launch_conv(stream, d, x, x_up, static_cast<const float*>(w), scale, shift, residual, y,
                               workspace, workspace_bytes, sk);
-    if (int rc = check_desc(d, x_up, "y3_conv2d_fwd_split")) return rc;
-    const y3_image_ranges rg(d, 0);
-    if (rg.n < 0) return rg.n;
-    if (rg.n > 1) {
-        // image ranges, as in y3_launch_conv: the pointers advance by whole images; no range takes stream-K
-        y3_sk_opts o;
-        if (sk) o = *sk;
-        o.flags = nullptr;
-        const size_t in_img = (size_t)d->h * d->w * (d->cin - d->c_up), up_img = (size_t)(d->h / 2) * (d->w / 2) * d->c_up;
-        const size_t out_img = (size_t)(d->h / d->stride) * (d->w / d->stride) * d->cout;
-        for (int i = 0; i < rg.n; ++i) {
-            y3_conv_desc dr = *d;
-            dr.n = rg.count[i];
-            const size_t b = (size_t)rg.begin[i];
-            if (int rc = y3_launch_conv_split(stream, &dr, planes, x + b * in_img, x_up ? x_up + b * up_img : nullptr, w, scale, shift,
-                                              residual ? residual + b * out_img : nullptr, y + b * out_img, nullptr, 0, &o))
-                return rc;
-        }
-        return Y3_OK;
-    }
-    ConvArgs a;
-    a.x = x; a.xu = x_up; a.w = static_cast<const float*>(w); a.scale = scale; a.shift = shift;
-    a.resid = residual; a.y = y;
-    fill_args(a, d);
-    return planes == 3 ? launch_np<3>(stream, d, a, workspace, workspace_bytes, sk)
-                       : launch_np<2>(stream, d, a, workspace, workspace_bytes, sk);
+    if (int rc = check_conv_desc(d, x_up, "y3_conv2d_fwd_split", 2 * SBK)) return rc;
+    const int k = d->k;
+    return walk_image_ranges(y3_image_ranges(d, 0), conv_args(d, x, x_up, w, scale, shift, residual, y), 0,
+                             [&](ConvArgs& r, bool whole) -> int {
+        void* ws = whole ? workspace : nullptr;
+        return planes == 3 ? launch_conv_family<SplitFamily<3>>(stream, r, k, ws, workspace_bytes, sk)
+                           : launch_conv_family<SplitFamily<2>>(stream, r, k, ws, workspace_bytes, sk);
+    });
 }
 
 // Data gradient of a stride-1 conv on the split kernel: dx (+)= conv_same(dz, flipped kernel).  `w` is the
@@ -470,32 +391,14 @@ int y3_launch_conv_dgrad_split(hipStream_t stream, const y3_conv_desc* fwd, int 
                  "y3_conv2d_dgrad_split: dz stride must be a multiple of %d", 2 * SBK);
     Y3_CHECK_ARG(fwd->cin % 4 == 0 && fwd->n > 0 && fwd->h > 0 && fwd->w > 0,
                  "y3_conv2d_dgrad_split: Cin must be a multiple of 4");
-    y3_conv_desc d = *fwd;              // the gradient conv: [n,h,w,dz_stride] -> [n,h,w,cin]
-    d.cin = dz_stride; d.c_up = 0; d.cout = fwd->cin; d.act = 0;
     Y3_CHECK_ARG(fwd->cin > 0 && fwd->cout > 0, "y3_conv2d_dgrad_split: non-positive dimension");
-    const y3_image_ranges rg(fwd, dz_stride);
-    if (rg.n < 0) return rg.n;
-    if (rg.n > 1) {
-        // image ranges, as in y3_launch_conv: dz and dx advance by whole images; no range takes stream-K
-        y3_sk_opts o;
-        if (sk) o = *sk;
-        o.flags = nullptr;
-        const size_t px = (size_t)fwd->h * fwd->w;
-        for (int i = 0; i < rg.n; ++i) {
-            y3_conv_desc fr = *fwd;
-            fr.n = rg.count[i];
-            const size_t b = (size_t)rg.begin[i];
-            if (int rc = y3_launch_conv_dgrad_split(stream, &fr, planes, dz + b * px * dz_stride, dz_stride, w, ones, zeros, accumulate,
-                                                    dx + b * px * fwd->cin, nullptr, 0, &o))
-                return rc;
-        }
-        return Y3_OK;
-    }
-    ConvArgs a;
-    a.x = dz; a.xu = nullptr; a.w = static_cast<const float*>(w); a.scale = ones; a.shift = zeros;
-    a.resid = accumulate ? dx : nullptr; a.y = dx;
-    fill_args(a, &d);
+    const y3_conv_desc g = dgrad_desc(fwd, dz_stride);
+    ConvArgs a = conv_args(&g, dz, nullptr, w, ones, zeros, accumulate ? dx : nullptr, dx);
     a.wrev = 1;
-    return planes == 3 ? launch_np<3>(stream, &d, a, workspace, workspace_bytes, sk)
-                       : launch_np<2>(stream, &d, a, workspace, workspace_bytes, sk);
+    const int k = fwd->k;
+    return walk_image_ranges(y3_image_ranges(fwd, dz_stride), a, 0, [&](ConvArgs& r, bool whole) -> int {
+        void* ws = whole ? workspace : nullptr;
+        return planes == 3 ? launch_conv_family<SplitFamily<3>>(stream, r, k, ws, workspace_bytes, sk)
+                           : launch_conv_family<SplitFamily<2>>(stream, r, k, ws, workspace_bytes, sk);
+    });
 }

@@ -25,7 +25,7 @@
 // few fp32 roundings per term (tests/test_conv_gpu.py holds it to the same 1e-4 tolerance against fp64).
 #include <cstdlib>
 #include <type_traits>
-#include "y3_internal.h"
+#include "y3_lds.h"
 
 namespace {
 
@@ -55,9 +55,6 @@ __device__ __host__ __forceinline__ long long wk_begin(long long items, int work
     const long long q = items / workers, r = items % workers;
     return (long long)w * q + (w < r ? w : r);
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
 // Stream-K work split.  The blocks are first divided, whole, among the 8 XCD groups (group x = workgroups with
 // blockIdx % 8 == x: they share an L2, and a group's blocks share weight panels); inside a group its G = workers/8
@@ -94,7 +91,6 @@ typedef __attribute__((address_space(1))) unsigned gu32;   // flags are only eve
 
 constexpr int WKC = 8;                   // input channels per K-step
 constexpr int WROW = 32;                 // LDS bytes per row (8 floats)
-constexpr unsigned OOB = 0x80000000u;
 
 // Identity the optimiser cannot see through.  The per-block set-up code below is a function of threadIdx only; left
 // visible, LICM hoists ~100 partial results out of the block loop and keeps them (spilled) across the K-loop.
@@ -104,26 +100,6 @@ __device__ __forceinline__ int opaque(int v) {
 }
 
 __device__ __forceinline__ int lds_off(int row, int half) { return row * WROW + ((half ^ ((row >> 3) & 1)) << 4); }
-
-// B^T d B on float4s (4 channels at once).  d[i][j], i = patch row, j = patch column; result v[i*4+j].
-template <typename V>
-__device__ __forceinline__ void input_transform(const V (&d)[16], V (&v)[16]) {
-    V t[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {          // rows: B^T d
-        t[0 * 4 + j] = d[0 * 4 + j] - d[2 * 4 + j];
-        t[1 * 4 + j] = d[1 * 4 + j] + d[2 * 4 + j];
-        t[2 * 4 + j] = d[2 * 4 + j] - d[1 * 4 + j];
-        t[3 * 4 + j] = d[1 * 4 + j] - d[3 * 4 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {          // columns: (B^T d) B
-        v[i * 4 + 0] = t[i * 4 + 0] - t[i * 4 + 2];
-        v[i * 4 + 1] = t[i * 4 + 1] + t[i * 4 + 2];
-        v[i * 4 + 2] = t[i * 4 + 2] - t[i * 4 + 1];
-        v[i * 4 + 3] = t[i * 4 + 1] - t[i * 4 + 3];
-    }
-}
 
 // The kernel's tail, in two steps so that the residual loads fly under the output transform: prepare() computes the output offsets of this thread's
 // float4 rows of the staging tile cs[BT*4][LDC] and issues the residual loads; finish() reads the staged rows ->
@@ -201,7 +177,7 @@ struct WinoRows {
                 for (int q = 0; q < 4; ++q) v[q] = v[q] > 0.f ? v[q] : 0.1f * v[q];
             }
             v += res[i];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs_y,
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_y,
                                                    ((ok >> i) & 1) ? off[i] * 4u : OOB, 0, 0);
             if (STATS) {
                 const float m = ((ok >> i) & 1) ? 1.f : 0.f;      // rows that do not exist contribute nothing
@@ -608,7 +584,7 @@ __global__ void __launch_bounds__(512, 1) conv_wino8_f32_kernel(const WinoArgs p
                 const int rr = f / C4, c4 = f - rr * C4;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(cs + rr * LDC + c4 * 4) +
                                 *reinterpret_cast<const f32x4*>(cs + (BT * 4 + rr) * LDC + c4 * 4);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs_part,
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_part,
                                                        slot_off + (unsigned)f * 16u, 0, 16);   // aux 16 = sc1
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -691,6 +667,14 @@ int y3_launch_pack_wino(hipStream_t stream, const float* w_hwio, int cin, int co
 }
 
 constexpr int WK_WORKERS = 256;     // one persistent workgroup per CU (139 KB of LDS, eight waves)
+constexpr int WINO_BT = 64;         // 2x2 tiles per block: the launcher's BT and the row blocks of the STATS output
+
+// rows of the `stats` output of the STATS instantiations: one per block of WINO_BT tiles
+int y3_conv_wino_stats_blocks_impl(const y3_conv_desc* d) {
+    if (!y3_conv_wino_eligible_impl(d)) return 0;
+    const long long T = (long long)d->n * ((d->h + 1) / 2) * ((d->w + 1) / 2);
+    return (int)((T + WINO_BT - 1) / WINO_BT);
+}
 
 // stream-K scratch: one partial-sum slot per worker, then one flag word per worker
 constexpr size_t WK_SLOT_BYTES = (size_t)64 * 4 * 64 * sizeof(float);
@@ -744,23 +728,9 @@ int y3_launch_conv_wino(hipStream_t stream, const y3_conv_desc* d, const float* 
         }
         a.bn_inner = force >= 0 ? (force != 0) : ((size_t)16 * d->cin * d->cout * sizeof(float) <= (size_t)(1u << 20));
     }
-    constexpr int BT = 64, BNW = 64;
+    constexpr int BT = WINO_BT, BNW = 64;
     constexpr int workers = WK_WORKERS;
     constexpr size_t lds = (size_t)2 * BT * 4 * (BNW + 4) * sizeof(float) + 2 * BT * sizeof(int);
-    auto kern = a.stats ? conv_wino8_f32_kernel<false, true> : conv_wino8_f32_kernel<false, false>;
-    auto kern_sk = a.stats ? conv_wino8_f32_kernel<true, true> : conv_wino8_f32_kernel<true, false>;
-    {
-        static bool attr_set[2][Y3_MAX_DEVICES] = {};   // per pair of instantiations and device; benign race (idempotent)
-        const int slot = a.stats ? 1 : 0;
-        const int dev_ = y3_current_device();
-        if (dev_ < 0 || !attr_set[slot][dev_]) {
-            Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_sk),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev_ >= 0) attr_set[slot][dev_] = true;
-        }
-    }
     const int nbt = (a.T + BT - 1) / BT, nbn = (a.Cout + BNW - 1) / BNW;
     const int blocks = nbt * nbn;
     // stream-K when the block count is a small non-integer multiple of the resident workgroups (the last round
@@ -786,10 +756,9 @@ int y3_launch_conv_wino(hipStream_t stream, const y3_conv_desc* d, const float* 
             a.flags = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + WK_FLAGS_OFFSET);
             Y3_CHECK_HIP(hipMemsetAsync(a.flags, 0, (size_t)workers * sizeof(unsigned), stream));
         }
-        hipLaunchKernelGGL(kern_sk, dim3(workers), dim3(512), lds, stream, a);
-    } else {
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, stream, a);
+        return a.stats ? y3_launch_lds<conv_wino8_f32_kernel<true, true>>(stream, dim3(workers), dim3(512), lds, a)
+                       : y3_launch_lds<conv_wino8_f32_kernel<true, false>>(stream, dim3(workers), dim3(512), lds, a);
     }
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return a.stats ? y3_launch_lds<conv_wino8_f32_kernel<false, true>>(stream, dim3(blocks), dim3(512), lds, a)
+                   : y3_launch_lds<conv_wino8_f32_kernel<false, false>>(stream, dim3(blocks), dim3(512), lds, a);
 }

@@ -45,11 +45,9 @@
 //     ahead of the store loop; STATS instantiation: column sums of y and y^2 per block for the training forward's batch norm;
 //   * mosaic tiling (w44_tiling): a batch whose map side is not a multiple of 4 is tiled as ONE picture (round 4).
 #include <cstdlib>
-#include "y3_internal.h"
+#include "y3_lds.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct W44Args {
     const float* x;      // [N,H,W,Cin]
@@ -77,7 +75,6 @@ constexpr int STAGE = 36 * PLANE;              // 18,432 B: one K-step of V (eit
 constexpr int VSTAGE = 2 * STAGE;              // 36,864 B: the two-kernel form stages TWO K-steps (16 channels) at a time
 constexpr int LDS_RING = 4 * STAGE;            // 73,728 B of K-loop buffers either way
 constexpr int LDS_BYTES = LDS_RING + 512;      // + the tiles' pixel-index parts: 74,240 B, two workgroups per CU
-constexpr unsigned OOB = 0x80000000u;
 #ifndef W44_BDEPTH
 #define W44_BDEPTH 6
 #endif
@@ -92,17 +89,6 @@ constexpr int VBDEPTH = W44V_BDEPTH;           // (two-kernel form) the same win
 #define W44V_AD 3
 #endif
 constexpr int VAD = W44V_AD;                   // (two-kernel form) activation fragment reads (16 B = one position pair) ahead
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-// 16 bytes per lane, global -> LDS without a register round trip: lane l's bytes land at lds_base + 16*l (lds_base is
-// wave-uniform), an out-of-range `voff` writes zeros (see y3_conv_bf16x.hip; the builtin exists in the device pass only).
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds_base, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_base, 16, voff, soff, 0, 0);
-#endif
-}
 
 // 1-D input transform B^T v for the 6-point rule; rows 1,2 and 3,4 share their sums
 template <typename V> __device__ __forceinline__ V bt0(const V& v0, const V& v2, const V& v4) { return 4.f * v0 - 5.f * v2 + v4; }
@@ -292,7 +278,7 @@ __device__ __forceinline__ void w44_tail(const W44Args& p, const f32x4 (&acc)[36
             for (int q = 0; q < 4; ++q) v[q] = v[q] > 0.f ? v[q] : 0.1f * v[q];
         }
         v += rv[it];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs_y, off[it], 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_y, off[it], 0, 0);
         if (STATS) {
             if (off[it] != OOB) { st1 += v; st2 += v * v; }
         }
@@ -797,7 +783,7 @@ int y3_conv_wino44_stats_blocks_impl(const y3_conv_desc* d) {
 
 int y3_launch_pack_wino44(hipStream_t stream, const float* w_hwio, int cin, int cout, float* out, int dgrad) {
     const long long total = (long long)cin * cout;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const int blocks = y3_blocks_for(total, 8192);
     hipLaunchKernelGGL(pack_weights_wino44_kernel, dim3(blocks), dim3(256), 0, stream, w_hwio, out, cin, cout, dgrad);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
@@ -820,16 +806,6 @@ int y3_conv_wino44_two_pass_impl(const y3_conv_desc* d) {
     static const int force = y3_exp_env("Y3_WINO44_V") ? atoi(y3_exp_env("Y3_WINO44_V")) : -1;
     if (force >= 0) return force;
     return d->cout >= 512;
-}
-
-static int w44_set_lds(const void* kern, int slot) {
-    static bool done[4][Y3_MAX_DEVICES] = {};      // per kernel and device (idempotent: a race sets it twice)
-    const int dev = y3_current_device();
-    if (dev < 0 || !done[slot][dev]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        if (dev >= 0) done[slot][dev] = true;
-    }
-    return Y3_OK;
 }
 
 int y3_launch_conv_wino44(hipStream_t stream, const y3_conv_desc* d, const float* x, const float* u, const float* scale,
@@ -867,19 +843,14 @@ int y3_launch_conv_wino44(hipStream_t stream, const y3_conv_desc* d, const float
         const long long items = (long long)nbt * (d->cin / 16);
         hipLaunchKernelGGL(wino44_input_transform_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, a);
         Y3_CHECK_HIP(hipGetLastError());
-        auto kern = a.stats ? conv_wino44v_f32_kernel<true> : conv_wino44v_f32_kernel<false>;
-        if (int rc = w44_set_lds(reinterpret_cast<const void*>(kern), a.stats ? 3 : 2)) return rc;
 #ifdef W44V_LDS      // probe: a larger request keeps the second workgroup off the CU
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, W44V_LDS));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), W44V_LDS, stream, a);
+        constexpr size_t vlds = W44V_LDS;
 #else
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), LDS_BYTES, stream, a);
+        constexpr size_t vlds = LDS_BYTES;
 #endif
-    } else {
-        auto kern = a.stats ? conv_wino44_f32_kernel<true> : conv_wino44_f32_kernel<false>;
-        if (int rc = w44_set_lds(reinterpret_cast<const void*>(kern), a.stats ? 1 : 0)) return rc;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), LDS_BYTES, stream, a);
+        return a.stats ? y3_launch_lds<conv_wino44v_f32_kernel<true>>(stream, dim3(grid), dim3(NTH), vlds, a)
+                       : y3_launch_lds<conv_wino44v_f32_kernel<false>>(stream, dim3(grid), dim3(NTH), vlds, a);
     }
-    Y3_CHECK_HIP(hipGetLastError());
-    return Y3_OK;
+    return a.stats ? y3_launch_lds<conv_wino44_f32_kernel<true>>(stream, dim3(grid), dim3(NTH), LDS_BYTES, a)
+                   : y3_launch_lds<conv_wino44_f32_kernel<false>>(stream, dim3(grid), dim3(NTH), LDS_BYTES, a);
 }

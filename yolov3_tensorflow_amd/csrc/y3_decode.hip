@@ -182,7 +182,7 @@ extern "C" int y3_pack_conv_weights(y3_ctx* ctx, const float* w_hwio, int k, int
     Y3_CHECK_ARG(ctx && w_hwio && w_packed, "y3_pack_conv_weights: null argument");
     Y3_CHECK_ARG(k > 0 && cin > 0 && cout > 0, "y3_pack_conv_weights: non-positive dimension");
     const size_t total = (size_t)k * k * cin * cout;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = y3_blocks_for(total);
     hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w_hwio, w_packed,
                        k * k, cin, cout);
     Y3_CHECK_HIP(hipGetLastError());

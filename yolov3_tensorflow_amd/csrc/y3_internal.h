@@ -98,6 +98,23 @@ size_t y3_device_max_lds();         // dynamic LDS one workgroup may ask for on 
         }                                                                           \
     } while (0)
 
+// Launch of a kernel that takes `lds` bytes of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize is set once per kernel
+// instantiation and device (the flags are per instantiation of this template; a benign race, the call is idempotent).
+template <auto Kern, typename... Args>
+int y3_launch_lds(hipStream_t stream, dim3 grid, dim3 block, size_t lds, const Args&... args) {
+    static bool attr_set[Y3_MAX_DEVICES] = {};
+    const int dev = y3_current_device();
+    if (dev < 0 || !attr_set[dev]) {
+        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds, stream, args...);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+// Grid of a grid-stride pass over `total` elements, 256 threads a workgroup, at most `cap` workgroups (the pack kernels)
+inline int y3_blocks_for(size_t total, int cap = 4096) { return (int)((total + 255) / 256 < (size_t)cap ? (total + 255) / 256 : (size_t)cap); }
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef f32x4 f32x4_u __attribute__((aligned(4)));   // a float4 at a 4-byte-aligned address (one dwordx4 access)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -167,6 +184,7 @@ int y3_launch_conv_split(hipStream_t stream, const y3_conv_desc* d, int planes, 
                          const void* w, const float* scale, const float* shift, const float* residual, float* y,
                          void* workspace, size_t workspace_bytes, const y3_sk_opts* sk = nullptr);
 int y3_conv_wino_eligible_impl(const y3_conv_desc* d);
+int y3_conv_wino_stats_blocks_impl(const y3_conv_desc* d);     // rows of the STATS output (one per 64-tile block)
 // F(4x4,3x3) inference kernel (y3_conv_wino44.hip)
 int y3_conv_wino44_eligible_impl(const y3_conv_desc* d);
 int y3_conv_wino44_candidate_impl(const y3_conv_desc* d);   // by shape (what to pack an alternative kernel for)

@@ -13,7 +13,7 @@
 // matrix-pipe-bound regime as the forward conv (K = M is long, so the prologue/epilogue are negligible).
 #include <cstdlib>
 #include <cmath>
-#include "y3_internal.h"
+#include "y3_lds.h"
 
 namespace {
 
@@ -30,7 +30,6 @@ struct WgradArgs {
 
 constexpr int WBK = 32;          // pixels per K-step
 constexpr int WLD = 128;         // LDS row stride (floats): lanes of a half-wave read consecutive floats
-constexpr unsigned OOB = 0x80000000u;
 
 // BNT = output-channel tile (128 / 64 / 32), waves arranged WGM x WGN over (j, co)
 template <int BNT, int WGM, int WGN>
@@ -475,13 +474,11 @@ extern "C" int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* d, const float* x,
         // one range of one split writes dw itself; with more ranges every split of every range goes to the scratch, so that
         // the one sum below adds them in one fixed order
         a.out = (rg.n == 1 && nsplit == 1) ? dw_hwio : static_cast<float*>(scratch) + (size_t)total * J * d->cout;
-        if (bnt == 128)
-            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2>), dim3(tiles, nsplit), dim3(256), lds, st, a);
-        else if (bnt == 64)
-            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2>), dim3(tiles, nsplit), dim3(256), lds, st, a);
-        else
-            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1>), dim3(tiles, nsplit), dim3(256), lds, st, a);
-        Y3_CHECK_HIP(hipGetLastError());
+        const dim3 grid(tiles, nsplit);
+        if (int rc = bnt == 128  ? y3_launch_lds<conv_wgrad_kernel<128, 2, 2>>(st, grid, dim3(256), lds, a)
+                     : bnt == 64 ? y3_launch_lds<conv_wgrad_kernel<64, 2, 2>>(st, grid, dim3(256), lds, a)
+                                 : y3_launch_lds<conv_wgrad_kernel<32, 4, 1>>(st, grid, dim3(256), lds, a))
+            return rc;
         total += nsplit;
     }
     if (total > 1) {

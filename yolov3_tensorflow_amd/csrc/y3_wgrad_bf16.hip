@@ -14,12 +14,11 @@
 // fixed (tap, ci) column chunk, and the P gather is x's row of that tap (zero outside the image: buffer loads past the end).
 #include <algorithm>
 #include "y3_bf16.h"
+#include "y3_lds.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short i16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct WgArgs {
     const bf16_t* x;   // [N,H,W,Cin]
@@ -35,7 +34,6 @@ struct WgArgs {
 constexpr int BK = 32;              // pixels per K-step
 constexpr int TJ = 128, TC = 128;   // output tile: j x co
 constexpr int LDR = 320;            // LDS row stride in bytes (128 bf16 + 64 bytes of pad)
-constexpr unsigned OOB = 0x80000000u;
 
 // 8 k (pixels) of operand column `col` for a 32x32x16 MFMA: lane l = 16g + 4q + p supplies row (8(g>>1) + 4rd + q), columns
 // col0 + 16(g&1) + 4p .. +3; it receives column col0 + 16(g&1) + (l&15), k = 8(g>>1) + 4rd + 0..3 in its elements 4rd..4rd+3
@@ -217,7 +215,7 @@ int y3_launch_conv_wgrad_bf16(hipStream_t stream, const y3_conv_desc* d, const v
     Y3_CHECK_HIP(hipGetLastError());
     if (q.nsplit > 1) {
         const long long total = (long long)a.J * d->cout;
-        const int blocks = (int)std::min<long long>((total + 255) / 256, 2048);
+        const int blocks = y3_blocks_for(total, 2048);
         hipLaunchKernelGGL(wgrad_bf16_sum_kernel, dim3(blocks), dim3(256), 0, stream, static_cast<const float*>(scratch),
                            q.nsplit, total, dw);
         Y3_CHECK_HIP(hipGetLastError());

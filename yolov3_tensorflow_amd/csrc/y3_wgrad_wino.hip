@@ -21,7 +21,7 @@
 //     sets, so G^T dU G (4x4 -> 3x3) is register arithmetic; the nine taps go straight to the HWIO layout of the kernel
 //     variable (or of this split's partial tile, which wgrad_sum_splits adds in a fixed order: deterministic).
 #include <cstdlib>
-#include "y3_internal.h"
+#include "y3_lds.h"
 
 namespace {
 
@@ -36,8 +36,6 @@ struct WgWinoArgs {
     int nsplit;
 };
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr unsigned OOB = 0x80000000u;
 constexpr int WROW = 32;                       // LDS bytes per (position, channel) row: 8 tiles
 constexpr int PLANE = 64 * WROW;               // bytes per transform position (64 channels)
 constexpr int STAGE = 16 * PLANE;              // one operand, one stage
@@ -45,24 +43,6 @@ constexpr int STAGE = 16 * PLANE;              // one operand, one stage
 // byte offset of tile pair `pair` (0..3) inside row `ch`
 __device__ __forceinline__ int row_off(int ch, int pair) { return ch * WROW + (((pair + (ch >> 2)) & 3) << 3); }
 
-// B^T d B (d[i*4+j], i = patch row) -> v[pos = i*4+j]
-__device__ __forceinline__ void input_transform(const float (&d)[16], float (&v)[16]) {
-    float t[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        t[0 * 4 + j] = d[0 * 4 + j] - d[2 * 4 + j];
-        t[1 * 4 + j] = d[1 * 4 + j] + d[2 * 4 + j];
-        t[2 * 4 + j] = d[2 * 4 + j] - d[1 * 4 + j];
-        t[3 * 4 + j] = d[1 * 4 + j] - d[3 * 4 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[i * 4 + 0] = t[i * 4 + 0] - t[i * 4 + 2];
-        v[i * 4 + 1] = t[i * 4 + 1] + t[i * 4 + 2];
-        v[i * 4 + 2] = t[i * 4 + 2] - t[i * 4 + 1];
-        v[i * 4 + 3] = t[i * 4 + 1] - t[i * 4 + 3];
-    }
-}
 // A dY A^T, A = [[1,0],[1,1],[1,-1],[0,-1]]; y[p*2+q] -> z[pos = i*4+j]
 __device__ __forceinline__ void grad_transform(const float (&y)[4], float (&z)[16]) {
     float r[4][2];      // rows: A dY
@@ -400,16 +380,8 @@ int y3_launch_conv_wgrad_wino(hipStream_t stream, const y3_conv_desc* d, const f
     wgw_split(d, &a.nsplit, &a.ksteps);
     a.out = a.nsplit == 1 ? dw_hwio : static_cast<float*>(scratch);
     constexpr size_t lds = (size_t)4 * STAGE;
-    static bool attr_set[Y3_MAX_DEVICES] = {};   // benign race (idempotent)
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_wino_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
     const int wt = (d->cin / 64) * (d->cout / 64);
-    hipLaunchKernelGGL(conv_wgrad_wino_kernel, dim3(wt, a.nsplit), dim3(256), lds, stream, a);
-    Y3_CHECK_HIP(hipGetLastError());
+    if (int rc = y3_launch_lds<conv_wgrad_wino_kernel>(stream, dim3(wt, a.nsplit), dim3(256), lds, a)) return rc;
     if (a.nsplit > 1) {
         const long long n4 = (long long)9 * a.Cin * a.Cout / 4;
         long long nb = (n4 + 63) / 64;
