@@ -220,3 +220,151 @@ HOST_ANSWERS = [
     ('y3_conv_workspace_bytes', (4, 20, 28, 64, 0, 64, 3, 2), (), 71681, 0),
     ('y3_conv_dgrad_bn_blocks', (4, 20, 28, 128, 0, 64, 1, 1), (), 143361, 36),
 ]
+
+
+# ---- 6. the host answers of the weight gradients and the train step's workspace -------------------------------------------------
+# Same form as HOST_ANSWERS.  Recorded from the library as it stood BEFORE the fp32 weight gradient's size query and launcher
+# were moved onto one plan (and the bf16 one's scratch size into its Plan); they are not derived from that code.  Scratch bytes
+# of the three kernel families and the Winograd eligibility for: the eight WGRAD shapes; one K-step (one split by construction);
+# a Winograd launch of 256 tiles (one split); the stem, small and at six 96 x 416 images; the seven cut launches and the stem's
+# three- and eight-range cases of test_conv_ranges_cpu.py under their limits; the five weight-gradient shapes of
+# test_train_bf16_kernels_gpu.py.  (The bf16 query only where Cin is a multiple of 32.)
+WGRAD_HOST_ANSWERS = [
+    ('y3_conv_wgrad_scratch_bytes', (3, 150, 146, 64, 0, 32, 1, 1), (), 0, 3367168),
+    ('y3_conv_wgrad_wino_eligible', (3, 150, 146, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (3, 150, 146, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (3, 150, 146, 64, 0, 32, 1, 1), (), 0, 2105344),
+    ('y3_conv_wgrad_scratch_bytes', (4, 94, 100, 32, 0, 64, 3, 2), (), 0, 10838272),
+    ('y3_conv_wgrad_wino_eligible', (4, 94, 100, 32, 0, 64, 3, 2), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (4, 94, 100, 32, 0, 64, 3, 2), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (4, 94, 100, 32, 0, 64, 3, 2), (), 0, 2727936),
+    ('y3_conv_wgrad_scratch_bytes', (8, 26, 26, 256, 0, 255, 1, 1), (), 0, 14884096),
+    ('y3_conv_wgrad_wino_eligible', (8, 26, 26, 256, 0, 255, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (8, 26, 26, 256, 0, 255, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (8, 26, 26, 256, 0, 255, 1, 1), (), 0, 5744640),
+    ('y3_conv_wgrad_scratch_bytes', (3, 37, 37, 64, 0, 128, 3, 1), (), 0, 12681472),
+    ('y3_conv_wgrad_wino_eligible', (3, 37, 37, 64, 0, 128, 3, 1), (), 0, 1),
+    ('y3_conv_wgrad_wino_scratch_bytes', (3, 37, 37, 64, 0, 128, 3, 1), (), 0, 20054272),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (3, 37, 37, 64, 0, 128, 3, 1), (), 0, 5013504),
+    ('y3_conv_wgrad_scratch_bytes', (2, 90, 92, 128, 0, 256, 3, 2), (), 0, 30671104),
+    ('y3_conv_wgrad_wino_eligible', (2, 90, 92, 128, 0, 256, 3, 2), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (2, 90, 92, 128, 0, 256, 3, 2), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (2, 90, 92, 128, 0, 256, 3, 2), (), 0, 20054016),
+    ('y3_conv_wgrad_scratch_bytes', (3, 61, 67, 128, 0, 64, 1, 1), (), 0, 6291712),
+    ('y3_conv_wgrad_wino_eligible', (3, 61, 67, 128, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (3, 61, 67, 128, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (3, 61, 67, 128, 0, 64, 1, 1), (), 0, 1572864),
+    ('y3_conv_wgrad_scratch_bytes', (3, 52, 50, 256, 0, 75, 1, 1), (), 0, 9369856),
+    ('y3_conv_wgrad_wino_eligible', (3, 52, 50, 256, 0, 75, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (3, 52, 50, 256, 0, 75, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (3, 52, 50, 256, 0, 75, 1, 1), (), 0, 2380800),
+    ('y3_conv_wgrad_scratch_bytes', (7, 26, 26, 512, 0, 18, 1, 1), (), 0, 2728192),
+    ('y3_conv_wgrad_wino_eligible', (7, 26, 26, 512, 0, 18, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (7, 26, 26, 512, 0, 18, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (7, 26, 26, 512, 0, 18, 1, 1), (), 0, 700416),
+    ('y3_conv_wgrad_scratch_bytes', (1, 4, 8, 64, 0, 32, 1, 1), (), 0, 8448),
+    ('y3_conv_wgrad_wino_eligible', (1, 4, 8, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (1, 4, 8, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (1, 4, 8, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_scratch_bytes', (1, 16, 4, 1024, 0, 1024, 3, 1), (), 0, 37748992),
+    ('y3_conv_wgrad_wino_eligible', (1, 16, 4, 1024, 0, 1024, 3, 1), (), 0, 1),
+    ('y3_conv_wgrad_wino_scratch_bytes', (1, 16, 4, 1024, 0, 1024, 3, 1), (), 0, 37748992),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (1, 16, 4, 1024, 0, 1024, 3, 1), (), 0, 0),
+    ('y3_conv_wgrad_scratch_bytes', (1, 32, 32, 3, 0, 32, 3, 1), (), 0, 14155776),
+    ('y3_conv_wgrad_wino_eligible', (1, 32, 32, 3, 0, 32, 3, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (1, 32, 32, 3, 0, 32, 3, 1), (), 0, 0),
+    ('y3_conv_wgrad_scratch_bytes', (6, 96, 416, 3, 0, 32, 3, 1), (), 0, 14155776),
+    ('y3_conv_wgrad_wino_eligible', (6, 96, 416, 3, 0, 32, 3, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (6, 96, 416, 3, 0, 32, 3, 1), (), 0, 0),
+    ('y3_conv_wgrad_scratch_bytes', (5, 32, 32, 32, 0, 64, 3, 1), (), 150000, 11796736),
+    ('y3_conv_wgrad_wino_eligible', (5, 32, 32, 32, 0, 64, 3, 1), (), 150000, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (5, 32, 32, 32, 0, 64, 3, 1), (), 150000, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (5, 32, 32, 32, 0, 64, 3, 1), (), 150000, 1474560),
+    ('y3_conv_wgrad_scratch_bytes', (5, 48, 32, 32, 0, 64, 3, 2), (), 150000, 4423936),
+    ('y3_conv_wgrad_wino_eligible', (5, 48, 32, 32, 0, 64, 3, 2), (), 150000, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (5, 48, 32, 32, 0, 64, 3, 2), (), 150000, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (5, 48, 32, 32, 0, 64, 3, 2), (), 150000, 589824),
+    ('y3_conv_wgrad_scratch_bytes', (5, 48, 32, 64, 0, 32, 1, 1), (), 200000, 1966336),
+    ('y3_conv_wgrad_wino_eligible', (5, 48, 32, 64, 0, 32, 1, 1), (), 200000, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (5, 48, 32, 64, 0, 32, 1, 1), (), 200000, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (5, 48, 32, 64, 0, 32, 1, 1), (), 200000, 245760),
+    ('y3_conv_wgrad_scratch_bytes', (5, 32, 32, 256, 0, 128, 1, 1), (), 600000, 20971776),
+    ('y3_conv_wgrad_wino_eligible', (5, 32, 32, 256, 0, 128, 1, 1), (), 600000, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (5, 32, 32, 256, 0, 128, 1, 1), (), 600000, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (5, 32, 32, 256, 0, 128, 1, 1), (), 600000, 2621440),
+    ('y3_conv_wgrad_scratch_bytes', (7, 26, 26, 128, 0, 256, 3, 1), (), 400000, 66060544),
+    ('y3_conv_wgrad_wino_eligible', (7, 26, 26, 128, 0, 256, 3, 1), (), 400000, 1),
+    ('y3_conv_wgrad_wino_scratch_bytes', (7, 26, 26, 128, 0, 256, 3, 1), (), 400000, 35389696),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (7, 26, 26, 128, 0, 256, 3, 1), (), 400000, 22413312),
+    ('y3_conv_wgrad_scratch_bytes', (5, 20, 28, 32, 0, 64, 3, 2), (), 40000, 1696000),
+    ('y3_conv_wgrad_wino_eligible', (5, 20, 28, 32, 0, 64, 3, 2), (), 40000, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (5, 20, 28, 32, 0, 64, 3, 2), (), 40000, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (5, 20, 28, 32, 0, 64, 3, 2), (), 40000, 221184),
+    ('y3_conv_wgrad_scratch_bytes', (5, 26, 26, 256, 0, 255, 1, 1), (), 400000, 28201216),
+    ('y3_conv_wgrad_wino_eligible', (5, 26, 26, 256, 0, 255, 1, 1), (), 400000, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (5, 26, 26, 256, 0, 255, 1, 1), (), 400000, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (5, 26, 26, 256, 0, 255, 1, 1), (), 400000, 3655680),
+    ('y3_conv_wgrad_scratch_bytes', (6, 96, 416, 3, 0, 32, 3, 1), (), 2555905, 14155776),
+    ('y3_conv_wgrad_wino_eligible', (6, 96, 416, 3, 0, 32, 3, 1), (), 2555905, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (6, 96, 416, 3, 0, 32, 3, 1), (), 2555905, 0),
+    ('y3_conv_wgrad_scratch_bytes', (64, 512, 512, 3, 0, 32, 3, 1), (), 67108865, 41195520),
+    ('y3_conv_wgrad_wino_eligible', (64, 512, 512, 3, 0, 32, 3, 1), (), 67108865, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (64, 512, 512, 3, 0, 32, 3, 1), (), 67108865, 0),
+    ('y3_conv_wgrad_scratch_bytes', (2, 20, 28, 64, 0, 32, 1, 1), (), 0, 286976),
+    ('y3_conv_wgrad_wino_eligible', (2, 20, 28, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (2, 20, 28, 64, 0, 32, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (2, 20, 28, 64, 0, 32, 1, 1), (), 0, 40960),
+    ('y3_conv_wgrad_scratch_bytes', (1, 6, 10, 32, 0, 64, 1, 1), (), 0, 16640),
+    ('y3_conv_wgrad_wino_eligible', (1, 6, 10, 32, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (1, 6, 10, 32, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (1, 6, 10, 32, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_scratch_bytes', (2, 13, 13, 64, 0, 192, 3, 1), (), 0, 4866304),
+    ('y3_conv_wgrad_wino_eligible', (2, 13, 13, 64, 0, 192, 3, 1), (), 0, 1),
+    ('y3_conv_wgrad_wino_scratch_bytes', (2, 13, 13, 64, 0, 192, 3, 1), (), 0, 5751040),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (2, 13, 13, 64, 0, 192, 3, 1), (), 0, 884736),
+    ('y3_conv_wgrad_scratch_bytes', (2, 26, 26, 64, 0, 128, 3, 2), (), 0, 3244288),
+    ('y3_conv_wgrad_wino_eligible', (2, 26, 26, 64, 0, 128, 3, 2), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (2, 26, 26, 64, 0, 128, 3, 2), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (2, 26, 26, 64, 0, 128, 3, 2), (), 0, 589824),
+    ('y3_conv_wgrad_scratch_bytes', (2, 25, 41, 128, 0, 64, 1, 1), (), 0, 2130176),
+    ('y3_conv_wgrad_wino_eligible', (2, 25, 41, 128, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_wino_scratch_bytes', (2, 25, 41, 128, 0, 64, 1, 1), (), 0, 0),
+    ('y3_conv_wgrad_bf16_scratch_bytes', (2, 25, 41, 128, 0, 64, 1, 1), (), 0, 294912),
+]
+
+# (dtype, batch, size, second stream on, y3_debug_conv_range_limit in force or 0, y3_net_train_workspace_bytes): all variables
+# trainable, 80 classes.  Recorded from the same library.
+TRAIN_WORKSPACE_ANSWERS = [
+    ('f32', 2, 64, 0, 0, 111795200),
+    ('f32', 2, 256, 0, 0, 354845952),
+    ('f32', 4, 256, 0, 0, 626124544),
+    ('f32', 4, 256, 0, 3000000, 626124544),
+    ('f32', 2, 64, 1, 0, 111795200),
+    ('f32', 2, 256, 1, 0, 367559936),
+    ('f32', 4, 256, 1, 0, 653387520),
+    ('f32', 4, 256, 1, 3000000, 653387520),
+    ('f32_wino', 2, 64, 0, 0, 141933568),
+    ('f32_wino', 2, 256, 0, 0, 365125888),
+    ('f32_wino', 4, 256, 0, 0, 626706176),
+    ('f32_wino', 4, 256, 0, 3000000, 626706176),
+    ('f32_wino', 2, 64, 1, 0, 142179328),
+    ('f32_wino', 2, 256, 1, 0, 368271616),
+    ('f32_wino', 4, 256, 1, 0, 653969152),
+    ('f32_wino', 4, 256, 1, 3000000, 653969152),
+    ('f32_bf16x6', 2, 64, 0, 0, 109403136),
+    ('f32_bf16x6', 2, 256, 0, 0, 364832000),
+    ('f32_bf16x6', 4, 256, 0, 0, 632801024),
+    ('f32_bf16x6', 4, 256, 0, 3000000, 632801024),
+    ('f32_bf16x6', 2, 64, 1, 0, 109583360),
+    ('f32_bf16x6', 2, 256, 1, 0, 365716736),
+    ('f32_bf16x6', 4, 256, 1, 0, 655050496),
+    ('f32_bf16x6', 4, 256, 1, 3000000, 655050496),
+    ('bf16', 2, 64, 0, 0, 42578944),
+    ('bf16', 2, 256, 0, 0, 190356736),
+    ('bf16', 4, 256, 0, 0, 361496320),
+    ('bf16', 4, 256, 0, 3000000, 361496320),
+    ('bf16', 2, 64, 1, 0, 42759168),
+    ('bf16', 2, 256, 1, 0, 200170752),
+    ('bf16', 4, 256, 1, 0, 382435072),
+    ('bf16', 4, 256, 1, 3000000, 382435072),
+]

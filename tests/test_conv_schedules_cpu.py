@@ -95,3 +95,63 @@ def test_host_answers_are_the_recorded_ones(L):
             wrong.append((fn, shape, extra, limit, want, got))
     assert not wrong, wrong
     assert len(C.HOST_ANSWERS) == 134
+
+
+def test_weight_gradient_host_answers_are_the_recorded_ones(L):
+    """The scratch sizes of the three weight-gradient families and the Winograd eligibility, against the table recorded ahead
+    of the one-plan refactor of the fp32 weight gradient (conv_schedule_cases.WGRAD_HOST_ANSWERS): the launcher walks the plan
+    the size query reads, so a split rule, a range cut or the stem's floor that moved shows up here, without a device."""
+    wrong = []
+    for fn, shape, extra, limit, want in C.WGRAD_HOST_ANSWERS:
+        if limit:
+            L.y3_debug_conv_range_limit(limit)
+        try:
+            got = getattr(L, fn)(ctypes.byref(C.desc(*shape)), *extra)
+        finally:
+            if limit:
+                L.y3_debug_conv_range_limit(0)
+        if got != want:
+            wrong.append((fn, shape, extra, limit, want, got))
+    assert not wrong, wrong
+    assert len(C.WGRAD_HOST_ANSWERS) == 100
+
+
+def test_train_workspace_bytes_are_the_recorded_ones(L):
+    """y3_net_train_workspace_bytes (a dry run through every route and scratch query) for the four train dtypes, with and
+    without the second stream, against conv_schedule_cases.TRAIN_WORKSPACE_ANSWERS."""
+    from yolov3_tensorflow_amd import training, _lib
+    from test_train_workspace_cpu import _Var
+    from test_train_gpu import _conv_name
+    layer_vars = []
+    for i, l in enumerate(training._Topology(80).layers):
+        base = _conv_name(i)
+        w = _Var(base + '/weights', (l['k'], l['k'], l['cin'], l['cout']))
+        if l['bn']:
+            bn = tuple(_Var(base + '/BatchNorm/' + s, (l['cout'],), trainable=s in ('gamma', 'beta'))
+                       for s in ('gamma', 'beta', 'moving_mean', 'moving_variance'))
+            layer_vars.append((w, bn, None))
+        else:
+            layer_vars.append((w, None, _Var(base + '/biases', (l['cout'],))))
+    table, _ = training._var_table(layer_vars)
+    net = ctypes.c_void_p()
+    _lib.check(L.y3_net_create(None, 80, ctypes.byref(net)))      # no context: sizing only
+    wrong = []
+    try:
+        for dtype, n, size, side, limit, want in C.TRAIN_WORKSPACE_ANSWERS:
+            _lib.check(L.y3_net_set_dtype(net, training._TRAIN_DTYPES[dtype]))
+            # any non-null stream handle: the dry run only asks whether there is one
+            _lib.check(L.y3_net_train_set_wgrad_stream(net, ctypes.c_void_p(0x1000) if side else None))
+            if limit:
+                L.y3_debug_conv_range_limit(limit)
+            try:
+                got = L.y3_net_train_workspace_bytes(net, table, n, size, size)
+            finally:
+                if limit:
+                    L.y3_debug_conv_range_limit(0)
+            if got != want:
+                wrong.append((dtype, n, size, side, limit, want, got))
+    finally:
+        _lib.check(L.y3_net_train_set_wgrad_stream(net, None))
+        L.y3_net_destroy(net)
+    assert not wrong, wrong
+    assert len(C.TRAIN_WORKSPACE_ANSWERS) == 32

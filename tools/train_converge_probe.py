@@ -2,7 +2,7 @@
 """Loss curve of the toy training loop of tests/test_train_script_gpu.py under experiment switches (is a different end
 state the chaos of a 200-step Adam memorisation, or a defect?).
 
-    python tools/train_converge_probe.py [--lr-drop]      # env: Y3_WGRAD_OLD_SPLIT=1, Y3_TRAIN_PER_TENSOR_UPDATE=1
+    python tools/train_converge_probe.py [--lr-drop]      # env: Y3_TRAIN_PER_TENSOR_UPDATE=1
 """
 import os
 import pathlib

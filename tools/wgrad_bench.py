@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Weight-gradient kernel (y3_conv_wgrad) on the layer shapes of BASELINE configs[3] (bs=64 @416).
 
-    python tools/wgrad_bench.py [--batch 64] [--iters 10]          # env Y3_WGRAD_OLD_SPLIT=1 = the round-1 split rule
+    python tools/wgrad_bench.py [--batch 64] [--iters 10]
 """
 import argparse
 import ctypes
@@ -55,9 +55,7 @@ def main():
             k, s, cin, cout, hw, n, ms, flop / ms / 1e9, cnt, '  [Winograd: TF/s counted as direct-algorithm FLOPs]' if wino else ''))
         tot_ms += ms * cnt
         tot_flop += flop * cnt
-    print('weighted: %.2f ms for %d layers, %.1f TF/s [old split %s]' % (
-        tot_ms, sum(c[-1] for c in SHAPES), tot_flop / tot_ms / 1e9,
-        os.environ.get('Y3_WGRAD_OLD_SPLIT', '0')))
+    print('weighted: %.2f ms for %d layers, %.1f TF/s' % (tot_ms, sum(c[-1] for c in SHAPES), tot_flop / tot_ms / 1e9))
 
 
 if __name__ == '__main__':

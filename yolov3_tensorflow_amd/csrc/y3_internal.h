@@ -196,6 +196,9 @@ int y3_conv_wino44_two_pass_impl(const y3_conv_desc* d);          // the form a 
 int y3_launch_conv_wino44(hipStream_t stream, const y3_conv_desc* d, const float* x, const float* u, const float* scale,
                           const float* shift, const float* residual, float* y, void* workspace, size_t workspace_bytes,
                           const y3_sk_opts* sk);
+// dw = the sum of nsplit partial tensors of 4 * n4 floats (y3_wgrad.hip; the Winograd weight gradient's splits too).
+// stem_sum_splits_kernel and wgrad_bf16_sum_kernel add in another order (other bits), so they stay kernels of their own.
+int y3_launch_wgrad_sum_splits(hipStream_t stream, const float* scratch, int nsplit, long long n4, float* dw);
 int y3_conv_wgrad_wino_eligible_impl(const y3_conv_desc* d);
 size_t y3_conv_wgrad_wino_scratch_bytes_impl(const y3_conv_desc* d);
 int y3_launch_conv_wgrad_wino(hipStream_t stream, const y3_conv_desc* d, const float* x, const float* dz, int dz_stride,

@@ -628,36 +628,41 @@ __global__ void __launch_bounds__(256) norm_finalize_kernel(const float* __restr
     if (threadIdx.x == 0) norm[0] = (float)sqrt(s);
 }
 
-// tf.clip_by_norm(g, clip) then the TF1 update rule.  kind: 0 sgd, 1 momentum, 2 adam,
-// 3 rmsprop.  hp: lr (or lr_t for adam), momentum, decay/beta1, beta2, eps.
+// The TF1 update rule on the clipped gradient gi.  kind: 0 sgd, 1 momentum, 2 adam, 3 rmsprop.
+// hp: lr (or lr_t for adam), momentum, decay/beta1, beta2, eps.
+__device__ __forceinline__ void mt_update_one(int kind, float& wi, float gi, float* s0, float* s1, long long i, float lr,
+                                              float momentum, float decay, float beta2, float eps) {
+    if (kind == 0) {
+        wi -= lr * gi;
+    } else if (kind == 1) {
+        const float acc = s0[i] * momentum + gi;
+        s0[i] = acc;
+        wi -= lr * acc;
+    } else if (kind == 2) {
+        const float m = s0[i] * decay + (1.f - decay) * gi;          // decay = beta1
+        const float v = s1[i] * beta2 + (1.f - beta2) * gi * gi;
+        s0[i] = m; s1[i] = v;
+        wi -= lr * m / (sqrtf(v) + eps);                              // lr = lr_t
+    } else {
+        const float ms = s0[i] * decay + (1.f - decay) * gi * gi;
+        const float mom = s1[i] * momentum + lr * gi / sqrtf(ms + eps);
+        s0[i] = ms; s1[i] = mom;
+        wi -= mom;
+    }
+}
+
+// tf.clip_by_norm(g, clip) then the update rule
 __global__ void __launch_bounds__(256) optimizer_update_kernel(float* __restrict__ w, float* __restrict__ g,
                                                                float* __restrict__ s0, float* __restrict__ s1,
                                                                const float* __restrict__ norm, float clip, int kind,
                                                                float lr, float momentum, float decay, float beta2,
                                                                float eps, long long n) {
-    const float nn = norm[0];
-    const float factor = clip / fmaxf(nn, clip);
+    const float factor = clip / fmaxf(norm[0], clip);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float gi = g[i] * factor;
         g[i] = gi;                                   // the clipped gradient stays observable
         float wi = w[i];
-        if (kind == 0) {
-            wi -= lr * gi;
-        } else if (kind == 1) {
-            const float acc = s0[i] * momentum + gi;
-            s0[i] = acc;
-            wi -= lr * acc;
-        } else if (kind == 2) {
-            const float m = s0[i] * decay + (1.f - decay) * gi;          // decay = beta1
-            const float v = s1[i] * beta2 + (1.f - beta2) * gi * gi;
-            s0[i] = m; s1[i] = v;
-            wi -= lr * m / (sqrtf(v) + eps);                              // lr = lr_t
-        } else {
-            const float ms = s0[i] * decay + (1.f - decay) * gi * gi;
-            const float mom = s1[i] * momentum + lr * gi / sqrtf(ms + eps);
-            s0[i] = ms; s1[i] = mom;
-            wi -= mom;
-        }
+        mt_update_one(kind, wi, gi, s0, s1, i, lr, momentum, decay, beta2, eps);
         w[i] = wi;
     }
 }
@@ -725,30 +730,7 @@ __global__ void __launch_bounds__(256) mt_norms_kernel(const MtDesc* __restrict_
     if (threadIdx.x == 0) norm[t] = (float)sqrt(s);
 }
 
-__device__ __forceinline__ void mt_update_one(int kind, float& wi, float& gi, float* s0, float* s1, long long i,
-                                              float factor, float lr, float momentum, float decay, float beta2,
-                                              float eps) {
-    gi *= factor;
-    if (kind == 0) {
-        wi -= lr * gi;
-    } else if (kind == 1) {
-        const float acc = s0[i] * momentum + gi;
-        s0[i] = acc;
-        wi -= lr * acc;
-    } else if (kind == 2) {
-        const float m = s0[i] * decay + (1.f - decay) * gi;          // decay = beta1
-        const float v = s1[i] * beta2 + (1.f - beta2) * gi * gi;
-        s0[i] = m; s1[i] = v;
-        wi -= lr * m / (sqrtf(v) + eps);                              // lr = lr_t
-    } else {
-        const float ms = s0[i] * decay + (1.f - decay) * gi * gi;
-        const float mom = s1[i] * momentum + lr * gi / sqrtf(ms + eps);
-        s0[i] = ms; s1[i] = mom;
-        wi -= mom;
-    }
-}
-
-// tf.clip_by_norm per tensor, then the TF1 update rule — the same arithmetic as optimizer_update_kernel
+// tf.clip_by_norm per tensor, then the TF1 update rule
 __global__ void __launch_bounds__(256) mt_update_kernel(const MtDesc* __restrict__ descs, int count,
                                                         const float* __restrict__ norm, float clip, int kind, float lr,
                                                         float momentum, float decay, float beta2, float eps) {
@@ -758,8 +740,8 @@ __global__ void __launch_bounds__(256) mt_update_kernel(const MtDesc* __restrict
     const long long base = (long long)(blockIdx.x - d.chunk_begin) * MT_CHUNK;
     const long long end = base + MT_CHUNK < d.n ? base + MT_CHUNK : d.n;
     for (long long i = base + threadIdx.x; i < end; i += 256) {
-        float gi = d.g[i], wi = d.w[i];
-        mt_update_one(kind, wi, gi, d.s0, d.s1, i, factor, lr, momentum, decay, beta2, eps);
+        float gi = d.g[i] * factor, wi = d.w[i];
+        mt_update_one(kind, wi, gi, d.s0, d.s1, i, lr, momentum, decay, beta2, eps);
         d.g[i] = gi;                                  // the clipped gradient stays observable
         d.w[i] = wi;
     }

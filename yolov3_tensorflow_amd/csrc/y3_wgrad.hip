@@ -344,16 +344,6 @@ static void wgrad_split(const y3_conv_desc* d, int* nsplit_out, int* chunk_out) 
     constexpr double SLOTS = 512.0;            // co-resident workgroups
     constexpr double T_K = 3.9, T_FIX = 6.0;   // us per K-step with two workgroups per CU; prologue + epilogue
     const double partial_us = 2.0 * (double)J * d->cout * 4.0 / 3.0e6;   // one partial tile set written + read at ~3 TB/s
-    if (const char* e = y3_exp_env("Y3_WGRAD_OLD_SPLIT"); e && e[0] == '1') {   // experiment hook: the round-1 rule
-        int nsplit = (1024 + tiles - 1) / tiles;
-        if (nsplit > 512) nsplit = 512;
-        if (nsplit > ksteps) nsplit = ksteps;
-        if (nsplit < 1) nsplit = 1;
-        const int chunk = ((ksteps + nsplit - 1) / nsplit) * WBK;
-        *chunk_out = chunk;
-        *nsplit_out = (int)((M + chunk - 1) / chunk);
-        return;
-    }
     int best_ns = 1, best_chunk = ksteps;
     double best = 1e300;
     const int ns_max = ksteps < 512 ? ksteps : 512;
@@ -369,46 +359,61 @@ static void wgrad_split(const y3_conv_desc* d, int* nsplit_out, int* chunk_out) 
     *nsplit_out = best_ns;
 }
 
-// The stem's work split over n images: pieces of 128 pixels of one image row; one round of co-resident workgroups (21 KB of
-// LDS each: six per CU)
-static void stem_split(const y3_conv_desc* d, int n, int* ppr_out, long long* pieces_out, int* nblk_out, int* chunk_out) {
+// The stem's work split: pieces of 128 pixels of one image row; one round of co-resident workgroups (21 KB of LDS each: six
+// per CU)
+static void stem_split(const y3_conv_desc* d, int* ppr_out, long long* pieces_out, int* nblk_out, int* chunk_out) {
     const int ppr = (d->w + 127) / 128;
-    const long long pieces = (long long)n * d->h * ppr;
+    const long long pieces = (long long)d->n * d->h * ppr;
     int nblk = (int)(pieces < 1536 ? pieces : 1536);
     const int chunk = (int)((pieces + nblk - 1) / nblk);
     nblk = (int)((pieces + chunk - 1) / chunk);
     *ppr_out = ppr; *pieces_out = pieces; *nblk_out = nblk; *chunk_out = chunk;
 }
 
-// A launch cut into image ranges keeps the split partials of every range, range-major, and one sum kernel adds them
-// all: the scratch holds the SUM of the ranges' splits (the stem: never less than the 4096 blocks it has always reserved).
-static size_t wgrad_scratch_need(const y3_conv_desc* d, const y3_image_ranges& rg) {
-    long long total = 0;
-    for (int i = 0; i < rg.n; ++i) {
-        y3_conv_desc dr = *d;
-        dr.n = rg.count[i];
-        if (d->cin == 3) {
-            int ppr, nblk, chunk;
-            long long pieces;
-            stem_split(&dr, dr.n, &ppr, &pieces, &nblk, &chunk);
-            total += nblk;
-        } else {
-            int nsplit, chunk;
-            wgrad_split(&dr, &nsplit, &chunk);
-            total += nsplit;
+// One plan per call: the image ranges and the split of each range's launch.  The size query reads its bytes and the
+// launcher walks its ranges, so what is reserved is what is written.  A cut launch keeps the split partials of every range,
+// range-major, and one sum kernel adds them all: the scratch holds the SUM of the ranges' splits (the stem: never less than the
+// 4096 blocks it has always reserved).
+struct WgradPlan {
+    struct Range {
+        int first;             // splits of the ranges before this one
+        int nsplit, chunk;     // general: splits, pixels per split; stem: workgroups (one partial each), pieces per workgroup
+        int ppr;               // stem: pieces per image row
+        long long pieces;      // stem: pieces of the range
+    };
+    const y3_image_ranges rg;
+    Range r[Y3_MAX_RANGES];
+    int total = 0;             // splits of all ranges
+    size_t bytes = 0;          // scratch
+    WgradPlan(const y3_conv_desc* d, int dz_stride) : rg(d, dz_stride) {
+        const bool stem = d->cin == 3;
+        for (int i = 0; i < rg.n; ++i) {
+            y3_conv_desc dr = *d;
+            dr.n = rg.count[i];
+            r[i].first = total;
+            if (stem) stem_split(&dr, &r[i].ppr, &r[i].pieces, &r[i].nsplit, &r[i].chunk);
+            else wgrad_split(&dr, &r[i].nsplit, &r[i].chunk);
+            total += r[i].nsplit;
         }
+        bytes = stem ? (size_t)(total > 4096 ? total : 4096) * 27 * 32 * sizeof(float)
+                     : (size_t)total * d->k * d->k * d->cin * d->cout * sizeof(float) + 256;
     }
-    if (d->cin == 3) return (size_t)(total > 4096 ? total : 4096) * 27 * 32 * sizeof(float);
-    return (size_t)total * d->k * d->k * d->cin * d->cout * sizeof(float) + 256;
-}
+};
 
 // (sized for dz rows of Cout rounded up to 4 floats: the densest dz y3_conv_wgrad takes.  A caller with wider rows whose launch
 // is cut differently is told "scratch too small" before anything runs.)
 extern "C" size_t y3_conv_wgrad_scratch_bytes(const y3_conv_desc* d) {
     if (!d || d->n <= 0 || d->cin <= 0 || d->cout <= 0 || d->stride <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    const y3_image_ranges rg(d, (d->cout + 3) / 4 * 4);
-    if (rg.n < 0) return 0;
-    return wgrad_scratch_need(d, rg);
+    const WgradPlan plan(d, (d->cout + 3) / 4 * 4);
+    return plan.rg.n < 0 ? 0 : plan.bytes;
+}
+
+int y3_launch_wgrad_sum_splits(hipStream_t stream, const float* scratch, int nsplit, long long n4, float* dw) {
+    long long nb = (n4 + 63) / 64;
+    if (nb > 8192) nb = 8192;
+    hipLaunchKernelGGL(wgrad_sum_splits_kernel, dim3((int)nb), dim3(256), 0, stream, scratch, nsplit, n4, dw);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
 }
 
 extern "C" int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* d, const float* x, const float* dz, int dz_stride,
@@ -420,75 +425,54 @@ extern "C" int y3_conv_wgrad(y3_ctx* ctx, const y3_conv_desc* d, const float* x,
     Y3_CHECK_ARG(dz_stride >= d->cout && dz_stride % 4 == 0, "y3_conv_wgrad: dz row stride must be >= Cout and a multiple of 4");
     Y3_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0, "y3_conv_wgrad: non-positive dimension");
     // image ranges: one range below 2^29 elements - then this is the single launch it has always been
-    const y3_image_ranges rg(d, dz_stride);
-    if (rg.n < 0) return rg.n;
-    Y3_CHECK_ARG(scratch_bytes >= wgrad_scratch_need(d, rg), "y3_conv_wgrad: scratch too small");
+    const WgradPlan plan(d, dz_stride);
+    if (plan.rg.n < 0) return plan.rg.n;
+    Y3_CHECK_ARG(scratch_bytes >= plan.bytes, "y3_conv_wgrad: scratch too small");
     Y3_CHECK_ARG((reinterpret_cast<size_t>(scratch) & 15) == 0, "y3_conv_wgrad: scratch must be 16-byte aligned");
-    const int Ho = d->h / d->stride, Wo = d->w / d->stride;
-    hipStream_t st = ctx->stream;
-    if (d->cin == 3) {
+    const bool stem = d->cin == 3;
+    if (stem)
         Y3_CHECK_ARG(d->k == 3 && d->cout == 32 && d->stride == 1 && dz_stride == 32,
                      "y3_conv_wgrad: Cin=3 is supported only as the 3x3 3->32 stem conv");
-        float* part = static_cast<float*>(scratch);
-        int total = 0;
-        for (int i = 0; i < rg.n; ++i) {
-            int ppr, nblk, chunk;
-            long long pieces;
-            stem_split(d, rg.count[i], &ppr, &pieces, &nblk, &chunk);
-            Y3_CHECK_ARG(pieces < (1LL << 30), "y3_conv_wgrad: too many pixels");
-            const size_t b = (size_t)rg.begin[i] * d->h * d->w;
-            hipLaunchKernelGGL(stem_wgrad_kernel, dim3(nblk), dim3(256), 0, st, x + b * 3, dz + b * 32, rg.count[i], d->h, d->w,
-                               ppr, (int)pieces, chunk, part + (size_t)total * 27 * 32);
-            Y3_CHECK_HIP(hipGetLastError());
-            total += nblk;
-        }
-        hipLaunchKernelGGL(stem_sum_splits_kernel, dim3(27), dim3(256), 0, st, part, total, dw_hwio);
-        Y3_CHECK_HIP(hipGetLastError());
-        return Y3_OK;
-    }
-    Y3_CHECK_ARG(d->cin % 4 == 0, "y3_conv_wgrad: Cin must be 3 or a multiple of 4");
-    static bool attr_set[Y3_MAX_DEVICES] = {};
-    const int dev_ = y3_current_device();
-    if (dev_ < 0 || !attr_set[dev_]) {
-        Y3_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<128, 2, 2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(2 * WBK * (WLD + 128) * sizeof(float))));
-        if (dev_ >= 0) attr_set[dev_] = true;
-    }
+    else
+        Y3_CHECK_ARG(d->cin % 4 == 0, "y3_conv_wgrad: Cin must be 3 or a multiple of 4");
+    const int Ho = d->h / d->stride, Wo = d->w / d->stride;
     const int J = d->k * d->k * d->cin;
     const int bnt = wgrad_co_tile(d->cout);
     const int tiles = ((J + 127) / 128) * ((d->cout + bnt - 1) / bnt);
     const size_t lds = (size_t)2 * WBK * (WLD + bnt) * sizeof(float);
-    int total = 0;                                   // splits written so far, all ranges
-    for (int i = 0; i < rg.n; ++i) {
-        y3_conv_desc dr = *d;
-        dr.n = rg.count[i];
+    hipStream_t st = ctx->stream;
+    float* part = static_cast<float*>(scratch);
+    for (int i = 0; i < plan.rg.n; ++i) {
+        const WgradPlan::Range& q = plan.r[i];
+        const int n = plan.rg.count[i];
+        const size_t b = (size_t)plan.rg.begin[i] * d->h * d->w;       // first input pixel of the range
+        if (stem) {
+            Y3_CHECK_ARG(q.pieces < (1LL << 30), "y3_conv_wgrad: too many pixels");
+            hipLaunchKernelGGL(stem_wgrad_kernel, dim3(q.nsplit), dim3(256), 0, st, x + b * 3, dz + b * 32, n, d->h, d->w, q.ppr,
+                               (int)q.pieces, q.chunk, part + (size_t)q.first * 27 * 32);
+            Y3_CHECK_HIP(hipGetLastError());
+            continue;
+        }
         WgradArgs a;
-        a.x = x + (size_t)rg.begin[i] * d->h * d->w * d->cin;
-        a.dz = dz + (size_t)rg.begin[i] * Ho * Wo * dz_stride;
-        a.N = dr.n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Ho = Ho; a.Wo = Wo; a.Cout = d->cout; a.CoP = dz_stride;
-        a.k = d->k; a.stride = d->stride; a.pad = d->k / 2; a.M = dr.n * Ho * Wo; a.J = J;
-        int nsplit;
-        wgrad_split(&dr, &nsplit, &a.chunk);
-        a.nsplit = nsplit;
+        a.x = x + b * d->cin;
+        a.dz = dz + (size_t)plan.rg.begin[i] * Ho * Wo * dz_stride;
+        a.N = n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Ho = Ho; a.Wo = Wo; a.Cout = d->cout; a.CoP = dz_stride;
+        a.k = d->k; a.stride = d->stride; a.pad = d->k / 2; a.M = n * Ho * Wo; a.J = J;
+        a.chunk = q.chunk; a.nsplit = q.nsplit;
         // one range of one split writes dw itself; with more ranges every split of every range goes to the scratch, so that
         // the one sum below adds them in one fixed order
-        a.out = (rg.n == 1 && nsplit == 1) ? dw_hwio : static_cast<float*>(scratch) + (size_t)total * J * d->cout;
-        const dim3 grid(tiles, nsplit);
+        a.out = plan.total == 1 ? dw_hwio : part + (size_t)q.first * J * d->cout;
+        const dim3 grid(tiles, q.nsplit);
         if (int rc = bnt == 128  ? y3_launch_lds<conv_wgrad_kernel<128, 2, 2>>(st, grid, dim3(256), lds, a)
                      : bnt == 64 ? y3_launch_lds<conv_wgrad_kernel<64, 2, 2>>(st, grid, dim3(256), lds, a)
                                  : y3_launch_lds<conv_wgrad_kernel<32, 4, 1>>(st, grid, dim3(256), lds, a))
             return rc;
-        total += nsplit;
     }
-    if (total > 1) {
-        const long long n4 = (long long)J * d->cout / 4;     // J = k*k*Cin, Cin % 4 == 0
-        long long nb = (n4 + 63) / 64;
-        if (nb > 8192) nb = 8192;
-        hipLaunchKernelGGL(wgrad_sum_splits_kernel, dim3((int)nb), dim3(256), 0, st, static_cast<float*>(scratch),
-                           total, n4, dw_hwio);
+    if (stem) {
+        hipLaunchKernelGGL(stem_sum_splits_kernel, dim3(27), dim3(256), 0, st, part, plan.total, dw_hwio);
         Y3_CHECK_HIP(hipGetLastError());
+    } else if (plan.total > 1) {
+        return y3_launch_wgrad_sum_splits(st, part, plan.total, (long long)J * d->cout / 4, dw_hwio);   // Cin % 4 == 0
     }
     return Y3_OK;
 }
-

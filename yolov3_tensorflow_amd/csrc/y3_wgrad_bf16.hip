@@ -165,6 +165,7 @@ __global__ void __launch_bounds__(256) wgrad_bf16_sum_kernel(const float* __rest
 
 struct Plan {
     int tiles, ksteps, chunk, nsplit;
+    size_t scratch;     // bytes of the nsplit fp32 partial tensors (one split writes dW itself: none)
 };
 
 Plan plan_of(const y3_conv_desc* d) {
@@ -177,15 +178,13 @@ Plan plan_of(const y3_conv_desc* d) {
     int ns = std::max(1, std::min((1024 + q.tiles - 1) / q.tiles, (q.ksteps + 7) / 8));
     q.chunk = (q.ksteps + ns - 1) / ns;
     q.nsplit = (q.ksteps + q.chunk - 1) / q.chunk;
+    q.scratch = q.nsplit > 1 ? (size_t)q.nsplit * J * d->cout * 4 : 0;
     return q;
 }
 
 }  // namespace
 
-extern "C" size_t y3_conv_wgrad_bf16_scratch_bytes(const y3_conv_desc* d) {
-    const Plan q = plan_of(d);
-    return q.nsplit > 1 ? (size_t)q.nsplit * d->k * d->k * d->cin * d->cout * 4 : 0;
-}
+extern "C" size_t y3_conv_wgrad_bf16_scratch_bytes(const y3_conv_desc* d) { return plan_of(d).scratch; }
 
 int y3_launch_conv_wgrad_bf16(hipStream_t stream, const y3_conv_desc* d, const void* x, const void* dz, int dz_stride, float* dw,
                               void* scratch, size_t scratch_bytes) {
@@ -199,9 +198,8 @@ int y3_launch_conv_wgrad_bf16(hipStream_t stream, const y3_conv_desc* d, const v
     Y3_CHECK_ARG((long long)d->n * d->h * d->w * d->cin < (1LL << 30) && m * dz_stride < (1LL << 30),
                  "y3_conv_wgrad_bf16: tensor exceeds 2^30 elements (32-bit byte offsets)");
     const Plan q = plan_of(d);
-    const size_t need = q.nsplit > 1 ? (size_t)q.nsplit * d->k * d->k * d->cin * d->cout * 4 : 0;
-    Y3_CHECK_ARG(scratch_bytes >= need && (need == 0 || scratch), "y3_conv_wgrad_bf16: scratch too small (%zu < %zu)",
-                 scratch_bytes, need);
+    Y3_CHECK_ARG(scratch_bytes >= q.scratch && (q.scratch == 0 || scratch), "y3_conv_wgrad_bf16: scratch too small (%zu < %zu)",
+                 scratch_bytes, q.scratch);
     WgArgs a;
     a.x = static_cast<const bf16_t*>(x); a.dz = static_cast<const bf16_t*>(dz);
     a.out = q.nsplit > 1 ? static_cast<float*>(scratch) : dw;

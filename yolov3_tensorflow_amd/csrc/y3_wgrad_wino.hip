@@ -307,26 +307,6 @@ __global__ void __launch_bounds__(256, 1) conv_wgrad_wino_kernel(const WgWinoArg
     }
 }
 
-// dw = sum over the splits in a fixed order (same scheme as y3_wgrad.hip: four lanes per group of four consecutive elements -
-// n = 9 * Cin * Cout is a multiple of 4 -, each adds every fourth split, then (q0 + q1) + (q2 + q3); dw at dword alignment)
-__global__ void __launch_bounds__(256) wgw_sum_splits_kernel(const float* __restrict__ scratch, int nsplit, long long n4,
-                                                             float* __restrict__ dw) {
-    __shared__ f32x4 part[4][64];
-    const int e = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const f32x4* s4 = reinterpret_cast<const f32x4*>(scratch);
-    for (long long base = (long long)blockIdx.x * 64; base < n4; base += (long long)gridDim.x * 64) {
-        const long long i = base + e;
-        f32x4 s = {0.f, 0.f, 0.f, 0.f};
-        if (i < n4)
-            for (int k = q; k < nsplit; k += 4) s += s4[(size_t)k * n4 + i];
-        part[q][e] = s;
-        __syncthreads();
-        if (q == 0 && i < n4)
-            *reinterpret_cast<f32x4_u*>(dw + 4 * i) = (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
-        __syncthreads();
-    }
-}
-
 constexpr int WGW_SLOTS = 256;      // one workgroup per CU (128 KB of LDS, 256 accumulator registers per wave)
 
 void wgw_split(const y3_conv_desc* d, int* nsplit, int* ksteps) {
@@ -382,14 +362,9 @@ int y3_launch_conv_wgrad_wino(hipStream_t stream, const y3_conv_desc* d, const f
     constexpr size_t lds = (size_t)4 * STAGE;
     const int wt = (d->cin / 64) * (d->cout / 64);
     if (int rc = y3_launch_lds<conv_wgrad_wino_kernel>(stream, dim3(wt, a.nsplit), dim3(256), lds, a)) return rc;
-    if (a.nsplit > 1) {
-        const long long n4 = (long long)9 * a.Cin * a.Cout / 4;
-        long long nb = (n4 + 63) / 64;
-        if (nb > 8192) nb = 8192;
-        hipLaunchKernelGGL(wgw_sum_splits_kernel, dim3((int)nb), dim3(256), 0, stream, static_cast<float*>(scratch),
-                           a.nsplit, n4, dw_hwio);
-        Y3_CHECK_HIP(hipGetLastError());
-    }
+    // the splits' partial tiles, added in a fixed order by the fp32 weight gradient's sum kernel (n = 9 * Cin * Cout is a multiple of 4)
+    if (a.nsplit > 1)
+        return y3_launch_wgrad_sum_splits(stream, static_cast<float*>(scratch), a.nsplit, (long long)9 * a.Cin * a.Cout / 4, dw_hwio);
     return Y3_OK;
 }
 
