@@ -527,12 +527,41 @@ int y3_pad_channels(y3_ctx* ctx, const float* src, int c_src, long long rows, in
  * 3*(5+C) floats of each row are written, the pad lanes behind them are left as they were.
  * The ignore mask takes the best IoU over every ground-truth box of the image on this scale: there is no limit on their
  * number (up to gh*gw*3, one per record), and the result does not depend on the order in which the boxes were collected,
- * so it is the same bits from run to run. */
+ * so it is the same bits from run to run.
+ *
+ * IoU box losses (y3_loss_layer_box; y3_loss_layer is its box_loss = Y3_BOX_MSE call).  Y3_BOX_MSE keeps the reference's
+ * box terms: squared error of the cell offset (xy) and of log(w / anchor) (wh), each weighted by 2 - area.  Under an IoU
+ * kind ONE box term replaces the two.  For a record with object_mask != 0, with the predicted box (px, py, pw, ph) in
+ * pixels as the reference's reorg_layer decodes it (px = (sigmoid(f0) + gx) * ratio_w, pw = exp(f2) * anchor_w, likewise
+ * y / h) and the true box (tx, ty, tw, th) = y_true[0:4]:
+ *   corners  c -+ s/2:  p1x = px - pw/2, p2x = px + pw/2, ... t2y = ty + th/2
+ *   inter = max(min(p2x,t2x) - max(p1x,t1x), 0) * max(min(p2y,t2y) - max(p1y,t1y), 0)
+ *   union = pw*ph + tw*th - inter + 1e-10,  iou = inter / union                          (as box_iou, model.py:307-345)
+ *   cw = max(p2x,t2x) - min(p1x,t1x),  ch = max(p2y,t2y) - min(p1y,t1y)                  (the enclosing box)
+ *   GIoU = iou - (cw*ch - union) / (cw*ch + 1e-10)
+ *   DIoU = iou - ((px-tx)^2 + (py-ty)^2) / (cw^2 + ch^2 + 1e-10)
+ *   CIoU = DIoU - alpha*v,  v = (4/pi^2) * (atan(tw/th) - atan(pw/ph))^2,  alpha = v / (1 - iou + v + 1e-10)
+ *   box term = sum over records of (1 - X) * object_mask * (2 - (tw/img_w)*(th/img_h)) * mixup_weight / N,  X the kind's
+ * quantity: the weight is the one the two squared-error terms carry.  alpha is a CONSTANT in the gradient (stop-gradient, as
+ * in the CIoU paper's implementation); the gradient w.r.t. f[0..3] runs through the decode (d px / d f0 = s(1-s) * ratio_w,
+ * d pw / d f2 = pw); at a tie of a min / max it is that of either side.  A record with object_mask == 0 contributes exactly
+ * 0 to the term and gets exactly 0 in its four box lanes whatever its logits hold (exp(f2) = inf included): no NaN or inf
+ * reaches loss4 or grad from it.  The box term is reported in the xy slot of loss4 / loss5 and the wh slot is exactly 0.0f;
+ * the total stays the sum of the slots.  The conf and class terms and the ignore mask (plain IoU) do not depend on the kind:
+ * their slots and gradient lanes are the same bits under every kind.  An unknown kind is Y3_EINVAL before any launch. */
+#define Y3_BOX_MSE 0
+#define Y3_BOX_GIOU 1
+#define Y3_BOX_DIOU 2
+#define Y3_BOX_CIOU 3
 size_t y3_loss_scratch_bytes(int n, int gh, int gw);
 int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
                   int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
                   int use_focal_loss, int accumulate, float* loss4, float* grad, int grad_stride, void* scratch,
                   size_t scratch_bytes);
+int y3_loss_layer_box(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
+                      int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
+                      int use_focal_loss, int box_loss, int accumulate, float* loss4, float* grad, int grad_stride,
+                      void* scratch, size_t scratch_bytes);
 
 /* ---- a14 as ONE call: the train step of train.py:72-115 on the y3_net graph ---------------------------------------
  * The per-op entry points above, sequenced by the library over a caller-owned workspace (whole-graph entries;
@@ -600,6 +629,10 @@ int y3_net_train_step(y3_net* net, const y3_train_var* vars, const float* x, int
  * than on one stream). */
 #define Y3_OWN_STREAM ((void*)(size_t)1)
 int y3_net_train_set_wgrad_stream(y3_net* net, void* stream);
+/* The box term of y3_net_train_loss / _step (a Y3_BOX_* kind, defined at y3_loss_layer_box), for all three scales; a new net
+ * has Y3_BOX_MSE.  Valid for every net dtype (the loss of the bf16 step is fp32 too); launches nothing and leaves the
+ * workspace size as it was.  An unknown kind is Y3_EINVAL and the net keeps the kind it had. */
+int y3_net_train_set_box_loss(y3_net* net, int box_loss);
 /* Optional synchronised batch norm for a data-parallel caller (off by default; a NULL fn switches it off again).  With a hook
  * set, y3_net_train_forward / _backward / _step run every BN layer's finalize as its two halves (y3_bn_sync_*): the sums half
  * is enqueued on the context's stream into exchange_dev, fn(user, layer, phase, doubles) is called on the host thread (phase 0

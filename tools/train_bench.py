@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of one training step (BASELINE configs[3]: 416x416, bs=64 per GPU, SGD) on synthetic batches.
 
-    python tools/train_bench.py [--batch 64] [--steps 5] [--optimizer sgd] [--head-only]
+    python tools/train_bench.py [--batch 64] [--steps 5] [--optimizer sgd] [--head-only] [--box_loss giou]
 
 --sync_bn measures what synchronised batch norm (training.Trainer(sync_bn=True)) costs on ONE GPU: a one-rank `nccl` group
 with the 144 collectives per step forced (as tests/test_rccl_gpu.py forces the gradient buckets), rounds of --steps steps
@@ -91,6 +91,8 @@ def main():
     ap.add_argument('--head-only', action='store_true')
     ap.add_argument('--precision', default='f32', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'],
                     help='the train mode (training._TRAIN_DTYPES): bf16 = mixed precision on the bf16 matrix pipe')
+    ap.add_argument('--box_loss', default='mse', choices=['mse', 'giou', 'diou', 'ciou'],
+                    help="the loss's box term (yolov3.box_loss): the reference's squared errors, or one IoU term")
     ap.add_argument('--sync_bn', action='store_true', help='A/B of synchronised batch norm over a one-rank nccl group')
     ap.add_argument('--rounds', type=int, default=4, help='--sync_bn: rounds per arm')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sync_bn_rate.txt'))
@@ -102,6 +104,7 @@ def main():
     import bench
     model = y3.yolov3(80, bench.ANCHORS, batch_norm_decay=0.99)
     model.compute_dtype = a.precision
+    model.box_loss = a.box_loss
     x = torch.rand((a.batch, a.size, a.size, 3), device='cuda')
     yt = synthetic_y_true(a.batch, a.size, 80, bench.ANCHORS, 0, 'cuda')
     with y3.variable_scope('yolov3'):
@@ -124,8 +127,8 @@ def main():
     flops = 3 * bench.conv_flops(model._train['topo_table'] if 'topo_table' in model._train else
                                  [(l['k'], l['stride'], l['cin'], l['cout'], l['bn']) for l in model._train['topo'].layers],
                                  a.batch, a.size, a.size).sum()
-    print('train step [%s]: batch %d @%d, %s%s: %.1f ms/step, %.1f images/s, %.1f TFLOP/s (3x forward FLOPs), loss %.3f, peak mem %.1f GB'
-          % (a.precision, a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
+    print('train step [%s, box_loss %s]: batch %d @%d, %s%s: %.1f ms/step, %.1f images/s, %.1f TFLOP/s (3x forward FLOPs), loss %.3f, peak mem %.1f GB'
+          % (a.precision, a.box_loss, a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
              flops / dt / 1e12, float(loss[0]), torch.cuda.max_memory_allocated() / 1e9))
 
 

@@ -118,6 +118,10 @@ def build_parser():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compute_dtype', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'], default='f32',
                    help='train-step mode: fp32-accurate modes, or bf16 = mixed precision on the bf16 matrix pipe')
+    p.add_argument('--box_loss', choices=['mse', 'giou', 'diou', 'ciou'], default='mse',
+                   help="the box term of the loss: mse = the reference's squared-error xy and wh terms; giou / diou / ciou = one "
+                        "IoU term in their place (yolov3.box_loss; defined in include/yolo355.h).  Under an IoU kind the "
+                        "progress line's `xy` field holds the IoU box term and its `wh` field is 0.00")
     p.add_argument('--sync_bn', type=_bool, default=False,
                    help='data-parallel runs: synchronised batch norm - every BN layer normalises with the statistics of the '
                         'global batch and all ranks keep the same moving statistics (training.Trainer(sync_bn=True)).  Cost: '
@@ -245,6 +249,7 @@ def main(argv=None):
     yolo_model = y3.yolov3(args.class_num, args.anchors, args.use_label_smooth, args.use_focal_loss,
                            args.batch_norm_decay, args.weight_decay, use_static_shape=False)
     yolo_model.compute_dtype = args.compute_dtype
+    yolo_model.box_loss = args.box_loss
     with y3.variable_scope('yolov3'):
         yolo_model.forward(torch.zeros((1, 64, 64, 3)), False)                 # create the variables
     variables = y3.global_variables(scope='yolov3')

@@ -95,6 +95,7 @@ PROTOTYPES = {
     "y3_net_train_step": (c_int, [c_void_p, POINTER(TrainVar), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   POINTER(TrainOpts), c_void_p, c_void_p, c_size_t, c_void_p, GradReadyFn, c_void_p]),
     "y3_net_train_set_wgrad_stream": (c_int, [c_void_p, c_void_p]),
+    "y3_net_train_set_box_loss": (c_int, [c_void_p, c_int]),
     "y3_net_train_set_bn_sync": (c_int, [c_void_p, BnSyncFn, c_void_p, c_void_p, c_size_t]),
     "y3_net_train_saved": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "y3_net_train_saved_type": (c_int, [c_void_p, c_int]),
@@ -177,6 +178,8 @@ PROTOTYPES = {
     "y3_loss_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "y3_loss_layer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               POINTER(c_float), c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    "y3_loss_layer_box": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  POINTER(c_float), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     "y3_process_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                POINTER(c_float), c_void_p, c_void_p, c_void_p]),
     "y3_feed_run": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,

@@ -446,6 +446,58 @@ __device__ __forceinline__ float iou_(float px, float py, float pw, float ph, fl
     return inter / (pw * ph + tw * th - inter + 1e-10f);
 }
 
+// The IoU box terms (include/yolo355.h, "IoU box losses"): X = GIoU / DIoU / CIoU of the predicted box (px, py, pw, ph) with
+// the true box (tx, ty, tw, th), and dX/d(px, py, pw, ph).  CIoU's alpha is a constant of the gradient.  At a tie of a min /
+// max the derivative is that of one of the two sides.  Each quotient's derivative is written as (du - q * dv) / v, which has
+// no difference of two large products in it: a predicted box of 1e13 px (a saturated f[2]) keeps its gradient.
+template <int BOX>
+__device__ __forceinline__ float box_term_(float px, float py, float pw, float ph, float tx, float ty, float tw, float th,
+                                           float& dpx, float& dpy, float& dpw, float& dph) {
+    const float p1x = px - pw / 2.f, p2x = px + pw / 2.f, p1y = py - ph / 2.f, p2y = py + ph / 2.f;
+    const float t1x = tx - tw / 2.f, t2x = tx + tw / 2.f, t1y = ty - th / 2.f, t2y = ty + th / 2.f;
+    const float iw = fmaxf(fminf(p2x, t2x) - fmaxf(p1x, t1x), 0.f);
+    const float ih = fmaxf(fminf(p2y, t2y) - fmaxf(p1y, t1y), 0.f);
+    const float inter = iw * ih;
+    const float uni = pw * ph + tw * th - inter + 1e-10f;
+    const float iou = inter / uni;
+    const float cw = fmaxf(p2x, t2x) - fminf(p1x, t1x), ch = fmaxf(p2y, t2y) - fminf(p1y, t1y);
+    // d(iw, cw)/d(px, pw) and d(ih, ch)/d(py, ph): which corner of the predicted box is the edge
+    const float ax1 = (iw > 0.f && p1x > t1x) ? 1.f : 0.f, ax2 = (iw > 0.f && p2x < t2x) ? 1.f : 0.f;
+    const float ay1 = (ih > 0.f && p1y > t1y) ? 1.f : 0.f, ay2 = (ih > 0.f && p2y < t2y) ? 1.f : 0.f;
+    const float bx1 = p1x < t1x ? 1.f : 0.f, bx2 = p2x > t2x ? 1.f : 0.f;
+    const float by1 = p1y < t1y ? 1.f : 0.f, by2 = p2y > t2y ? 1.f : 0.f;
+    const float cw_x = bx2 - bx1, cw_w = 0.5f * (bx2 + bx1), ch_y = by2 - by1, ch_h = 0.5f * (by2 + by1);
+    const float in_x = (ax2 - ax1) * ih, in_w = 0.5f * (ax2 + ax1) * ih;
+    const float in_y = (ay2 - ay1) * iw, in_h = 0.5f * (ay2 + ay1) * iw;
+    const float un_x = -in_x, un_w = ph - in_w, un_y = -in_y, un_h = pw - in_h;
+    dpx = (in_x - iou * un_x) / uni; dpw = (in_w - iou * un_w) / uni;
+    dpy = (in_y - iou * un_y) / uni; dph = (in_h - iou * un_h) / uni;
+    if constexpr (BOX == Y3_BOX_GIOU) {
+        const float ac = cw * ch, ace = ac + 1e-10f;
+        const float q = uni / ace;                         // d((ac - uni)/ace) = (d ac * q - d uni) / ace   (1e-10 of uni dropped)
+        dpx -= (cw_x * ch * q - un_x) / ace; dpw -= (cw_w * ch * q - un_w) / ace;
+        dpy -= (ch_y * cw * q - un_y) / ace; dph -= (ch_h * cw * q - un_h) / ace;
+        return iou - (ac - uni) / ace;
+    }
+    const float dx = px - tx, dy = py - ty;
+    const float c2 = cw * cw + ch * ch + 1e-10f;
+    const float pen = (dx * dx + dy * dy) / c2;
+    dpx -= (2.f * dx - pen * 2.f * cw * cw_x) / c2; dpw -= (-pen * 2.f * cw * cw_w) / c2;
+    dpy -= (2.f * dy - pen * 2.f * ch * ch_y) / c2; dph -= (-pen * 2.f * ch * ch_h) / c2;
+    float x = iou - pen;
+    if constexpr (BOX == Y3_BOX_CIOU) {
+        const float k = 0.40528473456935108577f;           // 4 / pi^2
+        const float da = atanf(tw / th) - atanf(pw / ph);
+        const float v = k * da * da;
+        const float alpha = v / (1.f - iou + v + 1e-10f);  // stop-gradient
+        const float hyp = pw * pw + ph * ph;               // d atan(pw/ph) = (ph dpw - pw dph) / (pw^2 + ph^2)
+        const float dv = -2.f * k * da * alpha;
+        dpw -= dv * (ph / hyp); dph += dv * (pw / hyp);
+        x -= alpha * v;
+    }
+    return x;
+}
+
 // A wave owns 64 consecutive (cell, anchor) records of one image.
 //   phase 1, one LANE per record: box decode, ignore mask (best IoU over ALL the image's ground-truth boxes of this scale:
 //            the first vmax read as LDS broadcasts, any beyond that as uniform loads from gt_boxes - a maximum over a set,
@@ -456,6 +508,8 @@ __device__ __forceinline__ float iou_(float px, float py, float pw, float ph, fl
 //            and ALL the chunk's gradients written out contiguously.
 // (The form this replaces ran one wave per record with the box / conf arithmetic on lane 0 alone: 0.84 ms for the
 // 52-grid of a bs=64 batch, 530 MB; profiles/r02_train_c4_kernel_stats.csv.)
+// BOX (Y3_BOX_*): 0 keeps the reference's xy / wh terms; an IoU kind replaces them by one box term, summed in the xy slot.
+template <int BOX>
 __global__ void __launch_bounds__(256) loss_kernel(const LossArgs a) {
     extern __shared__ float gts[];                         // [V][4] of this image
     __shared__ float red[4][4];
@@ -502,25 +556,40 @@ __global__ void __launch_bounds__(256) loss_kernel(const LossArgs a) {
             const float ignore = best < 0.5f ? 1.f : 0.f;
             const float bls = 2.f - (y2 / a.img_w) * (y3 / a.img_h);
             const float wgt = m * bls * mixw;
-            // xy (model.py:248-249,276)
-            const float txy0 = y0 / a.ratio_w - (float)gx, txy1 = y1 / a.ratio_h - (float)gy;
-            const float pxy0 = px / a.ratio_w - (float)gx, pxy1 = py / a.ratio_h - (float)gy;
-            const float d0 = txy0 - pxy0, d1 = txy1 - pxy1;
-            l_xy += (d0 * d0 + d1 * d1) * wgt;
-            g0 = -2.f * d0 * wgt * sx * (1.f - sx) * invN;
-            g1 = -2.f * d1 * wgt * sy * (1.f - sy) * invN;
-            // wh (model.py:254-262,277)
-            float tt0 = y2 / a.anc_w[anc], tt1 = y3 / a.anc_h[anc];
-            float pt0 = pw / a.anc_w[anc], pt1 = ph / a.anc_h[anc];
-            tt0 = tt0 == 0.f ? 1.f : tt0; tt1 = tt1 == 0.f ? 1.f : tt1;
-            const bool pz0 = pt0 == 0.f, pz1 = pt1 == 0.f;
-            pt0 = pz0 ? 1.f : pt0; pt1 = pz1 ? 1.f : pt1;
-            const bool in0 = !pz0 && pt0 >= 1e-9f && pt0 <= 1e9f, in1 = !pz1 && pt1 >= 1e-9f && pt1 <= 1e9f;
-            const float e0 = logf(fminf(fmaxf(tt0, 1e-9f), 1e9f)) - logf(fminf(fmaxf(pt0, 1e-9f), 1e9f));
-            const float e1 = logf(fminf(fmaxf(tt1, 1e-9f), 1e9f)) - logf(fminf(fmaxf(pt1, 1e-9f), 1e9f));
-            l_wh += (e0 * e0 + e1 * e1) * wgt;
-            g2 = in0 ? -2.f * e0 * wgt * invN : 0.f;     // d log(exp(t)*const)/dt = 1 inside the clip range
-            g3 = in1 ? -2.f * e1 * wgt * invN : 0.f;
+            if constexpr (BOX == Y3_BOX_MSE) {
+                // xy (model.py:248-249,276)
+                const float txy0 = y0 / a.ratio_w - (float)gx, txy1 = y1 / a.ratio_h - (float)gy;
+                const float pxy0 = px / a.ratio_w - (float)gx, pxy1 = py / a.ratio_h - (float)gy;
+                const float d0 = txy0 - pxy0, d1 = txy1 - pxy1;
+                l_xy += (d0 * d0 + d1 * d1) * wgt;
+                g0 = -2.f * d0 * wgt * sx * (1.f - sx) * invN;
+                g1 = -2.f * d1 * wgt * sy * (1.f - sy) * invN;
+                // wh (model.py:254-262,277)
+                float tt0 = y2 / a.anc_w[anc], tt1 = y3 / a.anc_h[anc];
+                float pt0 = pw / a.anc_w[anc], pt1 = ph / a.anc_h[anc];
+                tt0 = tt0 == 0.f ? 1.f : tt0; tt1 = tt1 == 0.f ? 1.f : tt1;
+                const bool pz0 = pt0 == 0.f, pz1 = pt1 == 0.f;
+                pt0 = pz0 ? 1.f : pt0; pt1 = pz1 ? 1.f : pt1;
+                const bool in0 = !pz0 && pt0 >= 1e-9f && pt0 <= 1e9f, in1 = !pz1 && pt1 >= 1e-9f && pt1 <= 1e9f;
+                const float e0 = logf(fminf(fmaxf(tt0, 1e-9f), 1e9f)) - logf(fminf(fmaxf(pt0, 1e-9f), 1e9f));
+                const float e1 = logf(fminf(fmaxf(tt1, 1e-9f), 1e9f)) - logf(fminf(fmaxf(pt1, 1e-9f), 1e9f));
+                l_wh += (e0 * e0 + e1 * e1) * wgt;
+                g2 = in0 ? -2.f * e0 * wgt * invN : 0.f;     // d log(exp(t)*const)/dt = 1 inside the clip range
+                g3 = in1 ? -2.f * e1 * wgt * invN : 0.f;
+            } else {
+                // one IoU term in place of the two (the wh slot stays 0); d/df runs through the decode: dpx/df0 =
+                // sx (1 - sx) ratio_w, dpw/df2 = pw.  Selected on m, not multiplied: a record without an object may hold
+                // logits whose pw is inf or 0, and the inf - inf that follows must reach neither the sums nor grad.
+                float dpx, dpy, dpw, dph;
+                const float xv = box_term_<BOX>(px, py, pw, ph, y0, y1, y2, y3, dpx, dpy, dpw, dph);
+                const bool obj = m != 0.f;
+                const float gw_ = -wgt * invN;
+                l_xy += obj ? (1.f - xv) * wgt : 0.f;
+                g0 = obj ? gw_ * dpx * (sx * (1.f - sx) * a.ratio_w) : 0.f;
+                g1 = obj ? gw_ * dpy * (sy * (1.f - sy) * a.ratio_h) : 0.f;
+                g2 = obj ? gw_ * dpw * pw : 0.f;
+                g3 = obj ? gw_ * dph * ph : 0.f;
+            }
             // conf (model.py:280-292)
             const float pc = sigmoid_(xc);
             const float cmask = m + (1.f - m) * ignore;
@@ -1080,12 +1149,13 @@ extern "C" size_t y3_loss_scratch_bytes(int n, int gh, int gw) {
            blocks * n * 4 * sizeof(float) + 256;
 }
 
-extern "C" int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
-                             int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
-                             int use_focal_loss, int accumulate, float* loss4, float* grad, int grad_stride,
-                             void* scratch, size_t scratch_bytes) {
+extern "C" int y3_loss_layer_box(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
+                                 int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
+                                 int use_focal_loss, int box_loss, int accumulate, float* loss4, float* grad,
+                                 int grad_stride, void* scratch, size_t scratch_bytes) {
     Y3_CHECK_ARG(ctx && feature_map && y_true && anchors3_host && loss4 && grad && scratch,
                  "y3_loss_layer: null argument");
+    Y3_CHECK_ARG(box_loss >= Y3_BOX_MSE && box_loss <= Y3_BOX_CIOU, "y3_loss_layer: unknown box_loss kind %d", box_loss);
     Y3_CHECK_ARG(n > 0 && gh > 0 && gw > 0 && class_num > 0 && img_h > 0 && img_w > 0, "y3_loss_layer: bad shape");
     Y3_CHECK_ARG(scratch_bytes >= y3_loss_scratch_bytes(n, gh, gw), "y3_loss_layer: scratch too small");
     Y3_CHECK_ARG(grad_stride >= 3 * (5 + class_num), "y3_loss_layer: grad_stride smaller than 3*(5+C)");
@@ -1115,12 +1185,22 @@ extern "C" int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float*
     // order in which the collecting kernel's atomic counter handed out the slots.
     a.vmax = cells < 2048 ? cells : 2048;
     const size_t lds = (size_t)a.vmax * 4 * sizeof(float);
-    hipLaunchKernelGGL(loss_kernel, dim3(blocks, n), dim3(256), lds, ctx->stream, a);
+    auto kernel = box_loss == Y3_BOX_GIOU ? loss_kernel<Y3_BOX_GIOU> : box_loss == Y3_BOX_DIOU ? loss_kernel<Y3_BOX_DIOU> :
+                  box_loss == Y3_BOX_CIOU ? loss_kernel<Y3_BOX_CIOU> : loss_kernel<Y3_BOX_MSE>;
+    hipLaunchKernelGGL(kernel, dim3(blocks, n), dim3(256), lds, ctx->stream, a);
     Y3_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(4), dim3(256), 0, ctx->stream, a.partial, blocks * n,
                        1.f / (float)n, accumulate, loss4);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
+}
+
+extern "C" int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
+                             int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
+                             int use_focal_loss, int accumulate, float* loss4, float* grad, int grad_stride,
+                             void* scratch, size_t scratch_bytes) {
+    return y3_loss_layer_box(ctx, feature_map, y_true, n, gh, gw, class_num, img_h, img_w, anchors3_host, use_label_smooth,
+                             use_focal_loss, Y3_BOX_MSE, accumulate, loss4, grad, grad_stride, scratch, scratch_bytes);
 }
 
 // ---- optimizer ----------------------------------------------------------------------------------------

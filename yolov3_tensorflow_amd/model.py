@@ -23,6 +23,10 @@ N_BODY_CONVS = 52  # utils/layer_utils.py:24-68
 NET_DTYPES = {'f32': 0, 'bf16': 1, 'f32_bf16x6': 2, 'f32_bf16x3': 3, 'f32_wino': 4}
 
 
+# box_loss -> the Y3_BOX_* kind of include/yolo355.h: 'mse' the reference's squared-error xy / wh terms, else one IoU term
+BOX_LOSSES = {'mse': 0, 'giou': 1, 'diou': 2, 'ciou': 3}
+
+
 _SIDE_STREAMS = {}      # (device index, parts) -> the side streams of yolov3._forward_on_streams, shared by every model
 
 class yolov3(object):
@@ -45,6 +49,19 @@ class yolov3(object):
         # matrix pipe, see NET_DTYPES) or 'bf16' (bf16 storage, fp32 accumulation; BASELINE configs[4]);
         # an attribute rather than a constructor argument so that the reference's signature is unchanged
         self.compute_dtype = 'f32'
+        # the box term of the loss, 'mse' | 'giou' | 'diou' | 'ciou' (BOX_LOSSES; defined in include/yolo355.h at
+        # y3_loss_layer_box): under an IoU kind loss_layer / compute_loss report the box term as xy_loss and wh_loss is 0
+        self.box_loss = 'mse'
+
+    @property
+    def box_loss(self):
+        return self._box_loss
+
+    @box_loss.setter
+    def box_loss(self, name):
+        if name not in BOX_LOSSES:
+            raise ValueError("box_loss must be one of %s (got %r)" % (sorted(BOX_LOSSES), name))
+        self._box_loss = name
 
     # ------------------------------------------------------------------------------------------
     # variables

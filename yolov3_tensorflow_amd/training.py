@@ -127,6 +127,7 @@ def _train_net(model, ctx, dev=None):
         _lib.check(L.y3_net_train_set_wgrad_stream(st['net'], ctypes.c_void_p(handle) if handle else None))
         st['wgrad_key'] = key
         st['ws_shape'] = None            # (the allocation sequence of backward changes with it)
+    _set_box_loss(model, st)
     # synchronised batch norm (include/yolo355.h: y3_net_train_set_bn_sync): the distributed.BnSync a Trainer(sync_bn=True)
     # left on the model, installed while it is active
     sync = getattr(model, 'bn_sync', None)
@@ -145,6 +146,23 @@ def _train_net(model, ctx, dev=None):
             st['bn_sync_cb'] = (cb, sync)        # (kept alive while the net may call it)
         st['bn_sync_key'] = key
     return st['net']
+
+
+def _box_kind(model):
+    """The Y3_BOX_* kind of model.box_loss ('mse' for a model object from before the attribute)."""
+    from .model import BOX_LOSSES
+    name = getattr(model, 'box_loss', 'mse')
+    if name not in BOX_LOSSES:
+        raise ValueError("box_loss must be one of %s (got %r)" % (sorted(BOX_LOSSES), name))
+    return BOX_LOSSES[name]
+
+
+def _set_box_loss(model, st):
+    """model.box_loss on the train net (include/yolo355.h: y3_net_train_set_box_loss), whenever either has changed."""
+    key = (_box_kind(model), st['net'].value)
+    if st.get('box_loss_key') != key:
+        _lib.check(_lib.lib().y3_net_train_set_box_loss(st['net'], key[0]))
+        st['box_loss_key'] = key
 
 
 def _checked(model, rc):
@@ -267,16 +285,17 @@ def _loss_one_scale(model, fm, y_true, anchors, loss4, accumulate, grad):
     st = _train_state(model)
     sc = _scratch(st, 'loss', L.y3_loss_scratch_bytes(n, gh, gw), fm.device)
     anc = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 2))
-    _lib.check(L.y3_loss_layer(fw.context(fm.device), fw.ptr(fm), fw.ptr(y_true), n, gh, gw, C,
-                               int(model.img_size[0]), int(model.img_size[1]),
-                               anc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                               1 if model.use_label_smooth else 0, 1 if model.use_focal_loss else 0,
-                               1 if accumulate else 0, fw.ptr(loss4), fw.ptr(grad), int(grad.shape[-1]),
-                               fw.ptr(sc), ctypes.c_size_t(sc.numel())))
+    _lib.check(L.y3_loss_layer_box(fw.context(fm.device), fw.ptr(fm), fw.ptr(y_true), n, gh, gw, C,
+                                   int(model.img_size[0]), int(model.img_size[1]),
+                                   anc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                   1 if model.use_label_smooth else 0, 1 if model.use_focal_loss else 0, _box_kind(model),
+                                   1 if accumulate else 0, fw.ptr(loss4), fw.ptr(grad), int(grad.shape[-1]),
+                                   fw.ptr(sc), ctypes.c_size_t(sc.numel())))
 
 
 def loss_layer(model, feature_map_i, y_true, anchors):
-    """reference model.py:192-304: returns (xy_loss, wh_loss, conf_loss, class_loss) device scalars."""
+    """reference model.py:192-304: returns (xy_loss, wh_loss, conf_loss, class_loss) device scalars.  With model.box_loss an
+    IoU kind, xy_loss is the IoU box term and wh_loss is 0 (include/yolo355.h: y3_loss_layer_box)."""
     fm = fw.as_device_f32(feature_map_i)
     loss4 = torch.zeros(4, dtype=torch.float32, device=fm.device)
     grad = torch.zeros(tuple(fm.shape[:3]) + (fm.shape[3],), dtype=torch.float32, device=fm.device)
@@ -298,6 +317,7 @@ def compute_loss(model, y_pred, y_true):
             if tuple(y.shape) != tuple(f.shape[:3]) + (3, 6 + int(model.class_num)):
                 raise ValueError("y_true shape %s does not match the feature map %s" % (tuple(y.shape), tuple(f.shape)))
         opts, anc = _opts(model)
+        _set_box_loss(model, st)         # (the attribute may have changed since the forward)
         loss5 = torch.empty(5, dtype=torch.float32, device=dev)
         _lib.check(L.y3_net_train_loss(st['net'], fw.ptr(yt[0]), fw.ptr(yt[1]), fw.ptr(yt[2]), ctypes.byref(opts),
                                        fw.ptr(loss5)))
