@@ -41,11 +41,16 @@ OPTIONS = (
     ('coco_metric', _flag, False, 'true: also report the twelve COCO numbers (AP@[.50:.95], AP50, AP75, AP / AR by size, AR@1/10/100); '
                                   'on the device with --map_on_device true, else eval_utils.coco_eval on the host'),
 )
+# options about the checkpoint rather than the evaluation
+RESTORE_OPTIONS = (
+    ('use_ema', _flag, False, 'true: evaluate the weight moving averages a native .npz of a run with --ema_decay holds '
+                              '(<variable>/ExponentialMovingAverage) instead of the raw weights'),
+)
 
 
 def build_parser():
     parser = argparse.ArgumentParser(description="YOLO-V3 eval procedure.")
-    for name, kind, default, text in OPTIONS:
+    for name, kind, default, text in OPTIONS + RESTORE_OPTIONS:
         extra = {'nargs': '*'} if isinstance(default, list) else {}
         parser.add_argument('--' + name, type=kind, default=default, help=text, **extra)
     return parser
@@ -59,7 +64,7 @@ def main(argv=None):
     from yolov3_tensorflow_amd.utils.eval_utils import get_preds_batch, voc_eval, parse_gt_rec, DeviceEval
     from yolov3_tensorflow_amd.utils import eval_utils
     from yolov3_tensorflow_amd.utils.misc_utils import (parse_anchors, read_class_names, AverageMeter, load_weights,
-                                                        run_ops, Saver)
+                                                        run_ops, restore_for_inference)
     from yolov3_tensorflow_amd.utils.nms_utils import gpu_nms_batched
 
     args.anchors = parse_anchors(args.anchor_path)
@@ -73,8 +78,10 @@ def main(argv=None):
     with y3.variable_scope('yolov3'):
         yolo_model.forward(torch.zeros((1, 64, 64, 3)), False)            # create the variables
         if args.restore_path.endswith('.npz'):       # native checkpoint (train.py best_model_*.npz, convert_weight.py)
-            Saver(y3.global_variables(scope='yolov3')).restore(args.restore_path)
+            restore_for_inference(y3.global_variables(scope='yolov3'), args.restore_path, use_ema=args.use_ema)
         else:
+            if args.use_ema:
+                print('--use_ema true: a darknet .weights file holds no weight moving averages; using the weights as they are')
             run_ops(load_weights(y3.global_variables(scope='yolov3'), args.restore_path))
 
     print('\n----------- start to eval -----------\n')

@@ -851,6 +851,33 @@ int y3_clip_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* params, int
                          float clip_norm, float lr, float momentum, float decay, float beta2, float eps,
                          void* scratch, size_t scratch_bytes);
 
+/* Weight moving average: TF1's tf.train.ExponentialMovingAverage(decay, num_updates).apply(update_vars) with
+ * zero_debias=False, kept by the update kernel.  After the step's update of a variable w:
+ *     d_t    = min(decay, (1 + t) / (10 + t))     with warm-up (num_updates = t), else d_t = decay
+ *     shadow = shadow - (1 - d_t) * (shadow - w_new)
+ *   t       the trainer's global_step BEFORE this step increments it (a resumed run continues the ramp).
+ *   shadow  one fp32 tensor per UPDATED variable, of the variable's shape; it starts as a copy of the variable (or with the
+ *           value a checkpoint stored).  A variable the step does not update is its own average and has no shadow; BN moving
+ *           mean / variance are not trainable and are not averaged (they are averages already).
+ *   ema_step = 1 - d_t is what the ABI carries: the host forms it in double and passes ONE float.  Passing `decay` would
+ *           make the kernel form 1 - float32(decay), and 1 - float32(0.9998) is 3e-4 (relative) away from 0.0002 - an error
+ *           on every step of the average.
+ *   arithmetic: s + (-ema_step) * (s - w_new) in fp32, the difference rounded once and the multiply-add fused (two
+ *           roundings; error <= 5 * 2^-24 * max(|s|, |w_new|) with room to spare), the same expression in both entries
+ *           below, for the fp32 and the bf16 train step alike (variables are fp32 in both).  ema_step = 0 writes no shadow.
+ * y3_clip_update_multi_ema: y3_clip_update_multi (same three launches; w, g, slot0, slot1 get the same bits) whose third
+ *   launch also updates ema[i], the shadow of params[i], from the w it is about to store.  `ema` is a HOST array of `count`
+ *   device pointers (uploaded with the descriptors); a NULL entry = that tensor has no shadow.  A shadow has the alignment
+ *   contract of w (16 bytes where n %% 4 == 0, else 4).  scratch: y3_clip_update_multi_ema_scratch_bytes(params, count),
+ *   16-byte aligned.  Y3_EINVAL before any launch: what y3_clip_update_multi refuses, a NULL `ema` array, ema_step outside
+ *   [0, 1] or not finite, a misaligned shadow, a shadow equal to or overlapping its tensor's w, g or slots.
+ * y3_ema_update: the same rule for one tensor of n elements (for a host that updates through y3_clip_update). */
+size_t y3_clip_update_multi_ema_scratch_bytes(const y3_param_desc* params, int count);
+int y3_clip_update_multi_ema(y3_ctx* ctx, int kind, const y3_param_desc* params, int count, float grad_scale,
+                             float clip_norm, float lr, float momentum, float decay, float beta2, float eps,
+                             float* const* ema, float ema_step, void* scratch, size_t scratch_bytes);
+int y3_ema_update(y3_ctx* ctx, float* shadow, const float* w, long long n, float ema_step);
+
 #ifdef __cplusplus
 }
 #endif

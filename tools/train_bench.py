@@ -93,6 +93,8 @@ def main():
                     help='the train mode (training._TRAIN_DTYPES): bf16 = mixed precision on the bf16 matrix pipe')
     ap.add_argument('--box_loss', default='mse', choices=['mse', 'giou', 'diou', 'ciou'],
                     help="the loss's box term (yolov3.box_loss): the reference's squared errors, or one IoU term")
+    ap.add_argument('--ema_decay', type=float, default=0,
+                    help='above 0: keep the weight moving average in the update kernel (training.Trainer(ema_decay=...))')
     ap.add_argument('--sync_bn', action='store_true', help='A/B of synchronised batch norm over a one-rank nccl group')
     ap.add_argument('--rounds', type=int, default=4, help='--sync_bn: rounds per arm')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sync_bn_rate.txt'))
@@ -115,7 +117,7 @@ def main():
             upd = [v for v in y3.global_variables(scope='yolov3') if v.op_name.startswith('yolov3/yolov3_head')]
         if a.sync_bn:
             return sync_bn_ab(a, model, upd, x, yt)
-        trainer = training.Trainer(model, config_optimizer(a.optimizer, 1e-4), update_vars=upd)
+        trainer = training.Trainer(model, config_optimizer(a.optimizer, 1e-4), update_vars=upd, ema_decay=a.ema_decay)
         for _ in range(2):
             loss = trainer.step(x, yt)
         torch.cuda.synchronize()
@@ -127,8 +129,8 @@ def main():
     flops = 3 * bench.conv_flops(model._train['topo_table'] if 'topo_table' in model._train else
                                  [(l['k'], l['stride'], l['cin'], l['cout'], l['bn']) for l in model._train['topo'].layers],
                                  a.batch, a.size, a.size).sum()
-    print('train step [%s, box_loss %s]: batch %d @%d, %s%s: %.1f ms/step, %.1f images/s, %.1f TFLOP/s (3x forward FLOPs), loss %.3f, peak mem %.1f GB'
-          % (a.precision, a.box_loss, a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
+    print('train step [%s, box_loss %s%s]: batch %d @%d, %s%s: %.1f ms/step, %.1f images/s, %.1f TFLOP/s (3x forward FLOPs), loss %.3f, peak mem %.1f GB'
+          % (a.precision, a.box_loss, ', ema_decay %g' % a.ema_decay if a.ema_decay else '', a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
              flops / dt / 1e12, float(loss[0]), torch.cuda.max_memory_allocated() / 1e9))
 
 

@@ -127,6 +127,14 @@ def build_parser():
                         'global batch and all ranks keep the same moving statistics (training.Trainer(sync_bn=True)).  Cost: '
                         'two small collectives per BN layer per step, 144 in total; all ranks need the same --batch_size, '
                         '--update_part and image size')
+    p.add_argument('--ema_decay', type=float, default=0,
+                   help='above 0 (e.g. 0.9998): keep an exponential moving average of every trained variable, written by the '
+                        'update kernel (training.Trainer(ema_decay=...)); validation, the best_model_* files and the periodic '
+                        '.weights files then use the averages, and the .npz checkpoints store them as '
+                        '<variable>/ExponentialMovingAverage beside the raw weights')
+    p.add_argument('--ema_warmup', type=_bool, default=True,
+                   help='ramp the decay as min(ema_decay, (1 + step) / (10 + step)), like tf.train.ExponentialMovingAverage '
+                        'with num_updates')
     return p
 
 
@@ -279,7 +287,12 @@ def main(argv=None):
         if resumed_step is not None and args.global_step == 0:
             args.global_step = int(resumed_step)
     trainer = training.Trainer(yolo_model, optimizer, update_vars=update_vars, global_step=float(args.global_step),
-                               process_group=dist.group.WORLD if world > 1 else None, sync_bn=args.sync_bn)
+                               process_group=dist.group.WORLD if world > 1 else None, sync_bn=args.sync_bn,
+                               ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+    if args.ema_decay and args.restore_path.endswith('.npz'):
+        # a resumed run continues the averages the checkpoint holds (of restored variables only, like the slots)
+        restored = set(v.op_name for v in to_restore)
+        Saver([v for v in variables if v.op_name in restored]).restore(args.restore_path, variables=False, averages=trainer)
     gpu_nms_op = functools.partial(gpu_nms, num_classes=args.class_num, max_boxes=args.nms_topk,
                                    score_thresh=args.score_threshold, nms_thresh=args.nms_threshold)
     if rank == 0:
@@ -330,23 +343,26 @@ def main(argv=None):
                         'Gradient exploded! Please train again and you may need modify some parameters.')
         if rank == 0 and epoch % args.save_epoch == 0 and epoch > 0 and meters[0].average <= 2.:
             os.makedirs(args.save_dir, exist_ok=True)
-            save_weights(variables, os.path.join(args.save_dir, 'model-epoch_{}_step_{}_loss_{:.4f}_lr_{:.5g}.weights'
-                                                 .format(epoch, int(trainer.global_step), meters[0].average, lr)))
+            with trainer.averaged():        # (the averaged weights when --ema_decay is on; the variables as they are otherwise)
+                save_weights(variables, os.path.join(args.save_dir, 'model-epoch_{}_step_{}_loss_{:.4f}_lr_{:.5g}.weights'
+                                                     .format(epoch, int(trainer.global_step), meters[0].average, lr)))
         if epoch % args.val_evaluation_epoch == 0 and epoch >= args.warm_up_epoch:
-            mAP, rec, prec, vloss, info = validate(yolo_model, y3, args, val_lines)
-            history['mAP'].append(mAP)
-            info = '======> Epoch: {}, global_step: {}, lr: {:.6g} <======\n'.format(epoch, trainer.global_step, lr) + info
-            if rank == 0:
-                print(info)
-                log.info(info)
-                if mAP > best_mAP:
-                    best_mAP = mAP
-                    os.makedirs(args.save_dir, exist_ok=True)
-                    stem = os.path.join(args.save_dir, 'best_model_Epoch_{}_step_{}_mAP_{:.4f}_loss_{:.4f}_lr_{:.7g}'
-                                        .format(epoch, int(trainer.global_step), best_mAP, vloss[0], lr))
-                    save_weights(variables, stem + '.weights')
-                    if args.save_optimizer:
-                        Saver(variables).save(stem, optimizer=optimizer, global_step=trainer.global_step)
+            with trainer.averaged():        # validation and both best_model_* files see the averaged weights
+                mAP, rec, prec, vloss, info = validate(yolo_model, y3, args, val_lines)
+                history['mAP'].append(mAP)
+                info = '======> Epoch: {}, global_step: {}, lr: {:.6g} <======\n'.format(epoch, trainer.global_step, lr) + info
+                if rank == 0:
+                    print(info)
+                    log.info(info)
+                    if mAP > best_mAP:
+                        best_mAP = mAP
+                        os.makedirs(args.save_dir, exist_ok=True)
+                        stem = os.path.join(args.save_dir, 'best_model_Epoch_{}_step_{}_mAP_{:.4f}_loss_{:.4f}_lr_{:.7g}'
+                                            .format(epoch, int(trainer.global_step), best_mAP, vloss[0], lr))
+                        save_weights(variables, stem + '.weights')
+                        if args.save_optimizer:     # (the .npz keeps the raw weights under the variables' names and adds the averages)
+                            Saver(variables).save(stem, optimizer=optimizer, global_step=trainer.global_step,
+                                                  averages=trainer if args.ema_decay else None)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -215,6 +215,10 @@ PROTOTYPES = {
     "y3_clip_update_multi_scratch_bytes": (c_size_t, [c_void_p, c_int]),
     "y3_clip_update_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float,
                                      c_float, c_float, c_void_p, c_size_t]),
+    "y3_clip_update_multi_ema_scratch_bytes": (c_size_t, [c_void_p, c_int]),
+    "y3_clip_update_multi_ema": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float,
+                                         c_float, c_float, c_void_p, c_float, c_void_p, c_size_t]),
+    "y3_ema_update": (c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_float]),
     "y3_net_set_profiling": (c_int, [c_void_p, c_int]),
     "y3_net_get_layer_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
     "y3_net_layer_is_streamk": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),

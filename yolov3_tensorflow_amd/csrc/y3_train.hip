@@ -816,6 +816,38 @@ __global__ void __launch_bounds__(256) mt_update_kernel(const MtDesc* __restrict
     }
 }
 
+// ---- moving average of the weights (include/yolo355.h, "Weight moving average") --------------------------------------
+// shadow <- shadow - ema_step * (shadow - w_new).  ONE expression for the fused and the stand-alone kernel: the explicit fma
+// fixes the rounding (two: the difference and the fused multiply-subtract) whatever the compiler contracts around it.
+__device__ __forceinline__ float ema_one(float s, float w_new, float ema_step) { return fmaf(-ema_step, s - w_new, s); }
+
+// mt_update_kernel with the shadow update behind it: w, g and the slots get the statements of that kernel, in its order; the
+// shadow of tensor t (ema[t]; NULL: none) is read and written once from the wi about to be stored.
+__global__ void __launch_bounds__(256) mt_update_ema_kernel(const MtDesc* __restrict__ descs, float* const* __restrict__ ema,
+                                                            int count, const float* __restrict__ norm, float clip, int kind,
+                                                            float lr, float momentum, float decay, float beta2, float eps,
+                                                            float ema_step) {
+    const int t = mt_find(descs, count, blockIdx.x);
+    const MtDesc d = descs[t];
+    float* const e = ema[t];
+    const float factor = clip / fmaxf(norm[t], clip);
+    const long long base = (long long)(blockIdx.x - d.chunk_begin) * MT_CHUNK;
+    const long long end = base + MT_CHUNK < d.n ? base + MT_CHUNK : d.n;
+    for (long long i = base + threadIdx.x; i < end; i += 256) {
+        float gi = d.g[i] * factor, wi = d.w[i];
+        mt_update_one(kind, wi, gi, d.s0, d.s1, i, lr, momentum, decay, beta2, eps);
+        d.g[i] = gi;                                  // the clipped gradient stays observable
+        d.w[i] = wi;
+        if (e) e[i] = ema_one(e[i], wi, ema_step);
+    }
+}
+
+__global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ shadow, const float* __restrict__ w,
+                                                         float ema_step, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        shadow[i] = ema_one(shadow[i], w[i], ema_step);
+}
+
 // sum over rows of an [M][C] matrix with arbitrary C (bias gradient of the detection convs, C = 3*(5+classes))
 __global__ void __launch_bounds__(256) col_sum_scalar_kernel(const float* __restrict__ x, long long M, int C,
                                                              float* __restrict__ partial /*[grid][C]*/) {
@@ -1237,41 +1269,65 @@ extern "C" size_t y3_clip_update_multi_scratch_bytes(const y3_param_desc* params
            (size_t)count * 4 + 256;
 }
 
-extern "C" int y3_clip_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* params, int count, float grad_scale,
-                                    float clip_norm, float lr, float momentum, float decay, float beta2, float eps,
-                                    void* scratch, size_t scratch_bytes) {
-    Y3_CHECK_ARG(ctx && params && scratch, "y3_clip_update_multi: null argument");
-    Y3_CHECK_ARG(count > 0 && count <= 65536, "y3_clip_update_multi: bad tensor count %d", count);
-    Y3_CHECK_ARG(kind >= 0 && kind <= 3, "y3_clip_update_multi: unknown optimizer kind %d", kind);
-    Y3_CHECK_ARG(scratch_bytes >= y3_clip_update_multi_scratch_bytes(params, count) && ((uintptr_t)scratch & 15) == 0,
-                 "y3_clip_update_multi: scratch too small or misaligned");
+// One host path for y3_clip_update_multi (ema == nullptr: its three launches, scratch layout and upload as they always were)
+// and y3_clip_update_multi_ema (the shadow pointers ride in the same pinned staging buffer, behind the descriptors).
+static size_t mt_ema_offset(const y3_param_desc* params, int count) {
+    return (y3_clip_update_multi_scratch_bytes(params, count) + 255) & ~(size_t)255;
+}
+
+static bool mt_overlap(const float* a, const float* b, long long n) {      // [a, a + n) meets [b, b + n)
+    return a && b && (uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n);
+}
+
+static int clip_update_multi_impl(const char* who, y3_ctx* ctx, int kind, const y3_param_desc* params, int count,
+                                  float grad_scale, float clip_norm, float lr, float momentum, float decay, float beta2,
+                                  float eps, float* const* ema, float ema_step, void* scratch, size_t scratch_bytes) {
+    Y3_CHECK_ARG(ctx && params && scratch, "%s: null argument", who);
+    Y3_CHECK_ARG(count > 0 && count <= 65536, "%s: bad tensor count %d", who, count);
+    Y3_CHECK_ARG(kind >= 0 && kind <= 3, "%s: unknown optimizer kind %d", who, kind);
+    const size_t need = ema ? y3_clip_update_multi_ema_scratch_bytes(params, count)
+                            : y3_clip_update_multi_scratch_bytes(params, count);
+    Y3_CHECK_ARG(scratch_bytes >= need && ((uintptr_t)scratch & 15) == 0, "%s: scratch too small or misaligned", who);
+    for (int i = 0; ema && i < count; ++i) {      // the shadows' contract, before anything is touched
+        const y3_param_desc& q = params[i];
+        float* const e = ema[i];
+        if (!e || q.n <= 0) continue;
+        Y3_CHECK_ARG(((uintptr_t)e & ((q.n & 3) ? 3 : 15)) == 0, "%s: tensor %d: the shadow is misaligned", who, i);
+        Y3_CHECK_ARG(!mt_overlap(e, q.w, q.n) && !mt_overlap(e, q.g, q.n) && !mt_overlap(e, q.slot0, q.n) &&
+                     !mt_overlap(e, q.slot1, q.n), "%s: tensor %d: the shadow overlaps w, g or a slot", who, i);
+    }
     // host staging of the device descriptors: the context's pinned buffer, handed out only once the previous upload
     // out of it has completed (an event behind that copy), so the asynchronous copy below can never race with this
     // or a later call's rewrite of the buffer
+    const size_t desc_bytes = (size_t)count * sizeof(MtDesc), ema_bytes = ema ? (size_t)count * sizeof(float*) : 0;
     void* stage = nullptr;
     {
-        const int rc = y3_ctx_stage_acquire(ctx, (size_t)count * sizeof(MtDesc), &stage);
+        const int rc = y3_ctx_stage_acquire(ctx, desc_bytes + ema_bytes, &stage);
         if (rc != Y3_OK) return rc;
     }
     MtDesc* host = static_cast<MtDesc*>(stage);
+    float** host_ema = reinterpret_cast<float**>(static_cast<char*>(stage) + desc_bytes);
     long long chunks = 0;
     for (int i = 0; i < count; ++i) {
         const y3_param_desc& q = params[i];
-        Y3_CHECK_ARG(q.w && q.g && q.n > 0, "y3_clip_update_multi: tensor %d has a null pointer or no elements", i);
-        Y3_CHECK_ARG(kind == 0 || q.slot0, "y3_clip_update_multi: tensor %d: optimizer slot missing", i);
-        Y3_CHECK_ARG(kind < 2 || q.slot1, "y3_clip_update_multi: tensor %d: second optimizer slot missing", i);
+        Y3_CHECK_ARG(q.w && q.g && q.n > 0, "%s: tensor %d has a null pointer or no elements", who, i);
+        Y3_CHECK_ARG(kind == 0 || q.slot0, "%s: tensor %d: optimizer slot missing", who, i);
+        Y3_CHECK_ARG(kind < 2 || q.slot1, "%s: tensor %d: second optimizer slot missing", who, i);
         Y3_CHECK_ARG((((uintptr_t)q.w | (uintptr_t)q.g) & 15) == 0 || (q.n & 3) != 0,
-                     "y3_clip_update_multi: tensor %d: w and g must be 16-byte aligned", i);
+                     "%s: tensor %d: w and g must be 16-byte aligned", who, i);
+        if (ema) host_ema[i] = ema_step != 0.f ? ema[i] : nullptr;     // a step of 0 keeps every shadow's bits: nothing to write
         host[i] = MtDesc{q.w, q.g, q.slot0, q.slot1, q.n, q.weight_decay, (int)chunks};
         chunks += mt_chunks(q.n);
-        Y3_CHECK_ARG(chunks < (1LL << 30), "y3_clip_update_multi: too many elements");
+        Y3_CHECK_ARG(chunks < (1LL << 30), "%s: too many elements", who);
     }
     char* base = static_cast<char*>(scratch);
     MtDesc* descs = reinterpret_cast<MtDesc*>(base);
-    float* partial = reinterpret_cast<float*>(base + (((size_t)count * sizeof(MtDesc) + 255) & ~(size_t)255));
+    float* partial = reinterpret_cast<float*>(base + ((desc_bytes + 255) & ~(size_t)255));
     float* norm = reinterpret_cast<float*>(reinterpret_cast<char*>(partial) + (((size_t)chunks * 4 + 255) & ~(size_t)255));
+    float** dev_ema = ema ? reinterpret_cast<float**>(base + mt_ema_offset(params, count)) : nullptr;
     hipStream_t st = ctx->stream;
-    Y3_CHECK_HIP(hipMemcpyAsync(descs, host, (size_t)count * sizeof(MtDesc), hipMemcpyHostToDevice, st));
+    Y3_CHECK_HIP(hipMemcpyAsync(descs, host, desc_bytes, hipMemcpyHostToDevice, st));
+    if (ema) Y3_CHECK_HIP(hipMemcpyAsync(dev_ema, host_ema, ema_bytes, hipMemcpyHostToDevice, st));
     {
         const int rc = y3_ctx_stage_release(ctx);
         if (rc != Y3_OK) return rc;
@@ -1280,8 +1336,47 @@ extern "C" int y3_clip_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* 
     Y3_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(mt_norms_kernel, dim3(count), dim3(256), 0, st, descs, count, (int)chunks, partial, norm);
     Y3_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mt_update_kernel, dim3((unsigned)chunks), dim3(256), 0, st, descs, count, norm, clip_norm, kind,
-                       lr, momentum, decay, beta2, eps);
+    if (ema)
+        hipLaunchKernelGGL(mt_update_ema_kernel, dim3((unsigned)chunks), dim3(256), 0, st, descs, dev_ema, count, norm,
+                           clip_norm, kind, lr, momentum, decay, beta2, eps, ema_step);
+    else
+        hipLaunchKernelGGL(mt_update_kernel, dim3((unsigned)chunks), dim3(256), 0, st, descs, count, norm, clip_norm, kind,
+                           lr, momentum, decay, beta2, eps);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
+}
+
+extern "C" int y3_clip_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* params, int count, float grad_scale,
+                                    float clip_norm, float lr, float momentum, float decay, float beta2, float eps,
+                                    void* scratch, size_t scratch_bytes) {
+    return clip_update_multi_impl("y3_clip_update_multi", ctx, kind, params, count, grad_scale, clip_norm, lr, momentum, decay,
+                                  beta2, eps, nullptr, 0.f, scratch, scratch_bytes);
+}
+
+// [the plain call's scratch, rounded up to 256][shadow pointer per tensor]
+extern "C" size_t y3_clip_update_multi_ema_scratch_bytes(const y3_param_desc* params, int count) {
+    if (!params || count <= 0) return 0;
+    return mt_ema_offset(params, count) + (size_t)count * sizeof(float*);
+}
+
+static bool ema_step_ok(float s) { return s >= 0.f && s <= 1.f; }      // (false for NaN)
+
+extern "C" int y3_clip_update_multi_ema(y3_ctx* ctx, int kind, const y3_param_desc* params, int count, float grad_scale,
+                                        float clip_norm, float lr, float momentum, float decay, float beta2, float eps,
+                                        float* const* ema, float ema_step, void* scratch, size_t scratch_bytes) {
+    Y3_CHECK_ARG(ema, "y3_clip_update_multi_ema: null shadow array");
+    Y3_CHECK_ARG(ema_step_ok(ema_step), "y3_clip_update_multi_ema: ema_step %g is not in [0, 1]", (double)ema_step);
+    return clip_update_multi_impl("y3_clip_update_multi_ema", ctx, kind, params, count, grad_scale, clip_norm, lr, momentum,
+                                  decay, beta2, eps, ema, ema_step, scratch, scratch_bytes);
+}
+
+extern "C" int y3_ema_update(y3_ctx* ctx, float* shadow, const float* w, long long n, float ema_step) {
+    Y3_CHECK_ARG(ctx && shadow && w, "y3_ema_update: null argument");
+    Y3_CHECK_ARG(n > 0, "y3_ema_update: empty tensor");
+    Y3_CHECK_ARG(ema_step_ok(ema_step), "y3_ema_update: ema_step %g is not in [0, 1]", (double)ema_step);
+    Y3_CHECK_ARG(!mt_overlap(shadow, w, n), "y3_ema_update: the shadow overlaps w");
+    if (ema_step == 0.f) return Y3_OK;       // every shadow keeps its bits
+    hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, shadow, w, ema_step, n);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }

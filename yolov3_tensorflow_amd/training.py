@@ -386,11 +386,26 @@ class Trainer(object):
     per-tensor clip_by_norm(100), optimizer.apply_gradients; with torch.distributed initialised, gradients
     are summed over ranks — RCCL all-reduce of the flat gradient buffer in buckets, issued in the order backward
     produces them and overlapped with the rest of backward (distributed.GradientExchange) — and averaged (the 1/world
-    factor is folded into the clip/update kernel) before clipping."""
+    factor is folded into the clip/update kernel) before clipping.
+
+    ema_decay in (0, 1) keeps a moving average of every updated variable (include/yolo355.h, "Weight moving average":
+    tf.train.ExponentialMovingAverage(ema_decay, num_updates=global_step) with zero_debias=False; ema_warmup=False drops
+    the num_updates ramp).  The update kernel writes the averages (y3_clip_update_multi_ema: no launch is added);
+    `averaged()` puts them into the variables for validation and saving.  None or 0: off, and the step is the one without
+    the argument, launch for launch.  Data-parallel ranks exchange nothing for it: every rank applies the same update to
+    the same weights, so identical weights give identical averages."""
 
     def __init__(self, model, optimizer, update_vars=None, clip_norm=CLIP_NORM, process_group=None,
-                 global_step=0.0, bucket_bytes=distributed.DEFAULT_BUCKET_BYTES, wgrad_stream='auto', sync_bn=False):
+                 global_step=0.0, bucket_bytes=distributed.DEFAULT_BUCKET_BYTES, wgrad_stream='auto', sync_bn=False,
+                 ema_decay=None, ema_warmup=True):
         self.model, self.opt = model, optimizer
+        self.ema_decay = float(ema_decay) if ema_decay else None
+        if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:
+            raise ValueError('ema_decay must lie in (0, 1), or be None / 0 for no averaging (got %r)' % (ema_decay,))
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None          # {op_name: the average of that variable} once the shadows exist (see _alloc_ema)
+        self._ema_pending = {}   # averages a checkpoint handed over before the shadows existed
+        self._averaged = False   # inside averaged(): the variables hold the averages, self.ema the raw values
         # Synchronised batch norm (distributed.BnSync; off by default): every BN layer normalises with the statistics of the
         # GLOBAL batch and every rank keeps the same moving statistics, so an N-rank step is the single-GPU step at N times
         # the batch (given equal local batch sizes).  Costs two small collectives per BN layer and step.  True, or a BnSync
@@ -435,6 +450,85 @@ class Trainer(object):
         self.layer_ends = ends
         self.exchange = distributed.GradientExchange(self.flat, sorted(ends.values()) or [total], self.pg,
                                                      self.bucket_bytes)
+        self._alloc_ema()
+
+    # ---- moving average of the weights ---------------------------------------------------------------------------------
+    def ema_step_at(self, global_step):
+        """1 - d_t of the step taken at `global_step` (its value before the step increments it), in double:
+        d_t = min(ema_decay, (1 + t) / (10 + t)) with warm-up, else ema_decay.  Pure host arithmetic."""
+        if self.ema_decay is None:
+            raise RuntimeError('this Trainer keeps no moving average (ema_decay is off)')
+        t = float(global_step)
+        d = min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+        return 1.0 - d
+
+    def _alloc_ema(self):
+        """The shadows of self.order: each starts as a copy of its variable, or with the value a checkpoint handed over."""
+        if self.ema_decay is None or self.ema is not None:
+            return
+        self.ema = {}
+        for v in self.order:
+            s = v.tensor.detach().clone()
+            stored = self._ema_pending.pop(v.op_name, None)
+            if stored is not None and tuple(stored.shape) == tuple(s.shape):
+                s.copy_(torch.as_tensor(np.ascontiguousarray(stored, dtype=np.float32)))
+            self.ema[v.op_name] = s
+        self._ema_pending = {}
+
+    def ema_assign(self, op_name, value):
+        """Set the average of one variable (Saver.restore).  Before the shadows exist the value is kept and becomes the
+        shadow's start value; a name the step does not update, or another shape, is ignored."""
+        if self.ema_decay is None:
+            return
+        if self.ema is None:
+            self._ema_pending[op_name] = np.array(value, dtype=np.float32)
+            return
+        t = self.ema_tensors().get(op_name)
+        if t is not None and tuple(t.shape) == tuple(np.shape(value)):
+            t.copy_(torch.as_tensor(np.ascontiguousarray(value, dtype=np.float32)))
+
+    def ema_tensors(self):
+        """{op_name: tensor holding that variable's AVERAGE}, inside and outside averaged() ({} while there are none)."""
+        if self.ema is None:
+            return {}
+        return {v.op_name: v.tensor for v in self.order} if self._averaged else dict(self.ema)
+
+    def raw_tensors(self):
+        """{op_name: tensor holding the raw iterate} of the averaged variables."""
+        if self.ema is None:
+            return {}
+        return dict(self.ema) if self._averaged else {v.op_name: v.tensor for v in self.order}
+
+    def averaged(self):
+        """Context manager: inside it every updated variable holds its average (validation, best-model files); on exit the
+        raw values are back, bit for bit.  The tensors are swapped, not copied, and every variable is touch()ed so the
+        packed-weight caches follow.  step(), backward() and apply_gradients() raise inside it.  Without averaging (or
+        before the first step created the shadows) the context changes nothing."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            if self._averaged:
+                raise RuntimeError('averaged() is already active')
+            swap = self.ema is not None
+            if swap:
+                self._swap_ema()
+            try:
+                yield self
+            finally:
+                if swap:
+                    self._swap_ema()
+        return ctx()
+
+    def _swap_ema(self):
+        for v in self.order:
+            v.tensor, self.ema[v.op_name] = self.ema[v.op_name], v.tensor
+            v.touch()
+        self._averaged = not self._averaged
+
+    def _no_update_while_averaged(self, what):
+        if self._averaged:
+            raise RuntimeError('%s inside Trainer.averaged(): the variables hold their averages' % what)
 
     def _vars(self, layer_vars, dev):
         self._alloc_grads(layer_vars, dev)
@@ -472,6 +566,7 @@ class Trainer(object):
     def backward(self):
         """train.py:112 compute_gradients: ONE library call (y3_net_train_backward) walks the graph backwards and writes every
         trainable variable's gradient into the flat buffer; the `ready` hook issues the gradient buckets as they complete."""
+        self._no_update_while_averaged('backward()')
         st = _train_state(self.model)
         if not st.get('have_loss') or st.get('fms') is None:
             raise RuntimeError('backward needs forward(is_training=True) and compute_loss first')
@@ -487,6 +582,8 @@ class Trainer(object):
         """Host array of y3_param_desc for self.order (rebuilt when a variable's storage or a slot changed)."""
         sig = tuple((v.tensor.data_ptr(),) + tuple(0 if s is None else s.data_ptr() for s in self.opt._slots_for(v))
                     for v in self.order)
+        if self.ema is not None:
+            sig += tuple(self.ema[v.op_name].data_ptr() for v in self.order)
         if getattr(self, '_descs_sig', None) != sig:
             arr = (_lib.ParamDesc * len(self.order))()
             keep = []
@@ -498,13 +595,17 @@ class Trainer(object):
                                         0 if s1 is None else s1.data_ptr(), v.tensor.numel(), wd, 0)
                 keep.append((v.tensor, s0, s1))
             self._descs, self._descs_keep, self._descs_sig = arr, keep, sig
+            if self.ema is not None:        # the HOST array of shadow pointers of y3_clip_update_multi_ema, in self.order
+                self._ema_arr = (ctypes.c_void_p * len(self.order))(*[self.ema[v.op_name].data_ptr() for v in self.order])
         return self._descs, self._descs_keep
 
     def apply_gradients(self):
         """all-reduce (mean over ranks) -> + weight_decay*w on conv kernels -> clip_by_norm -> update."""
+        self._no_update_while_averaged('apply_gradients()')
         L = _lib.lib()
         dev = self.flat.device
         ctx = fw.context(dev)
+        ema_step = None if self.ema is None else ctypes.c_float(self.ema_step_at(self.global_step))
         self.exchange.finish()      # buckets not yet issued by backward + join the asynchronous ones
         world = self.exchange.world
         self.opt.step += 1
@@ -525,18 +626,24 @@ class Trainer(object):
                                             ctypes.c_float(self.clip_norm), ctypes.c_float(lr),
                                             ctypes.c_float(self.opt.momentum), ctypes.c_float(decay),
                                             ctypes.c_float(self.opt.beta2), ctypes.c_float(self.opt.epsilon), fw.ptr(sc)))
+                if ema_step is not None:
+                    _lib.check(L.y3_ema_update(ctx, fw.ptr(self.ema[v.op_name]), fw.ptr(v.tensor), v.tensor.numel(), ema_step))
                 v.touch()
             self.global_step += 1.0
             return
         # ONE multi-tensor call (three launches) for every (gradient, variable) pair of train.py:112-115
         descs, keep = self._param_descs()
-        nbytes = L.y3_clip_update_multi_scratch_bytes(descs, len(self.order))
-        sc = _scratch(st, 'opt_multi', nbytes, dev)
-        _lib.check(L.y3_clip_update_multi(ctx, kind, descs, len(self.order), ctypes.c_float(1.0 / world),
-                                          ctypes.c_float(self.clip_norm), ctypes.c_float(lr),
-                                          ctypes.c_float(self.opt.momentum), ctypes.c_float(decay),
-                                          ctypes.c_float(self.opt.beta2), ctypes.c_float(self.opt.epsilon),
-                                          fw.ptr(sc), ctypes.c_size_t(sc.numel())))
+        hp = (ctypes.c_float(1.0 / world), ctypes.c_float(self.clip_norm), ctypes.c_float(lr), ctypes.c_float(self.opt.momentum),
+              ctypes.c_float(decay), ctypes.c_float(self.opt.beta2), ctypes.c_float(self.opt.epsilon))
+        if ema_step is None:
+            nbytes = L.y3_clip_update_multi_scratch_bytes(descs, len(self.order))
+            sc = _scratch(st, 'opt_multi', nbytes, dev)
+            _lib.check(L.y3_clip_update_multi(ctx, kind, descs, len(self.order), *(hp + (fw.ptr(sc), ctypes.c_size_t(sc.numel())))))
+        else:       # the same three launches; the third also moves every shadow towards the w it stores
+            nbytes = L.y3_clip_update_multi_ema_scratch_bytes(descs, len(self.order))
+            sc = _scratch(st, 'opt_multi', nbytes, dev)
+            _lib.check(L.y3_clip_update_multi_ema(ctx, kind, descs, len(self.order),
+                                                  *(hp + (self._ema_arr, ema_step, fw.ptr(sc), ctypes.c_size_t(sc.numel())))))
         for v in self.order:
             v.touch()
         self.global_step += 1.0
@@ -545,6 +652,7 @@ class Trainer(object):
         """One training step on a batch; returns [total, xy, wh, conf, class] (device scalars):
         forward(is_training=True) -> compute_loss -> backward in ONE library call (y3_net_train_step), then the
         all-reduce join, L2, clip and update (y3_clip_update_multi)."""
+        self._no_update_while_averaged('step()')
         x = fw.as_device_f32(images)
         self.model.img_size = [int(x.shape[1]), int(x.shape[2])]
         timing = None

@@ -214,6 +214,13 @@ def get_variables_to_restore(variables, include=None, exclude=None):
 # slot names TF1 gives the optimizer variables (utils/misc_utils.py:151-161 optimizers)
 _SLOT_NAMES = {'momentum': ('Momentum',), 'adam': ('Adam', 'Adam_1'), 'rmsprop': ('RMSProp', 'RMSProp_1'),
                'sgd': ()}
+# the name TF1 gives a variable's moving average (tf.train.ExponentialMovingAverage.average_name)
+EMA_SUFFIX = '/ExponentialMovingAverage'
+
+
+def has_averages(save_path):
+    """True when the native checkpoint at save_path stores weight moving averages."""
+    return any(k.endswith(EMA_SUFFIX) for k in np.load(Saver._path(save_path)).files)
 
 
 class Saver(object):
@@ -229,8 +236,19 @@ class Saver(object):
     def _path(path):
         return path if path.endswith('.npz') else path + '.npz'
 
-    def save(self, save_path, optimizer=None, global_step=None):
+    def save(self, save_path, optimizer=None, global_step=None, averages=None):
+        """averages: a training.Trainer that keeps a weight moving average.  Every average is stored as
+        '<variable>/ExponentialMovingAverage' (TF1's shadow name).  The variable's own key always holds the RAW iterate, also
+        when the call is made inside trainer.averaged(), so a run resumed from the file continues both."""
         out = {v.op_name: v.numpy() for v in self.var_list}
+        if averages is not None:
+            names = set(out)
+            for name, t in averages.raw_tensors().items():
+                if name in names:
+                    out[name] = t.detach().cpu().numpy()
+            for name, t in averages.ema_tensors().items():
+                if name in names:
+                    out[name + EMA_SUFFIX] = t.detach().cpu().numpy()
         if optimizer is not None:
             for name, slots in optimizer.slots.items():
                 for slot_name, t in zip(_SLOT_NAMES[optimizer.kind], slots):
@@ -244,17 +262,29 @@ class Saver(object):
             np.savez(f, **out)
         return path
 
-    def restore(self, save_path, optimizer=None, variables=True):
+    def restore(self, save_path, optimizer=None, variables=True, averages=None, use_ema=False):
         """Returns the stored global_step (or None).  variables=False leaves the variables alone and loads only the
         optimizer slots (of the variables in var_list whose stored slots match the variable's shape) and its step —
-        what resuming needs AFTER a filtered variable restore (train.py: restore_exclude must stay excluded)."""
+        what resuming needs AFTER a filtered variable restore (train.py: restore_exclude must stay excluded).
+        averages: a training.Trainer that keeps a weight moving average; the stored averages of the variables in var_list
+        that are present and match in shape become its shadows, the others keep their start value.
+        use_ema=True assigns the stored AVERAGE to the variable itself where the file holds one of the variable's shape
+        (TF's variables_to_restore() idiom for evaluation); a variable without one takes its own key."""
         import torch
         ckpt = np.load(self._path(save_path))
         if variables:
             for v in self.var_list:
                 if v.op_name not in ckpt.files:
                     raise KeyError('Key %s not found in checkpoint %s' % (v.op_name, save_path))
-                v.assign(ckpt[v.op_name], validate_shape=True)
+                key = v.op_name
+                if use_ema and key + EMA_SUFFIX in ckpt.files and tuple(ckpt[key + EMA_SUFFIX].shape) == tuple(v.shape):
+                    key += EMA_SUFFIX
+                v.assign(ckpt[key], validate_shape=True)
+        if averages is not None:
+            for v in self.var_list:
+                key = v.op_name + EMA_SUFFIX
+                if key in ckpt.files and tuple(ckpt[key].shape) == tuple(v.shape):
+                    averages.ema_assign(v.op_name, ckpt[key])
         if optimizer is not None:
             for v in self.var_list:
                 keys = [v.op_name + '/' + s for s in _SLOT_NAMES[optimizer.kind]]
@@ -264,6 +294,16 @@ class Saver(object):
             if 'optimizer/step' in ckpt.files:
                 optimizer.step = int(ckpt['optimizer/step'])
         return float(ckpt['global_step']) if 'global_step' in ckpt.files else None
+
+
+def restore_for_inference(variables, save_path, use_ema=False):
+    """What an inference script (eval.py --use_ema) does with a native .npz: Saver.restore, with the stored weight moving
+    averages in place of the raw weights when use_ema is set.  A file without averages is said so, and read as it is."""
+    if use_ema and not has_averages(save_path):
+        print('--use_ema true: %s holds no weight moving averages (it was not written by a run with --ema_decay); '
+              'using the raw weights' % save_path)
+        use_ema = False
+    return Saver(variables).restore(save_path, use_ema=use_ema)
 
 
 def config_learning_rate(args, global_step):
