@@ -8,7 +8,9 @@ LDS), so the file holds two tables: 'host' (made without a device) and 'device' 
 
 Per (dtype, n, h, w) it records, per layer, y3_net_layer_fused, y3_net_layer_is_streamk and
 y3_conv_bf16_tile of the layer's descriptor; y3_net_workspace_bytes; and, for the train dtypes (0, 2, 3, 4),
-y3_net_train_workspace_bytes with every variable trainable, the weight-gradient stream off and on.
+y3_net_train_workspace_bytes with every variable trainable, the weight-gradient stream off and on.  For every dtype at the
+SEL_SHAPES, 'train_workspace_sel' holds the same pair for the all-trainable table and for every partial update_vars of
+tests/test_train_gpu.py (SELECTIONS): the allocation sequence of backward changes with the selection.
 tests/test_conv_route_cpu.py holds the library against the file.  Y3_LIB_PATH selects the library it is made from.
 """
 import ctypes
@@ -18,11 +20,13 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(1, os.path.dirname(HERE))      # (tests/: SELECTIONS of test_train_gpu.py)
 
 OUT = os.path.join(HERE, 'conv_routes.json')
 SHAPES = ((32, 416, 416), (16, 608, 608), (64, 416, 416), (4, 256, 256), (3, 320, 320), (2, 416, 608), (1, 96, 96),
           (8, 416, 416))
 TRAIN_DTYPES = (0, 2, 3, 4)
+SEL_SHAPES = ((1, 96, 96), (4, 256, 256), (3, 320, 320), (2, 416, 608), (8, 416, 416))
 CLASS_NUM = 80
 
 
@@ -46,6 +50,31 @@ def layer_vars():
                                  for s in ('gamma', 'beta', 'moving_mean', 'moving_variance')), None))
         else:
             out.append((w, None, _Var('conv%d/biases' % i, (l['cout'],))))
+    return out
+
+
+def selection_tables():
+    """{name: y3_train_var table} of every partial update_vars of tests/test_train_gpu.py, built as
+    tests/test_train_workspace_cpu.py builds them (the variables under the names those prefixes select)"""
+    import torch
+    from yolov3_tensorflow_amd import training
+    from test_train_gpu import SELECTIONS, _conv_name
+    lvs = []
+    for i, l in enumerate(training._Topology(CLASS_NUM).layers):
+        base = _conv_name(i)
+        w = _Var(base + '/weights', (l['k'], l['k'], l['cin'], l['cout']))
+        if l['bn']:
+            lvs.append((w, tuple(_Var(base + '/BatchNorm/' + s, (l['cout'],), trainable=s in ('gamma', 'beta'))
+                                 for s in ('gamma', 'beta', 'moving_mean', 'moving_variance')), None))
+        else:
+            lvs.append((w, None, _Var(base + '/biases', (l['cout'],))))
+    out = {}
+    for name, prefixes in sorted(SELECTIONS.items()):
+        picked = [v for lv in lvs for v in (lv[0],) + tuple(lv[1] or ()) + ((lv[2],) if lv[2] else ())
+                  if any(v.op_name.startswith(p) for p in prefixes)]
+        trainer = training.Trainer(None, None, update_vars=picked)
+        trainer._alloc_grads(lvs, torch.device('cpu'))
+        out[name] = training._var_table(lvs, trainer.offsets, trainer.layer_ends)
     return out
 
 
@@ -75,6 +104,7 @@ def table():
     h = ctypes.c_void_p()
     _lib.check(L.y3_net_create(None, CLASS_NUM, ctypes.byref(h)))
     all_table, _ = training._var_table(layer_vars())
+    sel = dict(selection_tables(), all=(all_table, None))
     nl = L.y3_net_num_layers(h)
     dummy = ctypes.c_void_p(0x1000)      # a weight-gradient stream: the dry run only asks whether there is one
     out = {}
@@ -96,6 +126,15 @@ def table():
                         ws.append(L.y3_net_train_workspace_bytes(h, all_table, n, H, W))
                     _lib.check(L.y3_net_train_set_wgrad_stream(h, None))
                     e['train_workspace'] = ws
+                if (n, H, W) in SEL_SHAPES:
+                    e['train_workspace_sel'] = {}
+                    for name in sorted(sel):
+                        ws = []
+                        for side in (None, dummy):
+                            _lib.check(L.y3_net_train_set_wgrad_stream(h, side))
+                            ws.append(L.y3_net_train_workspace_bytes(h, sel[name][0], n, H, W))
+                        e['train_workspace_sel'][name] = ws
+                    _lib.check(L.y3_net_train_set_wgrad_stream(h, None))
                 # (dtype 4 keeps the '+alt' of the tables made while its F(4x4,3x3) packings were optional: the net now has them)
                 out['dtype%d%s/%dx%dx%d' % (dtype, '+alt' if dtype == 4 else '', n, H, W)] = e
     finally:

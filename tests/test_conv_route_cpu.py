@@ -2,7 +2,10 @@
 against tests/golden/conv_routes.json, recorded from the library before the route of each layer was decided in one place
 (csrc/y3_abi.hip y3_route_*).  Host-only ABI calls on a net created without a context (tests/golden/make_route_golden.py).
 One column was re-recorded since: 'streamk' (y3_net_layer_is_streamk).  y3_conv_schedule_impl used to read uninitialised
-fields and answered 0 for every layer; it now gives the schedule y3_launch_conv picks.
+fields and answered 0 for every layer; it now gives the schedule y3_launch_conv picks.  One column was added:
+'train_workspace_sel', the train step's workspace for every dtype (bf16 included), the all-trainable table and every partial
+update_vars of tests/test_train_gpu.py, stream off and on - recorded from the library before the train step's host code
+(csrc/y3_net_train.hip) was split into named steps, which must reproduce every number.
 
 Some entries depend on the device the library sees (the fused stem / residual block need the device to offer their kernels'
 LDS): the file holds one table made without a device and one made on an MI355X."""
@@ -35,7 +38,7 @@ def test_route_table_covers_every_net_dtype_and_shape(tables):
             assert '%s/%dx%dx%d' % (dt, n, h, w) in want
 
 
-@pytest.mark.parametrize('field', ['fused', 'streamk', 'bf16_tile', 'workspace', 'train_workspace'])
+@pytest.mark.parametrize('field', ['fused', 'streamk', 'bf16_tile', 'workspace', 'train_workspace', 'train_workspace_sel'])
 def test_route_table_matches_golden(tables, field):
     want, got = tables
     bad = [k for k in sorted(want) if want[k].get(field) != got[k].get(field)]

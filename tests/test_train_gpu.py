@@ -810,6 +810,39 @@ def test_every_ready_edge_follows_the_weight_gradients_it_covers(selection, isol
     assert not stale, 'ready edges %s issued before these gradients were joined: %s' % (edges, stale)
 
 
+@pytest.mark.parametrize('wgrad_stream', [False, True])
+@pytest.mark.parametrize('dtype', ['f32_wino', 'bf16'])
+@pytest.mark.parametrize('h,w', [(64, 64), (32, 64)])
+def test_backward_run_twice_from_one_forward_writes_the_same_bits(h, w, dtype, wgrad_stream, isolated_graph):
+    """The saved tensors and the loss gradients stay with the forward so that backward may be re-run from them (the end of
+    forward_impl, csrc/y3_net_train.hip): backward writes neither, rewinds the arena to the forward's top and starts its
+    gradient table and its side stream afresh.  Two Trainer.backward() after ONE forward(is_training=True) and compute_loss
+    must fill the flat gradient buffer (NaN before each) with the same bits, every trainable element written.  Batch 2 at
+    the smallest square and non-square sizes of tests/test_train_sizes_gpu.py, whose targets these are."""
+    import yolov3_tensorflow_amd as y3
+    from yolov3_tensorflow_amd import training
+    from yolov3_tensorflow_amd.utils.misc_utils import config_optimizer
+    from test_train_sizes_gpu import CLASS_NUM, _params, _targets
+    model = _fresh_model(_params(), CLASS_NUM, batch_norm_decay=0.99)
+    model.compute_dtype = dtype
+    model.wgrad_stream = wgrad_stream               # the split API reads the model's setting
+    trainer = training.Trainer(model, config_optimizer('sgd', 1e-3), wgrad_stream=wgrad_stream)
+    x, yts = _blob_images_hw(21, 2, h, w), _targets(22, 2, h, w)
+    flats = []
+    with y3.variable_scope('yolov3'):
+        fms = model.forward(x, is_training=True)
+        training.compute_loss(model, fms, yts)
+        trainer._alloc_grads(model._train['layer_vars'], fms[0].device)
+        for _ in range(2):
+            trainer.flat.fill_(float('nan'))
+            trainer.backward()
+            torch.cuda.synchronize()
+            for name, view in trainer.views.items():
+                assert bool(torch.isfinite(view).all()), '%s: gradient not written' % name
+            flats.append(trainer.flat.clone())
+    assert torch.equal(flats[0].view(torch.int32), flats[1].view(torch.int32))      # (bits: the alignment gaps hold NaN)
+
+
 def test_train_workspace_follows_the_dtype_and_a_small_one_is_refused_before_launch(isolated_graph):
     """(a) the step's workspace is sized per (shape, device, compute_dtype) - the allocation sequence differs
     between 'f32', 'f32_wino' and 'f32_bf16x6' - so switching the mode on a live model must re-size it, and the steps

@@ -303,8 +303,7 @@ extern "C" int y3_conv2d_dgrad_wino44(y3_ctx* ctx, const y3_conv_desc* fwd, cons
     Y3_CHECK_ARG(fwd && dz && w_wino44_d && ones && zeros && dx, "y3_conv2d_dgrad_wino44: null pointer argument");
     Y3_CHECK_ARG(fwd->k == 3 && fwd->stride == 1 && fwd->c_up == 0 && dz_stride >= fwd->cout,
                  "y3_conv2d_dgrad_wino44: needs a 3x3 stride-1 conv and dz_stride >= Cout");
-    y3_conv_desc g = *fwd;
-    g.cin = dz_stride; g.cout = fwd->cin; g.act = 0;
+    const y3_conv_desc g = y3_dgrad_desc(fwd, dz_stride);
     Y3_CHECK_ARG(y3_conv_wino44_eligible_impl(&g), "y3_conv2d_dgrad_wino44: needs dz_stride %% 32 == 0 and Cin %% 64 == 0");
     y3_sk_opts o;
     o.err = ctx->err_host;
@@ -319,8 +318,7 @@ static int wino_dgrad_desc(const y3_conv_desc* fwd, int dz_stride, y3_conv_desc*
     Y3_CHECK_ARG(fwd && fwd->k == 3 && fwd->stride == 1 && fwd->c_up == 0, "y3_conv2d_dgrad_wino: needs a 3x3 stride-1 conv");
     Y3_CHECK_ARG(dz_stride >= fwd->cout && dz_stride % 32 == 0 && fwd->cin % 32 == 0,
                  "y3_conv2d_dgrad_wino: dz stride and Cin must be multiples of 32");
-    *g = *fwd;
-    g->cin = dz_stride; g->cout = fwd->cin; g->act = 0;
+    *g = y3_dgrad_desc(fwd, dz_stride);
     Y3_CHECK_ARG(y3_conv_wino_eligible_impl(g), "y3_conv2d_dgrad_wino: shape not eligible for the Winograd kernel");
     return Y3_OK;
 }
@@ -560,7 +558,10 @@ ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w) {
         return r;
     }
     const y3_conv_desc d = net.desc(i, n, h, w, true);
-    const y3_conv_desc g = {n, d.h, d.w, net.dz_stride(i), 0, l.cin, l.k, l.stride, 0};
+    y3_conv_desc g = y3_dgrad_desc(&d, net.dz_stride(i));
+    // (a stride-2 layer's route, and with it its scratch, has always been asked of the forward's geometry: the image ranges of
+    // that view cut no later than the launch's own, y3_launch_conv_dgrad)
+    if (l.stride == 2) { g.h = d.h; g.w = d.w; g.stride = 2; }
     const bool wino = net.dtype == NetDtype::F32_WINO && l.up < 0 && l.k == 3 && l.stride == 1 && y3_conv_wino_eligible_impl(&g);
     const int planes = (l.cin != 3 && l.stride == 1 && l.cin % 4 == 0 && g.cin % 32 == 0) ? split_planes(net.dtype) : 0;
     ConvRoute r = fp32_route(g, wino && y3_conv_wino44_preferred_impl(&g), wino, planes);

@@ -478,7 +478,7 @@ int y3_launch_conv_dgrad(hipStream_t stream, const y3_conv_desc* fwd, const floa
     Y3_CHECK_ARG(dz_stride >= fwd->cout && dz_stride % BK == 0, "y3_conv2d_dgrad: dz stride must be a multiple of %d", BK);
     Y3_CHECK_ARG(fwd->cin % 4 == 0, "y3_conv2d_dgrad: Cin must be a multiple of 4");
     Y3_CHECK_ARG(fwd->n > 0 && fwd->h > 0 && fwd->w > 0 && fwd->cin > 0 && fwd->cout > 0, "y3_conv2d_dgrad: non-positive dimension");
-    const y3_conv_desc g = dgrad_desc(fwd, dz_stride);
+    const y3_conv_desc g = y3_dgrad_desc(fwd, dz_stride);
     ConvArgs a = conv_args(&g, dz, nullptr, w_d, ones, zeros, accumulate ? dx : nullptr, dx);
     a.wrev = 1;
     if (fwd->stride == 2) { a.tmode = 1; a.Ho = fwd->h; a.Wo = fwd->w; }

@@ -33,15 +33,6 @@ inline int check_conv_desc(const y3_conv_desc* d, const void* x_up, const char* 
     return Y3_OK;      // (the element limit: the image ranges)
 }
 
-// The data gradient of forward layer `fwd` as the conv the kernels run: [n, ho, wo, dz_stride] -> fwd cin at
-// stride 1 with the flipped kernel (ConvArgs::wrev); a stride-2 layer: ConvArgs::tmode on the same view.
-inline y3_conv_desc dgrad_desc(const y3_conv_desc* fwd, int dz_stride) {
-    y3_conv_desc g = *fwd;
-    g.h = fwd->h / fwd->stride; g.w = fwd->w / fwd->stride;
-    g.cin = dz_stride; g.c_up = 0; g.cout = fwd->cin; g.stride = 1; g.act = 0;
-    return g;
-}
-
 // The argument block of conv `d` over the whole batch: value-initialised, then what the descriptor and the tensors say.  The
 // rows (N, M) are set per image range by walk_image_ranges; what a form adds (stats, bz / bvec, wrev, tmode) by its entry point.
 inline ConvArgs conv_args(const y3_conv_desc* d, const float* x, const float* x_up, const void* w, const float* scale,

@@ -392,7 +392,7 @@ int y3_launch_conv_dgrad_split(hipStream_t stream, const y3_conv_desc* fwd, int 
     Y3_CHECK_ARG(fwd->cin % 4 == 0 && fwd->n > 0 && fwd->h > 0 && fwd->w > 0,
                  "y3_conv2d_dgrad_split: Cin must be a multiple of 4");
     Y3_CHECK_ARG(fwd->cin > 0 && fwd->cout > 0, "y3_conv2d_dgrad_split: non-positive dimension");
-    const y3_conv_desc g = dgrad_desc(fwd, dz_stride);
+    const y3_conv_desc g = y3_dgrad_desc(fwd, dz_stride);
     ConvArgs a = conv_args(&g, dz, nullptr, w, ones, zeros, accumulate ? dx : nullptr, dx);
     a.wrev = 1;
     const int k = fwd->k;

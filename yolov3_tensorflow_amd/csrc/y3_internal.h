@@ -63,6 +63,16 @@ struct y3_image_ranges {
     }
 };
 
+// The data gradient of forward layer `fwd` as the conv the kernels run: [n, ho, wo, dz_stride] -> fwd cin at
+// stride 1 with the flipped kernel (ConvArgs::wrev); a stride-2 layer: ConvArgs::tmode on the same view.  The one place
+// that builds it: the launchers, the train step, the route and the C-ABI wrappers of the Winograd forms.
+inline y3_conv_desc y3_dgrad_desc(const y3_conv_desc* fwd, int dz_stride) {
+    y3_conv_desc g = *fwd;
+    g.h = fwd->h / fwd->stride; g.w = fwd->w / fwd->stride;
+    g.cin = dz_stride; g.c_up = 0; g.cout = fwd->cin; g.stride = 1; g.act = 0;
+    return g;
+}
+
 // Experiment switches (A/B runs of tools/ and tests/test_conv_variants_gpu.py) exist only in a -DY3_EXPERIMENTS build
 // (csrc/libyolo355_exp.so, `python -m yolov3_tensorflow_amd.build --experiments`): in the product library no environment
 // variable changes which kernel runs.

@@ -95,7 +95,7 @@ struct Arena {
         fl.swap(merged);
         b = Buf();
     }
-    float* p(const Buf& b) const { return b.ok() ? reinterpret_cast<float*>(base + b.off) : nullptr; }
+    float* p(const Buf& b) const { return b.ok() && base ? reinterpret_cast<float*>(base + b.off) : nullptr; }   // (dry: null)
 };
 
 struct Tensor {
