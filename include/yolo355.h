@@ -681,6 +681,35 @@ int y3_feed_run(y3_ctx* ctx, const void* blob_dev, size_t blob_bytes, const stru
                 const void* tables_dev, void* scratch_dev, size_t scratch_bytes, const void* src_dev, size_t src_bytes,
                 float* out, int out_h, int out_w);
 
+/* ---- mosaic: n training images composed on the device from 4n ordinary samples of the same size (the Darknet form:
+ * windows are copied, never resampled).  THIS COMMENT IS THE DEFINITION; utils/data_aug.py:mosaic4 is its numpy form.
+ * in_images [4n][H][W][3] float32, in_boxes [4n][kmax][5] = (x0,y0,x1,y1,m), in_labels [4n][kmax] int32, in_counts [4n] int32
+ * (clamped to [0, kmax]).  Output image i is made of samples 4i+q, q = 0..3, by one record of ten int32 in records_host
+ * [n][10]: cx, cy, ox0, oy0, ox1, oy1, ox2, oy2, ox3, oy3.
+ *   tiles     q0 = [0,cx) x [0,cy), q1 = [cx,W) x [0,cy), q2 = [0,cx) x [cy,H), q3 = [cx,W) x [cy,H); tile q has origin
+ *             (tx,ty) and size (tw,th)
+ *   validity  1 <= cx <= W-1, 1 <= cy <= H-1, 0 <= ox_q <= W-tw, 0 <= oy_q <= H-th
+ *   pixels    out[i][y][x][c] = in[4i+q][y-ty+oy_q][x-tx+ox_q][c] for (x,y) in tile q
+ *   boxes     box k < counts[4i+q] of sample 4i+q is (x0,y0,x1,y1,m); the window is wx0 = ox_q, wy0 = oy_q, wx1 = ox_q+tw,
+ *             wy1 = oy_q+th.  Every operation is one float32 operation, rounded, with no fused multiply-add (max / min as
+ *             numpy's: a NaN operand is the result, so a box with a NaN corner is dropped):
+ *               a0 = max(x0,wx0), b0 = max(y0,wy0), a1 = min(x1,wx1), b1 = min(y1,wy1)
+ *               kept iff  a1-a0 >= min_side  and  b1-b0 >= min_side  and  (a1-a0)*(b1-b0) >= min_visible*((x1-x0)*(y1-y0))
+ *               a kept box becomes ((a0-wx0)+tx, (b0-wy0)+ty, (a1-wx0)+tx, (b1-wy0)+ty, m), with its label
+ *   order     kept boxes are written compacted in the order q = 0..3, k ascending within q; out_counts[i] is their number;
+ *             out_boxes [n][4*kmax][5] and out_labels [n][4*kmax] hold kout = 4*kmax rows per image, and every row at or
+ *             behind out_counts[i] is written as zero
+ * Every record is checked on the host against the validity rule before anything is launched (Y3_EINVAL naming the image);
+ * the kernels read the checked copy, uploaded into scratch: y3_mosaic_scratch_bytes(n) bytes (0 for n <= 0).  W is a
+ * multiple of 32 (rows of W*12 bytes, written with 16-byte stores: out_images 16-byte aligned, everything else 4); n <=
+ * 16383; the outputs do not overlap the inputs.  Asynchronous on the context's stream, no host synchronisation (the records
+ * go through the context's pinned staging buffer, like y3_feed_run's: the host waits only while the previous upload out of
+ * that buffer is still in flight); n = 0 returns 0 and launches nothing. */
+size_t y3_mosaic_scratch_bytes(int n);
+int y3_mosaic(y3_ctx* ctx, const float* in_images, const float* in_boxes, const int32_t* in_labels, const int32_t* in_counts,
+              int n, int kmax, int H, int W, const int32_t* records_host, float min_side, float min_visible, float* out_images,
+              float* out_boxes, int32_t* out_labels, int32_t* out_counts, void* scratch, size_t scratch_bytes);
+
 /* The device half of the feeder's JPEG decoder (include/yolo355_jpeg.h).  liby3feed.so's y3f_jpeg_plan wrote n files into
  * one blob; the caller uploads it and passes its device address and size, the host copy of the n y3j_rec records at its
  * start, a scratch of >= the plan's scratch bytes and an output of >= its output bytes.  Every record's extents are checked

@@ -159,6 +159,8 @@ def main():
     ap.add_argument('--epochs', type=int, default=1, help="time this many epochs over the SAME files (the first 3 batches of "
                                                            "epoch 0 are warm-up): with --cache_gb, epochs 1.. are cached ones")
     ap.add_argument('--batch_size', type=int, default=64)
+    ap.add_argument('--mosaic', default='0', help="0,1: Feeder(mosaic=...) - four samples composed into every image on the "
+                                                  "device; both values in one call give the pair of rates")
     ap.add_argument('--check', action='store_true', help="first compare the first batch of a process-backed feeder with a "
                                                          "thread-backed one (same seed): they must be equal")
     args = ap.parse_args()
@@ -194,22 +196,25 @@ def main():
                     if pixels == 'gpu' and (backend != 'thread' or native != '1'):
                         continue
                     cache = int(args.cache_gb * (1 << 30)) if pixels == 'gpu' else 0
-                    f = Feeder(lines, args.batch_size, 80, [416, 416], ANCHORS, mode='train', use_mix_up=True,
-                               num_threads=workers, prefetch=5, seed=1, backend=backend, pixels=pixels, cache_bytes=cache)
-                    if args.epochs > 1:
-                        timed_epochs(f, args, 'native=%s backend=%-7s workers=%3d pixels=%-4s cache=%gGB' % (
-                            native, backend, workers, pixels, args.cache_gb if cache else 0))
+                    for mosaic in [v == '1' for v in args.mosaic.split(',')]:
+                        f = Feeder(lines, args.batch_size, 80, [416, 416], ANCHORS, mode='train', use_mix_up=True,
+                                   num_threads=workers, prefetch=5, seed=1, backend=backend, pixels=pixels, cache_bytes=cache,
+                                   mosaic=mosaic)
+                        if args.epochs > 1:
+                            timed_epochs(f, args, 'native=%s backend=%-7s workers=%3d pixels=%-4s cache=%gGB mosaic=%d' % (
+                                native, backend, workers, pixels, args.cache_gb if cache else 0, mosaic))
+                            f.close()
+                            continue
+                        it = f.epoch(0)
+                        t0, t1, cpu = timed_batches(it, args.batches, torch.cuda.synchronize)
+                        dt = t1 - t0
+                        it.close()
                         f.close()
-                        continue
-                    it = f.epoch(0)
-                    t0, t1, cpu = timed_batches(it, args.batches, torch.cuda.synchronize)
-                    dt = t1 - t0
-                    it.close()
-                    f.close()
-                    images = args.batches * args.batch_size
-                    print('native=%s backend=%-7s workers=%3d pixels=%-4s: %7.0f images/s%s' % (
-                        native, backend, workers, pixels, images / dt,
-                        ', %.2f ms of this process\'s CPU per image' % (1e3 * cpu / images) if backend == 'thread' else ''), flush=True)
+                        images = args.batches * args.batch_size
+                        print('native=%s backend=%-7s workers=%3d pixels=%-4s mosaic=%d: %7.0f images/s%s' % (
+                            native, backend, workers, pixels, mosaic, images / dt,
+                            ', %.2f ms of this process\'s CPU per image' % (1e3 * cpu / images) if backend == 'thread' else ''),
+                            flush=True)
 
 
 if __name__ == '__main__':

@@ -96,6 +96,12 @@ def build_parser():
     p.add_argument('--fix_crop_labels', type=_bool, default=False,
                    help="true: a box keeps its own class when the random crop drops an earlier box of the image (the "
                         "reference filters the boxes but not their labels, utils/data_utils.py:150-153; false reproduces it)")
+    p.add_argument('--mosaic', type=_bool, default=False,
+                   help='true: every training image is cut together from four augmented samples on the device (the Darknet '
+                        'mosaic, feeder.Feeder(mosaic=True); the rule is in include/yolo355.h at y3_mosaic).  Costs four '
+                        'samples per image')
+    p.add_argument('--mosaic_off_epochs', type=int, default=0,
+                   help='with --mosaic true: the last N epochs run without mosaic ("close mosaic")')
     p.add_argument('--multi_scale_train', type=_bool, default=True)
     p.add_argument('--use_label_smooth', type=_bool, default=True)
     p.add_argument('--use_focal_loss', type=_bool, default=True)
@@ -142,6 +148,12 @@ def variables_to_restore(variables, include, exclude):
     """tf.contrib.framework.get_variables_to_restore(include, exclude) on our variable list (train.py:81)."""
     from yolov3_tensorflow_amd.utils.misc_utils import get_variables_to_restore
     return get_variables_to_restore(variables, include, exclude)
+
+
+def mosaic_in_epoch(args, epoch):
+    """Whether `epoch` trains on mosaic images: --mosaic, but not in the last --mosaic_off_epochs epochs of the run."""
+    off = max(0, int(getattr(args, 'mosaic_off_epochs', 0) or 0))
+    return bool(getattr(args, 'mosaic', False)) and epoch < args.total_epoches - off
 
 
 def _cache_bytes(args):
@@ -308,9 +320,10 @@ def main(argv=None):
                     mode='train' if args.augment else 'val', shuffle=True,
                     multi_scale=args.multi_scale_train, use_mix_up=args.use_mix_up, letterbox_resize=args.letterbox_resize,
                     num_threads=args.num_threads, prefetch=args.prefetech_buffer, seed=args.seed, rank=rank, world=world,
-                    backend=args.feeder_backend, cache_bytes=_cache_bytes(args))
+                    backend=args.feeder_backend, cache_bytes=_cache_bytes(args), mosaic=args.mosaic and args.augment)
     for epoch in range(args.total_epoches):
         meters = [AverageMeter() for _ in range(5)]
+        feeder.mosaic = mosaic_in_epoch(args, epoch) and args.augment      # (read by the feeder once per epoch)
         for i, batch in enumerate(feeder.epoch(epoch)):
             images, y_true = batch.images, batch.y_true
             with y3.variable_scope('yolov3'):

@@ -39,6 +39,7 @@ SOURCES = [
     ("y3_voc.hip", ["-ffp-contract=off"]),
     ("y3_beval.hip", ["-ffp-contract=off"]),
     ("y3_coco.hip", ["-ffp-contract=off"]),
+    ("y3_mosaic.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

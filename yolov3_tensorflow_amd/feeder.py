@@ -38,7 +38,13 @@ rebuilt for one process per GPU with the device-resident target assignment of th
   * multi-scale: a new size every `interval` batches, drawn exactly like get_batch_data (random.seed(count // interval)
     over range(10, 20) * 32 = 320 .. 608); mix-up pairing per batch; every random draw comes from generators seeded by
     (seed, epoch, batch, sample), so a run is reproducible whatever the thread interleaving (the reference's is not);
-  * data parallel: rank r of `world` takes samples r::world of every global batch (same shuffle on every rank).
+  * data parallel: rank r of `world` takes samples r::world of every global batch (same shuffle on every rank);
+  * mosaic=True ('train' only): every image of a batch is cut together from four samples - the batch's own entry and three
+    lines drawn from the whole file (utils.data_utils.mosaic_lines; grouped before the rank split).  The 4 * n samples go
+    through the chain above unchanged, by whichever delivery is configured; the coordinator then composes them on the side
+    stream (utils.data_utils.mosaic_batch -> y3_mosaic: windows copied, boxes clipped, filtered and compacted; the rule is
+    in include/yolo355.h) and the consumer assigns targets to the composed [n][4 * kmax][5] boxes.  Four samples' cost per
+    image, and 4 * n images of staging memory per batch in flight.  `feeder.mosaic` is read once per epoch.
 """
 from __future__ import division, print_function
 
@@ -308,7 +314,8 @@ class Batch(object):
 class Feeder(object):
     def __init__(self, lines, batch_size, class_num, img_size, anchors, mode='train', multi_scale=False, use_mix_up=False,
                  letterbox_resize=True, num_threads=10, prefetch=5, shuffle=None, seed=0, rank=0, world=1, interval=10,
-                 device=None, drop_remainder=False, backend=None, pixels=None, cache_bytes=0):
+                 device=None, drop_remainder=False, backend=None, pixels=None, cache_bytes=0, mosaic=False,
+                 mosaic_min_side=2.0, mosaic_min_visible=0.25):
         self.lines = [l for l in lines if (l.strip() if isinstance(l, str) else l)]
         self.batch_size, self.class_num = int(batch_size), int(class_num)
         self.img_size, self.anchors = list(img_size), np.asarray(anchors, np.float32).reshape(9, 2)
@@ -343,6 +350,10 @@ class Feeder(object):
         if self.cache_bytes < 0 or (self.cache_bytes > 0 and pixels != 'gpu'):
             raise ValueError("cache_bytes > 0 keeps decoded sources on the device for the device's pixel work: it needs "
                              "pixels='gpu' (thread backend, native job builder)")
+        if mosaic and mode != 'train':
+            raise ValueError("mosaic=True composes augmented training samples: it needs mode='train'")
+        self.mosaic = bool(mosaic)  # read once per epoch: a caller may switch it off between epochs ("close mosaic")
+        self.mosaic_min_side, self.mosaic_min_visible = float(mosaic_min_side), float(mosaic_min_visible)
         self.cache = None           # feed_cache.SourceCache, made with the side stream's device; lives as long as the feeder
         self._pool = None
         self._side = None           # (device, side stream, DevicePixels or None)
@@ -373,7 +384,11 @@ class Feeder(object):
 
     # ---- host side ------------------------------------------------------------------------------------------------
     def _plan(self, epoch):
-        """[(batch number within the epoch, img_size, [line or mix-up pair, ...] of THIS rank)] for one epoch."""
+        """[(batch number within the epoch, img_size, [line or mix-up pair, ...] of THIS rank)] for one epoch.  With mosaic on,
+        an entry is (batch number, img_size, [group of four lines or mix-up pairs, ...], [record, ...], [own, ...]) of this
+        rank: utils.data_utils.mosaic_lines' groups, formed before the rank split, one utils.data_aug.mosaic_draw record per
+        image, and the position of the batch's own entry in its group."""
+        mosaic = self.mosaic and self.mode == 'train'
         order = list(range(len(self.lines)))
         if self.shuffle:
             random.Random(self.seed * 1000003 + epoch).shuffle(order)      # same order on every rank
@@ -389,13 +404,32 @@ class Feeder(object):
                 from .utils.data_utils import mix_up_lines
                 key = (self.seed * 1000003 + epoch) * 100003 + b
                 lines = mix_up_lines(lines, rng=np.random.RandomState(key % (2 ** 31)), prng=random.Random(key))
+            if mosaic:
+                from .utils.data_aug import mosaic_draw
+                from .utils.data_utils import mosaic_lines
+                key = (self.seed * 1000003 + epoch) * 100003 + b
+                groups, own = mosaic_lines(lines, self.lines, random.Random('mosaic-groups-%d' % key))
+                records = [mosaic_draw(random.Random('mosaic-record-%d-%d' % (key, slot)), size[0], size[1])
+                           for slot in range(len(groups))]
+                mine = slice(self.rank, None, self.world) if groups[self.rank::self.world] else slice(0, 1)
+                plan.append((b, size, groups[mine], records[mine], own[mine]))
+                continue
             mine = lines[self.rank::self.world] or lines[:1]
             plan.append((b, size, mine))
         return plan
 
-    def _job(self, epoch, b, j, line, size):
+    def _job(self, epoch, b, j, line, size, tile=None):
         key = ((self.seed * 1000003 + epoch) * 100003 + b) * 1009 + j * self.world + self.rank
+        if tile is not None:        # sample `tile` of mosaic image j
+            key = key * 4 + tile
         return (line, size, self.mode, self.letterbox, key)
+
+    def _jobs(self, epoch, entry):
+        """The worker jobs of one entry of the plan, in sample order: n of them, or 4 * n (sample 4 * j + tile) with mosaic."""
+        b, size, lines = entry[:3]
+        if len(entry) == 3:
+            return [self._job(epoch, b, j, line, size) for j, line in enumerate(lines)]
+        return [self._job(epoch, b, j, line, size, tile) for j, group in enumerate(lines) for tile, line in enumerate(group)]
 
     def _delivery(self, buffers, shared, cached=None):
         """How this feeder's batches come from the workers (module docstring), over the given pools of batch buffers."""
@@ -405,18 +439,19 @@ class Feeder(object):
             return _HostPixels(buffers, True)
         return _SharedPixels(shared, buffers)
 
-    def _host_batches(self, epoch, delivery, stop):
+    def _host_batches(self, epoch, delivery, stop, plan=None):
         """The host half of an epoch, which needs no device: keeps up to `prefetch` batches of worker jobs in flight and
         yields (img_size,) + delivery.collect(oldest) until the plan is served or `stop` is set.  The consumer hands each
-        batch's buffer back (owner[0].give); the buffers of batches never collected are let go here."""
+        batch's buffer back (owner[0].give); the buffers of batches never collected are let go here.  plan: _plan(epoch) where
+        the caller has made it already.  A mosaic entry is delivered as its 4 * n samples; composing them is the device half's."""
         pool = self._executor()
         pending = []
-        plan = iter(self._plan(epoch))
+        plan = iter(self._plan(epoch) if plan is None else plan)
         try:
             while not stop.is_set():
-                for b, size, lines in islice(plan, self.prefetch - len(pending)):
-                    jobs = [self._job(epoch, b, j, line, size) for j, line in enumerate(lines)]
-                    pending.append((size, delivery.submit(pool, jobs, (len(lines), size[1], size[0], 3))))
+                for entry in islice(plan, self.prefetch - len(pending)):
+                    size, jobs = entry[1], self._jobs(epoch, entry)
+                    pending.append((size, delivery.submit(pool, jobs, (len(jobs), size[1], size[0], 3))))
                 if not pending:
                     break
                 size, oldest = pending.pop(0)
@@ -431,7 +466,7 @@ class Feeder(object):
         thread uploads what _host_batches delivers on a side stream, the consumer assigns the targets."""
         import torch
         from . import framework as fw
-        from .utils.data_utils import process_box_batch
+        from .utils.data_utils import mosaic_batch, process_box_batch
         dev = torch.device(self.device) if self.device is not None else fw.default_device()
         q = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
@@ -465,9 +500,13 @@ class Feeder(object):
                 except queue.Full:
                     continue
 
+        plan = self._plan(epoch)        # (reads self.mosaic: once per epoch)
+
         def produce():
             try:
-                for size, ids, images, boxes, labels, counts, owner in self._host_batches(epoch, delivery, stop):
+                entries = iter(plan)        # _host_batches serves the plan in order: entry and batch go in step
+                for size, ids, images, boxes, labels, counts, owner in self._host_batches(epoch, delivery, stop, plan):
+                    entry = next(entries)
                     with torch.cuda.stream(copy_stream):
                         if on_device:
                             images = device_pixels.run(images, threads=min(self.num_threads, 8), cache=cache)
@@ -476,6 +515,10 @@ class Feeder(object):
                         bx = torch.from_numpy(boxes).pin_memory().to(dev, non_blocking=True)
                         lb = torch.from_numpy(labels.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
                         ct = torch.from_numpy(counts.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+                        if len(entry) > 3:      # mosaic: 4 * n samples -> n images, behind the pixels and the three uploads
+                            images, bx, lb, ct = mosaic_batch(images, bx, lb, ct, entry[3], self.mosaic_min_side,
+                                                              self.mosaic_min_visible)
+                            ids = [ids[4 * j + own] for j, own in enumerate(entry[4])]
                         ev = torch.cuda.Event()
                         ev.record(copy_stream)
                     if owner is not None:

@@ -398,3 +398,94 @@ def random_expand(img, bbox, max_ratio=4, fill=0, keep_ratio=True, prng=None):
     canvas = np.full((big_h, big_w, channels), fill, dtype=img.dtype)
     canvas[at_y:at_y + src_h, at_x:at_x + src_w] = img
     return canvas, bbox
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# mosaic: one image cut together from windows of four samples of the same size (the rule: include/yolo355.h, y3_mosaic)
+# ---------------------------------------------------------------------------------------------------------------------
+def mosaic_tiles(record, w, h):
+    """The four tiles of one record (cx, cy, ox0, oy0, .., ox3, oy3) as (tx, ty, tw, th, ox, oy), q = 0..3."""
+    cx, cy = int(record[0]), int(record[1])
+    return [(cx if q & 1 else 0, cy if q & 2 else 0, w - cx if q & 1 else cx, h - cy if q & 2 else cy,
+             int(record[2 + 2 * q]), int(record[3 + 2 * q])) for q in range(4)]
+
+
+def mosaic_record_fault(record, w, h):
+    """The validity rule of a mosaic record: None, or what is wrong with it."""
+    record = [int(v) for v in record]
+    if len(record) != 10:
+        return 'a record holds ten integers, not %d' % len(record)
+    if not 1 <= record[0] <= w - 1:
+        return 'cx=%d outside [1, %d]' % (record[0], w - 1)
+    if not 1 <= record[1] <= h - 1:
+        return 'cy=%d outside [1, %d]' % (record[1], h - 1)
+    for q, (_, _, tw, th, ox, oy) in enumerate(mosaic_tiles(record, w, h)):
+        if not 0 <= ox <= w - tw:
+            return 'ox%d=%d outside [0, %d]' % (q, ox, w - tw)
+        if not 0 <= oy <= h - th:
+            return 'oy%d=%d outside [0, %d]' % (q, oy, h - th)
+    return None
+
+
+def mosaic_draw(prng, w, h):
+    """One mosaic record for a w x h image.  Ten draws from prng (a random.Random), in this order: the centre
+    cx = randrange(w // 4, w - w // 4 + 1) and cy likewise from h; then for each tile q = 0..3 the window's offset
+    ox = randrange(0, w - tw + 1), oy = randrange(0, h - th + 1)."""
+    w, h = int(w), int(h)
+    if w < 4 or h < 4:
+        raise ValueError("mosaic_draw: a %dx%d image is too small to cut" % (w, h))
+    cx = prng.randrange(w // 4, w - w // 4 + 1)
+    cy = prng.randrange(h // 4, h - h // 4 + 1)
+    record = [cx, cy]
+    for _, _, tw, th, _, _ in mosaic_tiles(record + [0] * 8, w, h):
+        record.append(prng.randrange(0, w - tw + 1))
+        record.append(prng.randrange(0, h - th + 1))
+    return record
+
+
+def mosaic4(images, boxes, labels, counts, records, min_side=2.0, min_visible=0.25):
+    """Compose n images from 4n samples of one size: the numpy float32 form of y3_mosaic and its oracle.
+    images [4n, h, w, 3], boxes [4n, kmax, 5] = (x0, y0, x1, y1, m), labels [4n, kmax], counts [4n], records [n, 10].
+    Output image i takes tile q from sample 4i+q: pixels are copied from the window at (ox_q, oy_q); the sample's boxes are
+    clipped to the window, dropped when a clipped side is below min_side or less than min_visible of the box's area is
+    left, and shifted to the tile.  Returns (images [n, h, w, 3], boxes [n, 4 * kmax, 5] float32, labels [n, 4 * kmax],
+    counts [n]): kept boxes compacted in the order q, k; zero rows behind the count, like collate's padding."""
+    images = np.asarray(images)
+    boxes = np.asarray(boxes, np.float32)
+    labels, counts = np.asarray(labels), np.asarray(counts)
+    records = np.asarray(records, np.int64).reshape(-1, 10)
+    n = len(records)
+    if images.ndim != 4 or images.shape[0] != 4 * n or boxes.ndim != 3 or boxes.shape[0] != 4 * n or boxes.shape[2] != 5:
+        raise ValueError("mosaic4: %d records need images [%d, h, w, 3] and boxes [%d, kmax, 5]" % (n, 4 * n, 4 * n))
+    h, w = images.shape[1:3]
+    kmax = boxes.shape[1]
+    labels, counts = labels.reshape(4 * n, kmax), counts.reshape(4 * n)
+    f32 = np.float32
+    min_side, min_visible = f32(min_side), f32(min_visible)
+    out_images = np.empty((n,) + images.shape[1:], images.dtype)
+    out_boxes = np.zeros((n, 4 * kmax, 5), np.float32)
+    out_labels = np.zeros((n, 4 * kmax), labels.dtype)
+    out_counts = np.zeros((n,), counts.dtype)
+    for i in range(n):
+        fault = mosaic_record_fault(records[i], w, h)
+        if fault:
+            raise ValueError("mosaic4: image %d: %s" % (i, fault))
+        at = 0
+        for q, (tx, ty, tw, th, ox, oy) in enumerate(mosaic_tiles(records[i], w, h)):
+            s = 4 * i + q
+            out_images[i, ty:ty + th, tx:tx + tw] = images[s, oy:oy + th, ox:ox + tw]
+            b = boxes[s, :min(max(int(counts[s]), 0), kmax)]
+            x0, y0, x1, y1 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+            wx0, wy0, wx1, wy1 = f32(ox), f32(oy), f32(ox + tw), f32(oy + th)
+            a0, b0, a1, b1 = np.maximum(x0, wx0), np.maximum(y0, wy0), np.minimum(x1, wx1), np.minimum(y1, wy1)
+            with np.errstate(invalid='ignore', over='ignore'):
+                cw, ch = a1 - a0, b1 - b0
+                keep = (cw >= min_side) & (ch >= min_side) & (cw * ch >= min_visible * ((x1 - x0) * (y1 - y0)))
+                moved = np.stack([(a0 - wx0) + f32(tx), (b0 - wy0) + f32(ty), (a1 - wx0) + f32(tx), (b1 - wy0) + f32(ty),
+                                  b[:, 4]], axis=1)
+            k = int(keep.sum())
+            out_boxes[i, at:at + k] = moved[keep]
+            out_labels[i, at:at + k] = labels[s, :len(b)][keep]
+            at += k
+        out_counts[i] = at
+    return out_images, out_boxes, out_labels, out_counts

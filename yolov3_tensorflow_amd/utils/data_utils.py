@@ -365,6 +365,58 @@ def mix_up_lines(batch_line, rng=None, prng=None):
     return mix_lines
 
 
+def mosaic_lines(entries, all_lines, prng):
+    """The mosaic grouping of a batch: every entry (a line or a mix-up pair) becomes a group of four - the entry itself and
+    three lines drawn with prng.randrange(len(all_lines)) - shuffled with prng.shuffle.  Returns (groups, own): own[i] is the
+    position of the entry inside groups[i] (the image id of the composed image is that entry's)."""
+    groups, own = [], []
+    for entry in entries:
+        group = [(entry, True)] + [(all_lines[prng.randrange(len(all_lines))], False) for _ in range(3)]
+        prng.shuffle(group)
+        groups.append([g[0] for g in group])
+        own.append([g[1] for g in group].index(True))
+    return groups, own
+
+
+def mosaic_batch(images, boxes, labels, counts, records, min_side=2.0, min_visible=0.25):
+    """utils.data_aug.mosaic4 on the device (y3_mosaic; the rule is in include/yolo355.h): device tensors images [4n,h,w,3]
+    float32, boxes [4n,kmax,5] float32, labels [4n,kmax] and counts [4n] int32, records [n][10] host integers ->
+    (images [n,h,w,3], boxes [n,4*kmax,5], labels [n,4*kmax], counts [n]) on the same device.  Asynchronous on torch's current
+    stream; a bad record raises ValueError naming the image before anything is launched."""
+    if not (torch.is_tensor(images) and images.is_cuda):
+        raise ValueError("mosaic_batch composes device tensors (utils.data_aug.mosaic4 is the host form)")
+    dev = images.device
+    images = images.contiguous()
+    if images.dtype != torch.float32 or images.dim() != 4 or images.shape[3] != 3 or images.shape[0] % 4:
+        raise ValueError("mosaic_batch: images must be float32 [4n, h, w, 3]")
+    n4, h, w, _ = images.shape
+    n = n4 // 4
+    recs = np.ascontiguousarray(np.asarray(records, np.int64).reshape(-1, 10))
+    if len(recs) != n or np.any(np.abs(recs) > 2 ** 31 - 1):
+        raise ValueError("mosaic_batch: %d images need %d records of ten int32" % (n4, n))
+    recs = recs.astype(np.int32)
+    boxes = boxes.to(device=dev, dtype=torch.float32).contiguous()
+    if boxes.dim() != 3 or boxes.shape[0] != n4 or boxes.shape[2] != 5:
+        raise ValueError("mosaic_batch: boxes must be [4n, kmax, 5]")
+    kmax = int(boxes.shape[1])
+    labels = labels.to(device=dev, dtype=torch.int32).reshape(n4, kmax).contiguous()
+    counts = counts.to(device=dev, dtype=torch.int32).reshape(n4).contiguous()
+    out_images = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    out_boxes = torch.empty((n, 4 * kmax, 5), dtype=torch.float32, device=dev)
+    out_labels = torch.empty((n, 4 * kmax), dtype=torch.int32, device=dev)
+    out_counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return out_images, out_boxes, out_labels, out_counts
+    lib = _lib.lib()
+    nbytes = int(lib.y3_mosaic_scratch_bytes(n))
+    scratch = fw.stream_scratch('mosaic', dev, nbytes)
+    _lib.check(lib.y3_mosaic(fw.context(dev), fw.ptr(images), fw.ptr(boxes), fw.ptr(labels), fw.ptr(counts), n, kmax, h, w,
+                             recs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), float(min_side), float(min_visible),
+                             fw.ptr(out_images), fw.ptr(out_boxes), fw.ptr(out_labels), fw.ptr(out_counts),
+                             fw.ptr(scratch), nbytes))
+    return out_images, out_boxes, out_labels, out_counts
+
+
 def multi_scale_size(count, interval=10):
     """The image size get_batch_data picks for batch number `count` when multi_scale is on
     (utils/data_utils.py:193-197): random.seed(count // interval); one of 320 .. 608 (range(10, 20) * 32)."""
