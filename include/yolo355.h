@@ -710,6 +710,47 @@ int y3_mosaic(y3_ctx* ctx, const float* in_images, const float* in_boxes, const 
               int n, int kmax, int H, int W, const int32_t* records_host, float min_side, float min_visible, float* out_images,
               float* out_boxes, int32_t* out_labels, int32_t* out_counts, void* scratch, size_t scratch_bytes);
 
+/* ---- random affine warp: n images resampled on the device through one affine map each (rotation / zoom / shear /
+ * translation: the "random perspective" step that follows a mosaic), their boxes mapped, clipped, filtered and compacted.
+ * THIS COMMENT IS THE DEFINITION; utils/data_aug.py:affine_warp is its numpy form.
+ * in_images / out_images [n][H][W][3] float32; boxes [n][kmax][5] = (x0,y0,x1,y1,m), labels [n][kmax] int32, counts [n] int32
+ * (clamped to [0, kmax]) on both sides: a warp never adds boxes.  Image i has one record of twelve int32 in records_host
+ * [n][12]: words 0-5 are ia, ib, ic, id, ie, if, the INVERSE map (output pixel -> source pixel) in Q16 fixed point; words
+ * 6-11 are the bit patterns of six float32 fa, fb, fc, fd, fe, ff, the FORWARD map (source coordinate -> output coordinate).
+ * The host folds the half-pixel centre convention into ic / if (utils/data_aug.py:affine_draw), so the rule below has none.
+ * Integer operations are exact; every float operation is one float32 operation, rounded, with no fused multiply-add.
+ *   validity  |ia|, |ib|, |id|, |ie| <= 2^20; |ic|, |if| <= 2^30; fa .. ff finite; 1 <= H, W <= 4096 (no multiple is asked of
+ *             W: a pixel is written with one 12-byte store at 4-byte alignment); n <= 16383; min_side, min_area and
+ *             max_aspect are no NaN
+ *   pixels    for output pixel (x, y) of image i, in int64:  SX = ia*x + ib*y + ic,  SY = id*x + ie*y + if;
+ *             u0 = SX >> 16, v0 = SY >> 16 (arithmetic shifts: floors);  fx = (SX >> 8) & 255, fy = (SY >> 8) & 255;
+ *             wx1 = fx/256, wx0 = (256-fx)/256, wy1 = fy/256, wy0 = (256-fy)/256 (exact in float32);
+ *             src(u,v,c) = in[i][v][u][c] if 0 <= u < W and 0 <= v < H, else fill;
+ *               top = (wx0*src(u0,v0,c)) + (wx1*src(u0+1,v0,c)),  bot = (wx0*src(u0,v0+1,c)) + (wx1*src(u0+1,v0+1,c))
+ *               out[i][y][x][c] = (wy0*top) + (wy1*bot)
+ *             All four taps are always taken.  Consequence: with fx = fy = 0 a finite pixel whose three neighbours (or fill)
+ *             are finite is reproduced exactly (1*p + 0*q; a -0 comes out as +0)
+ *   boxes     box k < counts[i] is (x0,y0,x1,y1,m).  Its corners, in the order (x0,y0), (x1,y0), (x0,y1), (x1,y1), map as
+ *             u = ((fa*x) + (fb*y)) + fc,  v = ((fd*x) + (fe*y)) + ff.  a0 / a1 are the min / max of the four u and b0 / b1
+ *             of the four v, folded in corner order (max / min as numpy's everywhere: a NaN operand is the result).  Clip:
+ *             a0 = max(a0,0), b0 = max(b0,0), a1 = min(a1,(float)W), b1 = min(b1,(float)H).  With w = a1-a0, h = b1-b0,
+ *             det = |(fa*fe) - (fb*fd)|, area0 = (x1-x0)*(y1-y0) the box is kept iff
+ *               w >= min_side  and  h >= min_side  and  w*h >= min_area*(det*area0)  and  w <= max_aspect*h  and
+ *               h <= max_aspect*w
+ *             (a NaN anywhere fails a comparison and drops the box); a kept box becomes (a0,b0,a1,b1,m), with its label
+ *   order     kept boxes are written compacted in ascending k; out_counts[i] is their number; every row of out_boxes and
+ *             out_labels at or behind out_counts[i] is written as zero
+ * Every record is checked on the host against the validity rule before anything is launched (Y3_EINVAL naming the image,
+ * the word and its range); the kernels read the checked copy, uploaded into scratch: y3_affine_scratch_bytes(n) bytes (0
+ * for n <= 0).  Every pointer is 4-byte aligned; the outputs do not overlap the inputs.  Asynchronous on the context's
+ * stream, no host synchronisation (the records go through the context's pinned staging buffer, as y3_mosaic's do); n = 0
+ * returns 0 and launches nothing. */
+size_t y3_affine_scratch_bytes(int n);
+int y3_affine(y3_ctx* ctx, const float* in_images, const float* in_boxes, const int32_t* in_labels, const int32_t* in_counts,
+              int n, int kmax, int H, int W, const int32_t* records_host, float fill, float min_side, float min_area,
+              float max_aspect, float* out_images, float* out_boxes, int32_t* out_labels, int32_t* out_counts, void* scratch,
+              size_t scratch_bytes);
+
 /* The device half of the feeder's JPEG decoder (include/yolo355_jpeg.h).  liby3feed.so's y3f_jpeg_plan wrote n files into
  * one blob; the caller uploads it and passes its device address and size, the host copy of the n y3j_rec records at its
  * start, a scratch of >= the plan's scratch bytes and an output of >= its output bytes.  Every record's extents are checked

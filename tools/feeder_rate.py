@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 ANCHORS = np.array([10, 13, 16, 30, 33, 23, 30, 61, 62, 45, 59, 119, 116, 90, 156, 198, 373, 326], np.float32)
+AFFINE = (10.0, 0.1, 0.5, 2.0)      # --affine 1: degrees, translate, scale, shear
 
 
 def write_set(folder, n, seed=0):
@@ -161,6 +162,9 @@ def main():
     ap.add_argument('--batch_size', type=int, default=64)
     ap.add_argument('--mosaic', default='0', help="0,1: Feeder(mosaic=...) - four samples composed into every image on the "
                                                   "device; both values in one call give the pair of rates")
+    ap.add_argument('--affine', default='0', help="0,1: Feeder(affine=(10, 0.1, 0.5, 2)) - every delivered image warped on the "
+                                                  "device; both values in one call give the pair of rates")
+    ap.add_argument('--repeat', type=int, default=1, help="run the --mosaic / --affine arms this many times over, alternating")
     ap.add_argument('--check', action='store_true', help="first compare the first batch of a process-backed feeder with a "
                                                          "thread-backed one (same seed): they must be equal")
     args = ap.parse_args()
@@ -196,13 +200,14 @@ def main():
                     if pixels == 'gpu' and (backend != 'thread' or native != '1'):
                         continue
                     cache = int(args.cache_gb * (1 << 30)) if pixels == 'gpu' else 0
-                    for mosaic in [v == '1' for v in args.mosaic.split(',')]:
+                    arms = [(m == '1', a == '1') for m in args.mosaic.split(',') for a in args.affine.split(',')]
+                    for mosaic, affine in arms * args.repeat:
                         f = Feeder(lines, args.batch_size, 80, [416, 416], ANCHORS, mode='train', use_mix_up=True,
                                    num_threads=workers, prefetch=5, seed=1, backend=backend, pixels=pixels, cache_bytes=cache,
-                                   mosaic=mosaic)
+                                   mosaic=mosaic, affine=AFFINE if affine else None)
                         if args.epochs > 1:
-                            timed_epochs(f, args, 'native=%s backend=%-7s workers=%3d pixels=%-4s cache=%gGB mosaic=%d' % (
-                                native, backend, workers, pixels, args.cache_gb if cache else 0, mosaic))
+                            timed_epochs(f, args, 'native=%s backend=%-7s workers=%3d pixels=%-4s cache=%gGB mosaic=%d affine=%d' % (
+                                native, backend, workers, pixels, args.cache_gb if cache else 0, mosaic, affine))
                             f.close()
                             continue
                         it = f.epoch(0)
@@ -211,8 +216,8 @@ def main():
                         it.close()
                         f.close()
                         images = args.batches * args.batch_size
-                        print('native=%s backend=%-7s workers=%3d pixels=%-4s mosaic=%d: %7.0f images/s%s' % (
-                            native, backend, workers, pixels, mosaic, images / dt,
+                        print('native=%s backend=%-7s workers=%3d pixels=%-4s mosaic=%d affine=%d: %7.0f images/s%s' % (
+                            native, backend, workers, pixels, mosaic, affine, images / dt,
                             ', %.2f ms of this process\'s CPU per image' % (1e3 * cpu / images) if backend == 'thread' else ''),
                             flush=True)
 

@@ -102,6 +102,15 @@ def build_parser():
                         'samples per image')
     p.add_argument('--mosaic_off_epochs', type=int, default=0,
                    help='with --mosaic true: the last N epochs run without mosaic ("close mosaic")')
+    p.add_argument('--affine_degrees', type=float, default=0.0,
+                   help='random affine warp of every training image on the device (feeder.Feeder(affine=...); the rule is in '
+                        'include/yolo355.h at y3_affine), on iff any of the four ranges is non-zero and --augment is set: the '
+                        'rotation is drawn from [-DEGREES, DEGREES]')
+    p.add_argument('--affine_translate', type=float, default=0.0,
+                   help='... the centre moves by up to this fraction of the width / height')
+    p.add_argument('--affine_scale', type=float, default=0.0, help='... the zoom is drawn from [1 - SCALE, 1 + SCALE]')
+    p.add_argument('--affine_shear', type=float, default=0.0, help='... both shears are drawn from [-SHEAR, SHEAR] degrees')
+    p.add_argument('--affine_off_epochs', type=int, default=0, help='the last N epochs run without the affine warp')
     p.add_argument('--multi_scale_train', type=_bool, default=True)
     p.add_argument('--use_label_smooth', type=_bool, default=True)
     p.add_argument('--use_focal_loss', type=_bool, default=True)
@@ -154,6 +163,19 @@ def mosaic_in_epoch(args, epoch):
     """Whether `epoch` trains on mosaic images: --mosaic, but not in the last --mosaic_off_epochs epochs of the run."""
     off = max(0, int(getattr(args, 'mosaic_off_epochs', 0) or 0))
     return bool(getattr(args, 'mosaic', False)) and epoch < args.total_epoches - off
+
+
+def affine_ranges(args):
+    """(degrees, translate, scale, shear) for feeder.Feeder(affine=...), or None: the warp is on iff any range is non-zero
+    and --augment is set."""
+    ranges = tuple(float(getattr(args, 'affine_' + k, 0) or 0) for k in ('degrees', 'translate', 'scale', 'shear'))
+    return ranges if any(ranges) and getattr(args, 'augment', True) else None
+
+
+def affine_in_epoch(args, epoch):
+    """The ranges `epoch` trains with: affine_ranges, but None in the last --affine_off_epochs epochs of the run."""
+    off = max(0, int(getattr(args, 'affine_off_epochs', 0) or 0))
+    return affine_ranges(args) if epoch < args.total_epoches - off else None
 
 
 def _cache_bytes(args):
@@ -320,10 +342,12 @@ def main(argv=None):
                     mode='train' if args.augment else 'val', shuffle=True,
                     multi_scale=args.multi_scale_train, use_mix_up=args.use_mix_up, letterbox_resize=args.letterbox_resize,
                     num_threads=args.num_threads, prefetch=args.prefetech_buffer, seed=args.seed, rank=rank, world=world,
-                    backend=args.feeder_backend, cache_bytes=_cache_bytes(args), mosaic=args.mosaic and args.augment)
+                    backend=args.feeder_backend, cache_bytes=_cache_bytes(args), mosaic=args.mosaic and args.augment,
+                    affine=affine_ranges(args))
     for epoch in range(args.total_epoches):
         meters = [AverageMeter() for _ in range(5)]
         feeder.mosaic = mosaic_in_epoch(args, epoch) and args.augment      # (read by the feeder once per epoch)
+        feeder.affine = affine_in_epoch(args, epoch)                       # (likewise)
         for i, batch in enumerate(feeder.epoch(epoch)):
             images, y_true = batch.images, batch.y_true
             with y3.variable_scope('yolov3'):

@@ -187,6 +187,9 @@ PROTOTYPES = {
     "y3_mosaic_scratch_bytes": (c_size_t, [c_int]),
     "y3_mosaic": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(ctypes.c_int32),
                           c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "y3_affine_scratch_bytes": (c_size_t, [c_int]),
+    "y3_affine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(ctypes.c_int32),
+                          c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "y3_jpeg_decode": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                c_void_p]),
     "y3_box_iou": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_void_p]),

@@ -11,16 +11,15 @@
 #include <string.h>
 #include "y3_eval_common.h"
 #include "y3_mosaic_px.h"
+#include "y3_wave_compact.h"
 
 namespace {
 
 using namespace y3ev;
 
-constexpr int kWave = 64;
+constexpr int kWave = y3wc::kWave;
 constexpr int kThreads = 256;
 constexpr int kMaxSide = 16384;
-
-static_assert(sizeof(unsigned long long) * 8 == kWave, "the ballot mask holds one bit per lane of a 64-wide wavefront");
 
 // block (x, i): groups x * kThreads .. of output image i, grid-stride over the image's groups
 __global__ __launch_bounds__(kThreads) void mosaic_pixels_kernel(const float* __restrict__ in, const int32_t* __restrict__ recs,
@@ -67,13 +66,11 @@ __global__ __launch_bounds__(kWave) void mosaic_boxes_kernel(const float* __rest
                 label = in_labels[s * kmax + k];
             }
         }
-        const unsigned long long mask = __ballot(keep);
+        const int at = y3wc::compact_slot(keep, lane, kept);       // at <= j < kout
         if (keep) {
-            const int at = kept + __popcll(mask & ((1ull << lane) - 1ull));       // at <= j < kout
             for (int e = 0; e < 5; ++e) ob[(size_t)at * 5 + e] = row[e];
             ol[at] = label;
         }
-        kept += __popcll(mask);
     }
     for (int j = kept + lane; j < kout; j += kWave) {
         for (int e = 0; e < 5; ++e) ob[(size_t)j * 5 + e] = 0.f;

@@ -44,7 +44,12 @@ rebuilt for one process per GPU with the device-resident target assignment of th
     through the chain above unchanged, by whichever delivery is configured; the coordinator then composes them on the side
     stream (utils.data_utils.mosaic_batch -> y3_mosaic: windows copied, boxes clipped, filtered and compacted; the rule is
     in include/yolo355.h) and the consumer assigns targets to the composed [n][4 * kmax][5] boxes.  Four samples' cost per
-    image, and 4 * n images of staging memory per batch in flight.  `feeder.mosaic` is read once per epoch.
+    image, and 4 * n images of staging memory per batch in flight.  `feeder.mosaic` is read once per epoch;
+  * affine=(degrees, translate, scale, shear) ('train' only): every delivered image, composed or not, is warped by its own
+    random rotation / zoom / shear / translation on the side stream (utils.data_utils.affine_batch -> y3_affine: bilinear
+    resampling through a Q16 inverse map, the letterbox grey outside; boxes mapped, clipped, filtered and compacted; the rule
+    is in include/yolo355.h), behind the composition when mosaic is on.  The host adds six draws and a 3 x 3 product per
+    image (utils.data_aug.affine_draw, _affine_records).  `feeder.affine` is read once per epoch.
 """
 from __future__ import division, print_function
 
@@ -315,7 +320,8 @@ class Feeder(object):
     def __init__(self, lines, batch_size, class_num, img_size, anchors, mode='train', multi_scale=False, use_mix_up=False,
                  letterbox_resize=True, num_threads=10, prefetch=5, shuffle=None, seed=0, rank=0, world=1, interval=10,
                  device=None, drop_remainder=False, backend=None, pixels=None, cache_bytes=0, mosaic=False,
-                 mosaic_min_side=2.0, mosaic_min_visible=0.25):
+                 mosaic_min_side=2.0, mosaic_min_visible=0.25, affine=None, affine_min_side=2.0, affine_min_area=0.1,
+                 affine_max_aspect=20.0):
         self.lines = [l for l in lines if (l.strip() if isinstance(l, str) else l)]
         self.batch_size, self.class_num = int(batch_size), int(class_num)
         self.img_size, self.anchors = list(img_size), np.asarray(anchors, np.float32).reshape(9, 2)
@@ -354,6 +360,16 @@ class Feeder(object):
             raise ValueError("mosaic=True composes augmented training samples: it needs mode='train'")
         self.mosaic = bool(mosaic)  # read once per epoch: a caller may switch it off between epochs ("close mosaic")
         self.mosaic_min_side, self.mosaic_min_visible = float(mosaic_min_side), float(mosaic_min_visible)
+        if affine is not None:
+            if mode != 'train':
+                raise ValueError("affine=(degrees, translate, scale, shear) warps augmented training samples: it needs "
+                                 "mode='train'")
+            affine = tuple(float(v) for v in affine)
+            if len(affine) != 4:
+                raise ValueError("affine must be None or (degrees, translate, scale, shear)")
+        self.affine = affine        # read once per epoch: a caller may set it to None between epochs
+        self.affine_min_side, self.affine_min_area = float(affine_min_side), float(affine_min_area)
+        self.affine_max_aspect = float(affine_max_aspect)
         self.cache = None           # feed_cache.SourceCache, made with the side stream's device; lives as long as the feeder
         self._pool = None
         self._side = None           # (device, side stream, DevicePixels or None)
@@ -418,6 +434,18 @@ class Feeder(object):
             plan.append((b, size, mine))
         return plan
 
+    def _affine_records(self, epoch, entry, affine):
+        """One utils.data_aug.affine_draw record per delivered image of one entry of the plan, for the ranges `affine`.  Image
+        j of this rank is slot rank + j * world of the global batch, and the record is drawn from (key, slot) as the mosaic
+        records are: it depends on neither the workers, the backend nor the number of ranks."""
+        from .utils.data_aug import affine_draw
+        b, size, lines = entry[:3]
+        key = (self.seed * 1000003 + epoch) * 100003 + b
+        whole = min(self.batch_size, len(self.lines) - b * self.batch_size)
+        first = self.rank if self.rank < whole else 0       # (a rank with no share of a short batch takes slot 0, as in _plan)
+        return [affine_draw(random.Random('affine-record-%d-%d' % (key, first + j * self.world)), size[0], size[1], *affine)
+                for j in range(len(lines))]
+
     def _job(self, epoch, b, j, line, size, tile=None):
         key = ((self.seed * 1000003 + epoch) * 100003 + b) * 1009 + j * self.world + self.rank
         if tile is not None:        # sample `tile` of mosaic image j
@@ -466,7 +494,7 @@ class Feeder(object):
         thread uploads what _host_batches delivers on a side stream, the consumer assigns the targets."""
         import torch
         from . import framework as fw
-        from .utils.data_utils import mosaic_batch, process_box_batch
+        from .utils.data_utils import affine_batch, mosaic_batch, pad_fill, process_box_batch
         dev = torch.device(self.device) if self.device is not None else fw.default_device()
         q = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
@@ -501,6 +529,7 @@ class Feeder(object):
                     continue
 
         plan = self._plan(epoch)        # (reads self.mosaic: once per epoch)
+        affine = self.affine if self.mode == 'train' else None      # (likewise)
 
         def produce():
             try:
@@ -519,6 +548,10 @@ class Feeder(object):
                             images, bx, lb, ct = mosaic_batch(images, bx, lb, ct, entry[3], self.mosaic_min_side,
                                                               self.mosaic_min_visible)
                             ids = [ids[4 * j + own] for j, own in enumerate(entry[4])]
+                        if affine is not None:  # every delivered image warped; the border is the letterbox padding's grey
+                            images, bx, lb, ct = affine_batch(images, bx, lb, ct, self._affine_records(epoch, entry, affine),
+                                                              pad_fill(), self.affine_min_side, self.affine_min_area,
+                                                              self.affine_max_aspect)
                         ev = torch.cuda.Event()
                         ev.record(copy_stream)
                     if owner is not None:

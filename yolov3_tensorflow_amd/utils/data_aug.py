@@ -489,3 +489,143 @@ def mosaic4(images, boxes, labels, counts, records, min_side=2.0, min_visible=0.
             at += k
         out_counts[i] = at
     return out_images, out_boxes, out_labels, out_counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# random affine warp: rotation / zoom / shear / translation of one image and its boxes (the rule: include/yolo355.h, y3_affine)
+# ---------------------------------------------------------------------------------------------------------------------
+AFFINE_WORDS = ('ia', 'ib', 'ic', 'id', 'ie', 'if', 'fa', 'fb', 'fc', 'fd', 'fe', 'ff')
+AFFINE_COEF_MAX, AFFINE_OFFSET_MAX, AFFINE_MAX_SIDE = 1 << 20, 1 << 30, 4096
+AFFINE_IDENTITY = (65536, 0, 0, 0, 65536, 0, 0x3f800000, 0, 0, 0, 0x3f800000, 0)
+
+
+def _f32_bits(v):
+    """The bit pattern of float32(v) as a signed 32-bit integer (what a record's words 6-11 hold)."""
+    return int(np.asarray(v, np.float32).view(np.int32))
+
+
+def affine_record(inverse, forward):
+    """A record from an inverse map (ia, ib, ic, id, ie, if as floats in SOURCE PIXEL INDEX units: u = ia*x + ib*y + ic gives
+    the source pixel index of output pixel index (x, y)) and a forward map (fa .. ff on continuous coordinates): the inverse
+    quantised to Q16 with round(v * 65536), the forward cast to float32."""
+    return [int(round(float(v) * 65536.0)) for v in inverse] + [_f32_bits(v) for v in forward]
+
+
+def affine_forward(record):
+    """The six float32 of the forward map held by a record's words 6-11."""
+    return (np.asarray([int(v) for v in record[6:12]], np.int64) & 0xffffffff).astype(np.uint32).view(np.float32)
+
+
+def affine_record_fault(record, w=None, h=None):
+    """The validity rule of an affine record (and of the image size, where given): None, or what is wrong with it - the word
+    by number and name, and the range it has to lie in."""
+    record = [int(v) for v in record]
+    if len(record) != 12:
+        return 'a record holds twelve integers, not %d' % len(record)
+    for name, side in (('w', w), ('h', h)):
+        if side is not None and not 1 <= int(side) <= AFFINE_MAX_SIDE:
+            return '%s=%d outside [1, %d]' % (name, side, AFFINE_MAX_SIDE)
+    for j in range(6):
+        bound = AFFINE_OFFSET_MAX if j in (2, 5) else AFFINE_COEF_MAX
+        if not -bound <= record[j] <= bound:
+            return 'word %d, %s=%d outside [%d, %d]' % (j, AFFINE_WORDS[j], record[j], -bound, bound)
+    for j in range(6, 12):
+        if not -2 ** 31 <= record[j] < 2 ** 32:
+            return 'word %d, %s=%d is no 32-bit pattern' % (j, AFFINE_WORDS[j], record[j])
+        if (record[j] & 0x7f800000) == 0x7f800000:
+            return 'word %d, %s is not finite (bits 0x%08x)' % (j, AFFINE_WORDS[j], record[j] & 0xffffffff)
+    return None
+
+
+def affine_draw(prng, w, h, degrees=0.0, translate=0.0, scale=0.0, shear=0.0):
+    """One affine record for a w x h image.  Six draws from prng (a random.Random), in this order: the angle
+    prng.uniform(-degrees, degrees) in degrees; the zoom prng.uniform(1 - scale, 1 + scale); the shears
+    prng.uniform(-shear, shear) along x and then along y, in degrees; tx = prng.uniform(0.5 - translate, 0.5 + translate) * w
+    and ty likewise with h.  In float64, on continuous coordinates (pixel j covers [j, j + 1), as for boxes and mosaic tiles),
+    the forward map is A = T(tx, ty) . Shear . (zoom . Rot) . T(-w/2, -h/2) with Rot = [[cos, -sin], [sin, cos]] and
+    Shear = [[1, tan(shear x)], [tan(shear y), 1]].  Its closed-form inverse (ia .. if on continuous coordinates) is taken at
+    pixel centres: ic -> ic + 0.5 * (ia + ib) - 0.5, if likewise; affine_record quantises it and casts the forward map.  With
+    every range zero the record is exactly AFFINE_IDENTITY."""
+    w, h = int(w), int(h)
+    angle = math.radians(prng.uniform(-degrees, degrees))
+    zoom = prng.uniform(1.0 - scale, 1.0 + scale)
+    shx = math.tan(math.radians(prng.uniform(-shear, shear)))
+    shy = math.tan(math.radians(prng.uniform(-shear, shear)))
+    tx = prng.uniform(0.5 - translate, 0.5 + translate) * w
+    ty = prng.uniform(0.5 - translate, 0.5 + translate) * h
+    c, s = zoom * math.cos(angle), zoom * math.sin(angle)
+    # M = Shear . (zoom . Rot);  A = [M | (tx, ty) - M . (w/2, h/2)]
+    fa, fb, fd, fe = c + shx * s, shx * c - s, shy * c + s, c - shy * s
+    fc, ff = tx - (fa * (0.5 * w) + fb * (0.5 * h)), ty - (fd * (0.5 * w) + fe * (0.5 * h))
+    det = fa * fe - fb * fd
+    if not abs(det) > 1e-12:
+        raise ValueError("affine_draw: the drawn map is singular (zoom %r, shears %r, %r)" % (zoom, shx, shy))
+    ia, ib, id_, ie = fe / det, -fb / det, -fd / det, fa / det
+    ic, if_ = -(ia * fc + ib * ff), -(id_ * fc + ie * ff)
+    ic, if_ = ic + 0.5 * (ia + ib) - 0.5, if_ + 0.5 * (id_ + ie) - 0.5
+    return affine_record((ia, ib, ic, id_, ie, if_), [v + 0.0 for v in (fa, fb, fc, fd, fe, ff)])     # (+ 0.0: no -0)
+
+
+def affine_warp(images, boxes, labels, counts, records, fill, min_side=2.0, min_area=0.1, max_aspect=20.0):
+    """Warp n images and their boxes, one record each: the numpy float32 form of y3_affine and its oracle.
+    images [n, h, w, 3] float32, boxes [n, kmax, 5] = (x0, y0, x1, y1, m), labels [n, kmax], counts [n], records [n, 12].
+    Every output pixel is the bilinear blend of four taps of its image at the Q16 source position (fill outside); every box
+    is the clipped bounding box of its four mapped corners, dropped when a side is below min_side, its area below min_area of
+    the mapped box's, or one side more than max_aspect times the other.  Returns (images [n, h, w, 3], boxes [n, kmax, 5]
+    float32, labels [n, kmax], counts [n]): kept boxes compacted in order, zero rows behind the count."""
+    images = np.asarray(images)
+    boxes = np.asarray(boxes, np.float32)
+    labels, counts = np.asarray(labels), np.asarray(counts)
+    records = np.asarray(records, np.int64).reshape(-1, 12)
+    n = len(records)
+    if images.ndim != 4 or images.shape[0] != n or images.shape[3] != 3 or images.dtype != np.float32 or boxes.ndim != 3 or \
+            boxes.shape[0] != n or boxes.shape[2] != 5:
+        raise ValueError("affine_warp: %d records need float32 images [%d, h, w, 3] and boxes [%d, kmax, 5]" % (n, n, n))
+    h, w = images.shape[1:3]
+    kmax = boxes.shape[1]
+    labels, counts = labels.reshape(n, kmax), counts.reshape(n)
+    f32 = np.float32
+    fill, min_side, min_area, max_aspect = f32(fill), f32(min_side), f32(min_area), f32(max_aspect)
+    out_images = np.empty_like(images)
+    out_boxes = np.zeros((n, kmax, 5), np.float32)
+    out_labels = np.zeros((n, kmax), labels.dtype)
+    out_counts = np.zeros((n,), counts.dtype)
+    xs, ys = np.arange(w, dtype=np.int64)[None, :], np.arange(h, dtype=np.int64)[:, None]
+    for i in range(n):
+        fault = affine_record_fault(records[i], w, h)
+        if fault:
+            raise ValueError("affine_warp: image %d: %s" % (i, fault))
+        ia, ib, ic, id_, ie, if_ = (int(v) for v in records[i][:6])
+        sx, sy = ia * xs + ib * ys + ic, id_ * xs + ie * ys + if_
+        u0, v0 = sx >> 16, sy >> 16
+        fx, fy = (sx >> 8) & 255, (sy >> 8) & 255
+        wx1, wx0 = (fx.astype(f32) / f32(256))[..., None], ((256 - fx).astype(f32) / f32(256))[..., None]
+        wy1, wy0 = (fy.astype(f32) / f32(256))[..., None], ((256 - fy).astype(f32) / f32(256))[..., None]
+
+        def src(u, v):
+            inside = (u >= 0) & (u < w) & (v >= 0) & (v < h)
+            return np.where(inside[..., None], images[i][np.clip(v, 0, h - 1), np.clip(u, 0, w - 1)], fill)
+        with np.errstate(invalid='ignore', over='ignore'):
+            top = wx0 * src(u0, v0) + wx1 * src(u0 + 1, v0)
+            bot = wx0 * src(u0, v0 + 1) + wx1 * src(u0 + 1, v0 + 1)
+            out_images[i] = wy0 * top + wy1 * bot
+        fa, fb, fc, fd, fe, ff = affine_forward(records[i])
+        b = boxes[i, :min(max(int(counts[i]), 0), kmax)]
+        x0, y0, x1, y1 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+        with np.errstate(invalid='ignore', over='ignore'):
+            us = [(fa * x + fb * y) + fc for x, y in ((x0, y0), (x1, y0), (x0, y1), (x1, y1))]
+            vs = [(fd * x + fe * y) + ff for x, y in ((x0, y0), (x1, y0), (x0, y1), (x1, y1))]
+            a0 = np.minimum(np.minimum(np.minimum(us[0], us[1]), us[2]), us[3])
+            a1 = np.maximum(np.maximum(np.maximum(us[0], us[1]), us[2]), us[3])
+            b0 = np.minimum(np.minimum(np.minimum(vs[0], vs[1]), vs[2]), vs[3])
+            b1 = np.maximum(np.maximum(np.maximum(vs[0], vs[1]), vs[2]), vs[3])
+            a0, b0, a1, b1 = np.maximum(a0, f32(0)), np.maximum(b0, f32(0)), np.minimum(a1, f32(w)), np.minimum(b1, f32(h))
+            bw, bh = a1 - a0, b1 - b0
+            det = np.abs(fa * fe - fb * fd)
+            keep = (bw >= min_side) & (bh >= min_side) & (bw * bh >= min_area * (det * ((x1 - x0) * (y1 - y0)))) & \
+                (bw <= max_aspect * bh) & (bh <= max_aspect * bw)
+        k = int(keep.sum())
+        out_boxes[i, :k] = np.stack([a0, b0, a1, b1, b[:, 4]], axis=1)[keep]
+        out_labels[i, :k] = labels[i, :len(b)][keep]
+        out_counts[i] = k
+    return out_images, out_boxes, out_labels, out_counts

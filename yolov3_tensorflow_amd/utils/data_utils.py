@@ -201,6 +201,7 @@ def resize_with_bbox(img, bbox, new_width, new_height, interp=0, letterbox=False
 # ---------------------------------------------------------------------------------------------------------------------
 # the per-image / per-batch feeder functions (reference utils/data_utils.py:118-224)
 # ---------------------------------------------------------------------------------------------------------------------
+PAD_VALUE = 128     # the grey byte of the letterbox padding (reference utils/data_aug.py:286)
 iter_cnt = 0        # the reference's module-global batch counter (multi-scale: a new size every `interval` batches)
 
 
@@ -302,10 +303,10 @@ def parse_sample(line, img_size, mode, letterbox_resize, rng=None, prng=None, as
         _, fit_w, fit_h, pad_x, pad_y = data_aug.letterbox_geometry(window[2], window[3], width, height)
         resized, pad = (fit_w, fit_h), (pad_x, pad_y)
     if defer:
-        image = feed_native.make_job(img, partner, lam, colour, offset, window, interp, resized, (width, height), pad, 128, flip)
+        image = feed_native.make_job(img, partner, lam, colour, offset, window, interp, resized, (width, height), pad, PAD_VALUE, flip)
         image.key1, image.key2 = keys
     else:
-        image = feed_native.sample(img, partner, lam, colour, offset, window, interp, resized, (width, height), pad, 128, flip,
+        image = feed_native.sample(img, partner, lam, colour, offset, window, interp, resized, (width, height), pad, PAD_VALUE, flip,
                                    out=out, as_float=not as_uint8)
     return (img_idx, image) + split(boxes)
 
@@ -414,6 +415,48 @@ def mosaic_batch(images, boxes, labels, counts, records, min_side=2.0, min_visib
                              recs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), float(min_side), float(min_visible),
                              fw.ptr(out_images), fw.ptr(out_boxes), fw.ptr(out_labels), fw.ptr(out_counts),
                              fw.ptr(scratch), nbytes))
+    return out_images, out_boxes, out_labels, out_counts
+
+
+def pad_fill(value=PAD_VALUE):
+    """The float32 a padded pixel of byte `value` holds in a batch: parse_sample's own `uint8 -> float32 / 255.`."""
+    return float((np.asarray([value], np.uint8).astype(np.float32) / 255.)[0])
+
+
+def affine_batch(images, boxes, labels, counts, records, fill=None, min_side=2.0, min_area=0.1, max_aspect=20.0):
+    """utils.data_aug.affine_warp on the device (y3_affine; the rule is in include/yolo355.h): device tensors images
+    [n,h,w,3] float32, boxes [n,kmax,5] float32, labels [n,kmax] and counts [n] int32, records [n][12] host integers ->
+    new tensors of the same shapes on the same device.  fill: what a tap outside the image reads (default: pad_fill(), the
+    letterbox padding's grey).  Asynchronous on torch's current stream; a bad record raises ValueError naming the image and
+    the word before anything is launched."""
+    if not (torch.is_tensor(images) and images.is_cuda):
+        raise ValueError("affine_batch warps device tensors (utils.data_aug.affine_warp is the host form)")
+    dev = images.device
+    images = images.contiguous()
+    if images.dtype != torch.float32 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("affine_batch: images must be float32 [n, h, w, 3]")
+    n, h, w, _ = images.shape
+    recs = np.ascontiguousarray(np.asarray(records, np.int64).reshape(-1, 12))
+    if len(recs) != n or np.any(recs < -2 ** 31) or np.any(recs >= 2 ** 32):
+        raise ValueError("affine_batch: %d images need %d records of twelve 32-bit words" % (n, n))
+    recs = (recs & 0xffffffff).astype(np.uint32).view(np.int32)
+    boxes = boxes.to(device=dev, dtype=torch.float32).contiguous()
+    if boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 5:
+        raise ValueError("affine_batch: boxes must be [n, kmax, 5]")
+    kmax = int(boxes.shape[1])
+    labels = labels.to(device=dev, dtype=torch.int32).reshape(n, kmax).contiguous()
+    counts = counts.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+    out_images, out_boxes = torch.empty_like(images), torch.empty_like(boxes)
+    out_labels, out_counts = torch.empty_like(labels), torch.empty_like(counts)
+    if n == 0:
+        return out_images, out_boxes, out_labels, out_counts
+    lib = _lib.lib()
+    nbytes = int(lib.y3_affine_scratch_bytes(n))
+    scratch = fw.stream_scratch('affine', dev, nbytes)
+    _lib.check(lib.y3_affine(fw.context(dev), fw.ptr(images), fw.ptr(boxes), fw.ptr(labels), fw.ptr(counts), n, kmax, h, w,
+                             recs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), pad_fill() if fill is None else float(fill),
+                             float(min_side), float(min_area), float(max_aspect), fw.ptr(out_images), fw.ptr(out_boxes),
+                             fw.ptr(out_labels), fw.ptr(out_counts), fw.ptr(scratch), nbytes))
     return out_images, out_boxes, out_labels, out_counts
 
 
