@@ -914,7 +914,7 @@ typedef struct y3_param_desc {
     float* slot1;
     long long n;         /* elements */
     float weight_decay;  /* l2 coefficient (0 for BN parameters and biases) */
-    int reserved;
+    int reserved;        /* flags of y3_layerwise_update_multi (Y3_PARAM_NO_ADAPT); y3_clip_update_multi{,_ema} ignore it */
 } y3_param_desc;
 size_t y3_clip_update_multi_scratch_bytes(const y3_param_desc* params, int count);
 int y3_clip_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* params, int count, float grad_scale,
@@ -947,6 +947,83 @@ int y3_clip_update_multi_ema(y3_ctx* ctx, int kind, const y3_param_desc* params,
                              float clip_norm, float lr, float momentum, float decay, float beta2, float eps,
                              float* const* ema, float ema_step, void* scratch, size_t scratch_bytes);
 int y3_ema_update(y3_ctx* ctx, float* shadow, const float* w, long long n, float ema_step);
+
+/* Layer-wise update rules for large global batches: AdamW (decoupled weight decay, Loshchilov & Hutter 2019), LARS (You et
+ * al. 2017) and LAMB (You et al. 2020), for ALL tensors of a step like y3_clip_update_multi, on its machinery: chunks of
+ * 8192 elements, per-chunk fp32 partial sums, per-tensor sums of the partials in a fixed order in fp64, no atomics - two
+ * calls on the same inputs give the same bits.  Kinds 0-3 are not taken here, and kinds 4-6 are not taken by
+ * y3_clip_update / y3_clip_update_multi / y3_clip_update_multi_ema (which go on ignoring `reserved`).
+ *
+ * Per tensor, with lambda = the descriptor's weight_decay, and every hyper-parameter from `hp`:
+ *     g     = grad_scale * g_in                 NO L2 term is added to the gradient: lambda is used as each kind says below
+ *     G     = ||g||_2,  W = ||w||_2             w BEFORE the step.  Each is float32(sqrt(fp64 sum of the fp32 chunk partials))
+ *     c     = clip_norm / max(G, clip_norm)     tf.clip_by_norm, as in y3_clip_update_multi (G = 0: c = 1)
+ *     gh    = c * g,   Gh = c * G
+ *     adapt = bit 0 of the descriptor's `reserved` (Y3_PARAM_NO_ADAPT) is CLEAR
+ *   (1 - beta1) and (1 - beta2) are formed in fp32 in the kernel from the floats passed, as the adam and rmsprop rules do.
+ *
+ *   Y3_OPT_ADAMW (4)   slot0 = m, slot1 = v
+ *     m <- beta1 * m + (1 - beta1) * gh
+ *     v <- beta2 * v + (1 - beta2) * gh * gh
+ *     w <- w - lr_t * m / (sqrt(v) + eps) - lr * lambda * w_old
+ *       lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t): the host forms it in double, as for adam, and passes BOTH lr and lr_t.
+ *     g is left holding gh.  The ratio reported is 1.
+ *
+ *   Y3_OPT_LARS (5)    slot0 = acc
+ *     ratio = trust * W / (Gh + lambda * W)     if adapt and W > 0 and Gh > 0, else 1
+ *     u     = gh + lambda * w
+ *     acc  <- momentum * acc + ratio * u        the ratio sits INSIDE the accumulator, as in the LARS paper
+ *     w    <- w - lr * acc
+ *     g is left holding gh.  With ratio = 1 this is kind 1 (momentum) with the L2 term added after the clip, not before it.
+ *
+ *   Y3_OPT_LAMB (6)    slot0 = m, slot1 = v
+ *     m, v as for AdamW
+ *     r     = (m * bias1) / (sqrt(v * bias2) + eps) + lambda * w
+ *       bias1 = 1 / (1 - beta1^t), bias2 = 1 / (1 - beta2^t): the host forms both in double and passes them as floats.
+ *     R     = ||r||_2                           by the same reduction as G and W
+ *     ratio = W / R                             if adapt and W > 0 and R > 0, else 1
+ *     w    <- w - lr * ratio * r
+ *     g is left holding r, the direction whose norm was taken: R is the norm of exactly the values that are applied.
+ *
+ *   Corners: a tensor of zeros (W = 0), a zero gradient (Gh = 0; LAMB: R = 0) and a NO_ADAPT tensor take ratio 1, so they
+ *   still move by the plain rule (a new layer can leave zero).  trust = 0 freezes every adapted LARS tensor.  The usual
+ *   exclusion is NO_ADAPT on BN gamma / beta and biases, with lambda = 0 there.
+ *
+ * Launches: AdamW and LARS three - prepare (scales g; two partials per chunk, of g^2 and w^2), norms (one workgroup per
+ * tensor: c, Gh, W, ratio), update (the rule, and the shadow where one is given).  LAMB five - prepare, norms, direction
+ * (m, v; r into g; partials of r^2), norms of r (the ratio), apply (w, the shadow).  A tensor with n %% 4 == 0 moves four
+ * elements per lane in every launch.
+ *
+ * params: HOST array as in y3_clip_update_multi.  ema: HOST array of `count` shadow pointers as in y3_clip_update_multi_ema
+ * ("Weight moving average": the same expression from the w about to be stored, hp->ema_step = 1 - d_t); NULL = no
+ * averages, and NULL entries are allowed.  ratio_dev: NULL, or a DEVICE array of `count` floats that receives each tensor's
+ * ratio.  scratch: y3_layerwise_update_multi_scratch_bytes(params, count) (0 for no tensors), 16-byte aligned.
+ * Asynchronous on the context's stream.
+ *
+ * Y3_EINVAL before any launch, with w, g, slots and shadows untouched: a kind outside 4..6; a NULL ctx, params, hp or
+ * scratch; a tensor with a null w or g, n <= 0 or a missing slot (LARS needs slot0, the others both); a member of hp or a
+ * weight_decay that is not finite; a negative trust, lr, eps or weight_decay; ema_step outside [0, 1]; w, g, a slot or a
+ * shadow of a tensor with n %% 4 == 0 that is not 16-byte aligned; a shadow that overlaps its tensor's w, g or slots; a
+ * scratch too small or misaligned. */
+#define Y3_OPT_ADAMW 4
+#define Y3_OPT_LARS 5
+#define Y3_OPT_LAMB 6
+#define Y3_PARAM_NO_ADAPT 1      /* y3_param_desc.reserved, bit 0: this tensor takes ratio 1 */
+typedef struct y3_layerwise_hp {
+    float grad_scale;    /* 1 / world size, or 1 */
+    float clip_norm;
+    float lr;
+    float lr_t;          /* AdamW's bias-corrected step size */
+    float momentum;      /* LARS */
+    float beta1, beta2;  /* AdamW, LAMB */
+    float eps;           /* AdamW, LAMB */
+    float bias1, bias2;  /* LAMB's 1 / (1 - beta^t) */
+    float trust;         /* LARS's trust coefficient */
+    float ema_step;      /* 1 - d_t of the weight moving average (read only where `ema` is given, checked always) */
+} y3_layerwise_hp;
+size_t y3_layerwise_update_multi_scratch_bytes(const y3_param_desc* params, int count);
+int y3_layerwise_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* params, int count, const y3_layerwise_hp* hp,
+                              float* const* ema, float* ratio_dev, void* scratch, size_t scratch_bytes);
 
 #ifdef __cplusplus
 }

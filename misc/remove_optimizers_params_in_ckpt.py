@@ -1,6 +1,6 @@
 # coding: utf-8
 """Strip the optimizer state from a native checkpoint (the reference's misc/remove_optimizers_params_in_ckpt.py for its TF
-checkpoints): train.py's `.npz` files hold, next to every variable, its Momentum / Adam / RMSProp slots, `optimizer/step` and
+checkpoints): train.py's `.npz` files hold, next to every variable, its Momentum / Adam / RMSProp / AdamW / LARS / LAMB slots, `optimizer/step` and
 `global_step` (utils.misc_utils.Saver) - two to three times the size the forward needs.  A run with --ema_decay also stores
 every trained variable's moving average as '<variable>/ExponentialMovingAverage'; those keys are dropped as well, and with
 --use_ema true the averages are what the stripped file holds under the variables' own names.
@@ -14,7 +14,8 @@ import sys
 
 import numpy as np
 
-SLOT_SUFFIXES = ('/Momentum', '/Adam', '/Adam_1', '/RMSProp', '/RMSProp_1')
+SLOT_SUFFIXES = ('/Momentum', '/Adam', '/Adam_1', '/RMSProp', '/RMSProp_1',
+                 '/AdamW', '/AdamW_1', '/LARS', '/LAMB', '/LAMB_1')
 EMA_SUFFIX = '/ExponentialMovingAverage'
 BOOKKEEPING = ('optimizer/step', 'global_step')
 

@@ -59,10 +59,17 @@ def build_parser():
     p.add_argument('--val_evaluation_epoch', type=int, default=2)
     p.add_argument('--save_epoch', type=int, default=10)
     p.add_argument('--batch_norm_decay', type=float, default=0.99)
-    p.add_argument('--weight_decay', type=float, default=5e-4)
+    p.add_argument('--weight_decay', type=float, default=5e-4,
+                   help='lambda of the conv kernels (BN gamma / beta and biases have none).  sgd, momentum, adam, rmsprop: '
+                        'the L2 term lambda * w added to the gradient before the clip.  adamw: decoupled decay, '
+                        'w -= lr * lambda * w beside the Adam step.  lars: lambda * w joins the clipped gradient and the '
+                        'denominator of the trust ratio.  lamb: lambda * w joins the direction whose norm gives the ratio')
     p.add_argument('--global_step', type=int, default=0)
     # learning rate and optimizer
-    p.add_argument('--optimizer_name', default='momentum', help='sgd | momentum | adam | rmsprop')
+    p.add_argument('--optimizer_name', default='momentum',
+                   help='sgd | momentum | adam | rmsprop (the reference\'s), or for large global batches adamw | lars | lamb '
+                        '(include/yolo355.h, "Layer-wise update rules")')
+    p.add_argument('--lars_trust', type=float, default=0.001, help="lars: the trust coefficient of the per-tensor ratio")
     p.add_argument('--learning_rate_init', type=float, default=1e-4)
     p.add_argument('--lr_type', default='piecewise',
                    help='fixed | exponential | cosine_decay | cosine_decay_restart | piecewise')
@@ -312,7 +319,7 @@ def main(argv=None):
             return args.learning_rate_init * global_step / warm
         return config_learning_rate(args, global_step - warm if args.use_warm_up else global_step)
 
-    optimizer = config_optimizer(args.optimizer_name, learning_rate)
+    optimizer = config_optimizer(args.optimizer_name, learning_rate, trust=args.lars_trust)
     if args.restore_path.endswith('.npz') and args.save_optimizer:
         # optimizer slots + step only, and only for variables that were restored: restore_exclude stays excluded
         restored = set(v.op_name for v in to_restore)

@@ -22,6 +22,15 @@ class ParamDesc(ctypes.Structure):      # y3_param_desc
                 ("weight_decay", c_float), ("reserved", c_int)]
 
 
+Y3_OPT_ADAMW, Y3_OPT_LARS, Y3_OPT_LAMB = 4, 5, 6
+Y3_PARAM_NO_ADAPT = 1                   # ParamDesc.reserved, bit 0
+
+
+class LayerwiseHp(ctypes.Structure):    # y3_layerwise_hp
+    _fields_ = [(n, c_float) for n in ("grad_scale", "clip_norm", "lr", "lr_t", "momentum", "beta1", "beta2", "eps",
+                                       "bias1", "bias2", "trust", "ema_step")]
+
+
 class TrainVar(ctypes.Structure):       # y3_train_var
     _fields_ = [("weights", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("moving_mean", c_void_p),
                 ("moving_variance", c_void_p), ("biases", c_void_p), ("g_weights", c_longlong), ("g_gamma", c_longlong),
@@ -225,6 +234,8 @@ PROTOTYPES = {
     "y3_clip_update_multi_ema": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float,
                                          c_float, c_float, c_void_p, c_float, c_void_p, c_size_t]),
     "y3_ema_update": (c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_float]),
+    "y3_layerwise_update_multi_scratch_bytes": (c_size_t, [c_void_p, c_int]),
+    "y3_layerwise_update_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "y3_net_set_profiling": (c_int, [c_void_p, c_int]),
     "y3_net_get_layer_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
     "y3_net_layer_is_streamk": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),

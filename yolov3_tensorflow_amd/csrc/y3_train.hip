@@ -5,6 +5,7 @@
 // All are HBM-bound streaming/reduction kernels: 16-byte-per-lane accesses along the channel axis,
 // per-workgroup partial sums written to a scratch array and combined by a finalize kernel in a FIXED order
 // (fp64 accumulation) so that every statistic and gradient is run-to-run deterministic (no float atomics).
+#include <cmath>
 #include <vector>
 #include "y3_bf16.h"
 
@@ -848,6 +849,226 @@ __global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ sha
         shadow[i] = ema_one(shadow[i], w[i], ema_step);
 }
 
+// ---- layer-wise rules: AdamW, LARS, LAMB (include/yolo355.h, "Layer-wise update rules") -------------------------------
+// The multi-tensor machinery above (MtDesc, mt_find, MT_CHUNK, fixed-order fp64 sums of per-chunk partials) with TWO
+// partials per chunk (g^2, w^2) and FOUR statistics per tensor.  Every kernel body exists once, for V = 4 elements per lane
+// (n % 4 == 0: every view 16-byte aligned) and V = 1.
+enum { LW_C = 0, LW_GH = 1, LW_W = 2, LW_RATIO = 3, LW_STATS = 4 };     // stat[LW_STATS * t + .]
+
+template <int V> struct LwPack;
+template <> struct LwPack<4> {
+    static __device__ __forceinline__ void ld(float (&r)[4], const float* p) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+        r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3];
+    }
+    static __device__ __forceinline__ void st(float* p, const float (&r)[4]) {
+        f32x4 v; v[0] = r[0]; v[1] = r[1]; v[2] = r[2]; v[3] = r[3];
+        *reinterpret_cast<f32x4*>(p) = v;
+    }
+};
+template <> struct LwPack<1> {
+    static __device__ __forceinline__ void ld(float (&r)[1], const float* p) { r[0] = *p; }
+    static __device__ __forceinline__ void st(float* p, const float (&r)[1]) { *p = r[0]; }
+};
+
+// the chunk of workgroup blockIdx.x: its tensor, and [base, end) inside it
+struct LwChunk { int t; MtDesc d; long long base, end; };
+__device__ __forceinline__ LwChunk lw_chunk(const MtDesc* __restrict__ descs, int count) {
+    LwChunk c;
+    c.t = mt_find(descs, count, blockIdx.x);
+    c.d = descs[c.t];
+    c.base = (long long)(blockIdx.x - c.d.chunk_begin) * MT_CHUNK;
+    c.end = c.base + MT_CHUNK < c.d.n ? c.base + MT_CHUNK : c.d.n;
+    return c;
+}
+
+// the workgroup's sum of one value per thread, in a fixed order (thread 0 holds it)
+__device__ __forceinline__ float lw_wg_sum(float s, float* red /*[4]*/) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    const float r = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return r;
+}
+
+// m and v of AdamW and LAMB from the clipped gradient
+__device__ __forceinline__ void lw_moments(float& m, float& v, float gh, float beta1, float beta2) {
+    m = m * beta1 + (1.f - beta1) * gh;
+    v = v * beta2 + (1.f - beta2) * gh * gh;
+}
+
+// g <- gscale * g ; partial[2 * chunk] = sum of g^2, partial[2 * chunk + 1] = sum of w^2 over the chunk
+template <int V>
+__device__ __forceinline__ void lw_prepare_body(const LwChunk& c, float gscale, float& sg, float& sw) {
+    for (long long i = c.base + V * threadIdx.x; i < c.end; i += 256 * V) {
+        float g[V], w[V];
+        LwPack<V>::ld(g, c.d.g + i);
+        LwPack<V>::ld(w, c.d.w + i);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            g[k] *= gscale;
+            sg += g[k] * g[k];
+            sw += w[k] * w[k];
+        }
+        LwPack<V>::st(c.d.g + i, g);
+    }
+}
+__global__ void __launch_bounds__(256) lw_prepare_kernel(const MtDesc* __restrict__ descs, int count, float gscale,
+                                                         float* __restrict__ partial) {
+    __shared__ float red[4];
+    const LwChunk c = lw_chunk(descs, count);
+    float sg = 0.f, sw = 0.f;
+    if ((c.d.n & 3) == 0) lw_prepare_body<4>(c, gscale, sg, sw); else lw_prepare_body<1>(c, gscale, sg, sw);
+    sg = lw_wg_sum(sg, red);
+    sw = lw_wg_sum(sw, red);
+    if (threadIdx.x == 0) {
+        partial[2 * (size_t)blockIdx.x] = sg;
+        partial[2 * (size_t)blockIdx.x + 1] = sw;
+    }
+}
+
+// one workgroup per tensor: G and W from the chunk partials, then c, Gh, W and the ratio (LARS's; 1 for AdamW, and for LAMB
+// until lw_rnorm_kernel writes it)
+__global__ void __launch_bounds__(256) lw_norms_kernel(const MtDesc* __restrict__ descs, const int* __restrict__ flags,
+                                                       int count, int total_chunks, const float* __restrict__ partial,
+                                                       int kind, float clip, float trust, float* __restrict__ stat,
+                                                       float* __restrict__ ratio_dev) {
+    __shared__ double sh[512];
+    const int t = blockIdx.x;
+    const int b = descs[t].chunk_begin, e = t + 1 < count ? descs[t + 1].chunk_begin : total_chunks;
+    double s_g, s_w;
+    block_sum2_fixed(partial + 2 * (size_t)b, e - b, (size_t)2, (size_t)0, (size_t)1, sh, s_g, s_w);
+    if (threadIdx.x == 0) {
+        const float G = (float)sqrt(s_g), W = (float)sqrt(s_w);
+        const float c = clip / fmaxf(G, clip), Gh = c * G, wd = descs[t].wd;
+        float ratio = 1.f;
+        if (kind == Y3_OPT_LARS && !(flags[t] & Y3_PARAM_NO_ADAPT) && W > 0.f && Gh > 0.f) ratio = trust * W / (Gh + wd * W);
+        stat[LW_STATS * t + LW_C] = c;
+        stat[LW_STATS * t + LW_GH] = Gh;
+        stat[LW_STATS * t + LW_W] = W;
+        stat[LW_STATS * t + LW_RATIO] = ratio;
+        if (ratio_dev && kind != Y3_OPT_LAMB) ratio_dev[t] = ratio;
+    }
+}
+
+// AdamW / LARS: the rule on the clipped gradient, and the shadow (ema: NULL, or one pointer per tensor, NULL = none)
+template <int V>
+__device__ __forceinline__ void lw_update_body(const LwChunk& c, float* e, int kind, float cf, float ratio,
+                                               const y3_layerwise_hp& hp) {
+    const float wd = c.d.wd;
+    for (long long i = c.base + V * threadIdx.x; i < c.end; i += 256 * V) {
+        float g[V], w[V], s0[V], s1[V] = {}, sh[V] = {};
+        LwPack<V>::ld(g, c.d.g + i);
+        LwPack<V>::ld(w, c.d.w + i);
+        LwPack<V>::ld(s0, c.d.s0 + i);
+        if (kind == Y3_OPT_ADAMW) LwPack<V>::ld(s1, c.d.s1 + i);
+        if (e) LwPack<V>::ld(sh, e + i);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const float gh = g[k] * cf;
+            g[k] = gh;
+            if (kind == Y3_OPT_ADAMW) {
+                lw_moments(s0[k], s1[k], gh, hp.beta1, hp.beta2);
+                w[k] = w[k] - hp.lr_t * s0[k] / (sqrtf(s1[k]) + hp.eps) - hp.lr * wd * w[k];
+            } else {
+                s0[k] = hp.momentum * s0[k] + ratio * (gh + wd * w[k]);
+                w[k] -= hp.lr * s0[k];
+            }
+            if (e) sh[k] = ema_one(sh[k], w[k], hp.ema_step);
+        }
+        LwPack<V>::st(c.d.g + i, g);                  // the clipped gradient stays observable
+        LwPack<V>::st(c.d.w + i, w);
+        LwPack<V>::st(c.d.s0 + i, s0);
+        if (kind == Y3_OPT_ADAMW) LwPack<V>::st(c.d.s1 + i, s1);
+        if (e) LwPack<V>::st(e + i, sh);
+    }
+}
+__global__ void __launch_bounds__(256) lw_update_kernel(const MtDesc* __restrict__ descs, float* const* __restrict__ ema,
+                                                        int count, const float* __restrict__ stat, int kind,
+                                                        y3_layerwise_hp hp) {
+    const LwChunk c = lw_chunk(descs, count);
+    float* const e = ema ? ema[c.t] : nullptr;
+    const float cf = stat[LW_STATS * c.t + LW_C], ratio = stat[LW_STATS * c.t + LW_RATIO];
+    if ((c.d.n & 3) == 0) lw_update_body<4>(c, e, kind, cf, ratio, hp); else lw_update_body<1>(c, e, kind, cf, ratio, hp);
+}
+
+// LAMB, third launch: m and v; the direction r into g; partial[2 * chunk] = sum of r^2 over the chunk
+template <int V>
+__device__ __forceinline__ void lw_direction_body(const LwChunk& c, float cf, const y3_layerwise_hp& hp, float& sr) {
+    const float wd = c.d.wd;
+    for (long long i = c.base + V * threadIdx.x; i < c.end; i += 256 * V) {
+        float g[V], w[V], m[V], v[V];
+        LwPack<V>::ld(g, c.d.g + i);
+        LwPack<V>::ld(w, c.d.w + i);
+        LwPack<V>::ld(m, c.d.s0 + i);
+        LwPack<V>::ld(v, c.d.s1 + i);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            lw_moments(m[k], v[k], g[k] * cf, hp.beta1, hp.beta2);
+            const float r = (m[k] * hp.bias1) / (sqrtf(v[k] * hp.bias2) + hp.eps) + wd * w[k];
+            g[k] = r;
+            sr += r * r;
+        }
+        LwPack<V>::st(c.d.g + i, g);
+        LwPack<V>::st(c.d.s0 + i, m);
+        LwPack<V>::st(c.d.s1 + i, v);
+    }
+}
+__global__ void __launch_bounds__(256) lw_direction_kernel(const MtDesc* __restrict__ descs, int count,
+                                                           const float* __restrict__ stat, y3_layerwise_hp hp,
+                                                           float* __restrict__ partial) {
+    __shared__ float red[4];
+    const LwChunk c = lw_chunk(descs, count);
+    const float cf = stat[LW_STATS * c.t + LW_C];
+    float sr = 0.f;
+    if ((c.d.n & 3) == 0) lw_direction_body<4>(c, cf, hp, sr); else lw_direction_body<1>(c, cf, hp, sr);
+    sr = lw_wg_sum(sr, red);
+    if (threadIdx.x == 0) partial[2 * (size_t)blockIdx.x] = sr;
+}
+
+// LAMB, fourth launch: R from the chunk partials of r^2, then the ratio W / R
+__global__ void __launch_bounds__(256) lw_rnorm_kernel(const MtDesc* __restrict__ descs, const int* __restrict__ flags,
+                                                       int count, int total_chunks, const float* __restrict__ partial,
+                                                       float* __restrict__ stat, float* __restrict__ ratio_dev) {
+    __shared__ double sh[256];
+    const int t = blockIdx.x;
+    const int b = descs[t].chunk_begin, e = t + 1 < count ? descs[t + 1].chunk_begin : total_chunks;
+    const double s = block_sum_fixed(partial + 2 * (size_t)b, e - b, (size_t)2, (size_t)0, sh);
+    if (threadIdx.x == 0) {
+        const float R = (float)sqrt(s), W = stat[LW_STATS * t + LW_W];
+        const float ratio = !(flags[t] & Y3_PARAM_NO_ADAPT) && W > 0.f && R > 0.f ? W / R : 1.f;
+        stat[LW_STATS * t + LW_RATIO] = ratio;
+        if (ratio_dev) ratio_dev[t] = ratio;
+    }
+}
+
+// LAMB, fifth launch: w <- w - lr * ratio * r, and the shadow
+template <int V>
+__device__ __forceinline__ void lw_apply_body(const LwChunk& c, float* e, float step, float ema_step) {
+    for (long long i = c.base + V * threadIdx.x; i < c.end; i += 256 * V) {
+        float r[V], w[V], sh[V] = {};
+        LwPack<V>::ld(r, c.d.g + i);
+        LwPack<V>::ld(w, c.d.w + i);
+        if (e) LwPack<V>::ld(sh, e + i);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            w[k] -= step * r[k];
+            if (e) sh[k] = ema_one(sh[k], w[k], ema_step);
+        }
+        LwPack<V>::st(c.d.w + i, w);
+        if (e) LwPack<V>::st(e + i, sh);
+    }
+}
+__global__ void __launch_bounds__(256) lw_apply_kernel(const MtDesc* __restrict__ descs, float* const* __restrict__ ema,
+                                                       int count, const float* __restrict__ stat, float lr, float ema_step) {
+    const LwChunk c = lw_chunk(descs, count);
+    float* const e = ema ? ema[c.t] : nullptr;
+    const float step = lr * stat[LW_STATS * c.t + LW_RATIO];
+    if ((c.d.n & 3) == 0) lw_apply_body<4>(c, e, step, ema_step); else lw_apply_body<1>(c, e, step, ema_step);
+}
+
 // sum over rows of an [M][C] matrix with arbitrary C (bias gradient of the detection convs, C = 3*(5+classes))
 __global__ void __launch_bounds__(256) col_sum_scalar_kernel(const float* __restrict__ x, long long M, int C,
                                                              float* __restrict__ partial /*[grid][C]*/) {
@@ -1260,33 +1481,59 @@ extern "C" int y3_clip_update(y3_ctx* ctx, int kind, float* w, float* g, float* 
 
 static long long mt_chunks(long long n) { return (n + MT_CHUNK - 1) / MT_CHUNK; }
 
-extern "C" size_t y3_clip_update_multi_scratch_bytes(const y3_param_desc* params, int count) {
+// ---- one host path for every multi-tensor update call ----------------------------------------------------------------------
+// Scratch: [descs][`parts` partials per chunk][`stats` floats per tensor], and from the next multiple of 256 on
+// [shadow pointer per tensor][flag word per tensor] for the calls that have them.  y3_clip_update_multi{,_ema} use MT_CLIP
+// (their layout as it always was), y3_layerwise_update_multi uses MT_LAYERWISE.
+struct MtLayout { int parts, stats; bool layerwise; };
+constexpr MtLayout MT_CLIP = {1, 1, false}, MT_LAYERWISE = {2, LW_STATS, true};
+
+static size_t mt_base_bytes(const y3_param_desc* params, int count, MtLayout lay) {
     if (!params || count <= 0) return 0;
     long long chunks = 0;
     for (int i = 0; i < count; ++i) chunks += params[i].n > 0 ? mt_chunks(params[i].n) : 0;
-    // [descs][partial per chunk][norm per tensor]
-    return (((size_t)count * sizeof(MtDesc) + 255) & ~(size_t)255) + (((size_t)chunks * 4 + 255) & ~(size_t)255) +
-           (size_t)count * 4 + 256;
+    return (((size_t)count * sizeof(MtDesc) + 255) & ~(size_t)255) + (((size_t)chunks * 4 * lay.parts + 255) & ~(size_t)255) +
+           (size_t)count * 4 * lay.stats + 256;
+}
+static size_t mt_ema_offset(const y3_param_desc* params, int count, MtLayout lay) {
+    return (mt_base_bytes(params, count, lay) + 255) & ~(size_t)255;
 }
 
-// One host path for y3_clip_update_multi (ema == nullptr: its three launches, scratch layout and upload as they always were)
-// and y3_clip_update_multi_ema (the shadow pointers ride in the same pinned staging buffer, behind the descriptors).
-static size_t mt_ema_offset(const y3_param_desc* params, int count) {
-    return (y3_clip_update_multi_scratch_bytes(params, count) + 255) & ~(size_t)255;
+extern "C" size_t y3_clip_update_multi_scratch_bytes(const y3_param_desc* params, int count) {
+    return mt_base_bytes(params, count, MT_CLIP);
+}
+
+// [the plain call's scratch, rounded up to 256][shadow pointer per tensor]
+extern "C" size_t y3_clip_update_multi_ema_scratch_bytes(const y3_param_desc* params, int count) {
+    if (!params || count <= 0) return 0;
+    return mt_ema_offset(params, count, MT_CLIP) + (size_t)count * sizeof(float*);
+}
+
+// [descs][two partials per chunk][four statistics per tensor], rounded up to 256, [shadow pointer][flag word] per tensor
+extern "C" size_t y3_layerwise_update_multi_scratch_bytes(const y3_param_desc* params, int count) {
+    if (!params || count <= 0) return 0;
+    return mt_ema_offset(params, count, MT_LAYERWISE) + (size_t)count * (sizeof(float*) + sizeof(int));
 }
 
 static bool mt_overlap(const float* a, const float* b, long long n) {      // [a, a + n) meets [b, b + n)
     return a && b && (uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n);
 }
 
-static int clip_update_multi_impl(const char* who, y3_ctx* ctx, int kind, const y3_param_desc* params, int count,
-                                  float grad_scale, float clip_norm, float lr, float momentum, float decay, float beta2,
-                                  float eps, float* const* ema, float ema_step, void* scratch, size_t scratch_bytes) {
-    Y3_CHECK_ARG(ctx && params && scratch, "%s: null argument", who);
-    Y3_CHECK_ARG(count > 0 && count <= 65536, "%s: bad tensor count %d", who, count);
-    Y3_CHECK_ARG(kind >= 0 && kind <= 3, "%s: unknown optimizer kind %d", who, kind);
-    const size_t need = ema ? y3_clip_update_multi_ema_scratch_bytes(params, count)
-                            : y3_clip_update_multi_scratch_bytes(params, count);
+static int mt_slots(int kind) {        // how many slots the rule keeps
+    static const int n[] = {0, 1, 2, 2, 2, 1, 2};
+    return n[kind];
+}
+
+// What the launches of a call work on, in the scratch (ema, flags: nullptr where the call has none).
+struct MtPlan {
+    MtDesc* descs; float* partial; float* stat; float** ema; int* flags;
+    long long chunks;
+};
+
+// Checks the tensors' and the shadows' contracts (before anything is touched), fills the descriptors, the shadow pointers and
+// the flag words into the context's pinned staging buffer and issues their upload.  `need`: the caller's scratch size.
+static int mt_stage(const char* who, y3_ctx* ctx, int kind, const y3_param_desc* params, int count, float* const* ema,
+                    float ema_step, MtLayout lay, size_t need, void* scratch, size_t scratch_bytes, MtPlan* plan) {
     Y3_CHECK_ARG(scratch_bytes >= need && ((uintptr_t)scratch & 15) == 0, "%s: scratch too small or misaligned", who);
     for (int i = 0; ema && i < count; ++i) {      // the shadows' contract, before anything is touched
         const y3_param_desc& q = params[i];
@@ -1300,48 +1547,77 @@ static int clip_update_multi_impl(const char* who, y3_ctx* ctx, int kind, const 
     // out of it has completed (an event behind that copy), so the asynchronous copy below can never race with this
     // or a later call's rewrite of the buffer
     const size_t desc_bytes = (size_t)count * sizeof(MtDesc), ema_bytes = ema ? (size_t)count * sizeof(float*) : 0;
+    const size_t flag_bytes = lay.layerwise ? (size_t)count * sizeof(int) : 0;
     void* stage = nullptr;
     {
-        const int rc = y3_ctx_stage_acquire(ctx, desc_bytes + ema_bytes, &stage);
+        const int rc = y3_ctx_stage_acquire(ctx, desc_bytes + ema_bytes + flag_bytes, &stage);
         if (rc != Y3_OK) return rc;
     }
     MtDesc* host = static_cast<MtDesc*>(stage);
     float** host_ema = reinterpret_cast<float**>(static_cast<char*>(stage) + desc_bytes);
+    int* host_flags = reinterpret_cast<int*>(static_cast<char*>(stage) + desc_bytes + ema_bytes);
     long long chunks = 0;
     for (int i = 0; i < count; ++i) {
         const y3_param_desc& q = params[i];
         Y3_CHECK_ARG(q.w && q.g && q.n > 0, "%s: tensor %d has a null pointer or no elements", who, i);
-        Y3_CHECK_ARG(kind == 0 || q.slot0, "%s: tensor %d: optimizer slot missing", who, i);
-        Y3_CHECK_ARG(kind < 2 || q.slot1, "%s: tensor %d: second optimizer slot missing", who, i);
+        Y3_CHECK_ARG(mt_slots(kind) < 1 || q.slot0, "%s: tensor %d: optimizer slot missing", who, i);
+        Y3_CHECK_ARG(mt_slots(kind) < 2 || q.slot1, "%s: tensor %d: second optimizer slot missing", who, i);
         Y3_CHECK_ARG((((uintptr_t)q.w | (uintptr_t)q.g) & 15) == 0 || (q.n & 3) != 0,
                      "%s: tensor %d: w and g must be 16-byte aligned", who, i);
+        if (lay.layerwise) {        // the slots move four elements per lane too; weight_decay is a factor of its own here
+            Y3_CHECK_ARG((((uintptr_t)q.slot0 | (uintptr_t)q.slot1) & 15) == 0 || (q.n & 3) != 0,
+                         "%s: tensor %d: the slots must be 16-byte aligned", who, i);
+            Y3_CHECK_ARG(std::isfinite(q.weight_decay) && q.weight_decay >= 0.f, "%s: tensor %d: weight_decay %g", who, i,
+                         (double)q.weight_decay);
+            host_flags[i] = q.reserved;
+        }
         if (ema) host_ema[i] = ema_step != 0.f ? ema[i] : nullptr;     // a step of 0 keeps every shadow's bits: nothing to write
         host[i] = MtDesc{q.w, q.g, q.slot0, q.slot1, q.n, q.weight_decay, (int)chunks};
         chunks += mt_chunks(q.n);
         Y3_CHECK_ARG(chunks < (1LL << 30), "%s: too many elements", who);
     }
     char* base = static_cast<char*>(scratch);
-    MtDesc* descs = reinterpret_cast<MtDesc*>(base);
-    float* partial = reinterpret_cast<float*>(base + ((desc_bytes + 255) & ~(size_t)255));
-    float* norm = reinterpret_cast<float*>(reinterpret_cast<char*>(partial) + (((size_t)chunks * 4 + 255) & ~(size_t)255));
-    float** dev_ema = ema ? reinterpret_cast<float**>(base + mt_ema_offset(params, count)) : nullptr;
+    char* tail = base + mt_ema_offset(params, count, lay);
+    plan->descs = reinterpret_cast<MtDesc*>(base);
+    plan->partial = reinterpret_cast<float*>(base + ((desc_bytes + 255) & ~(size_t)255));
+    plan->stat = reinterpret_cast<float*>(reinterpret_cast<char*>(plan->partial) +
+                                          (((size_t)chunks * 4 * lay.parts + 255) & ~(size_t)255));
+    plan->ema = ema ? reinterpret_cast<float**>(tail) : nullptr;
+    plan->flags = lay.layerwise ? reinterpret_cast<int*>(tail + (size_t)count * sizeof(float*)) : nullptr;
+    plan->chunks = chunks;
     hipStream_t st = ctx->stream;
-    Y3_CHECK_HIP(hipMemcpyAsync(descs, host, desc_bytes, hipMemcpyHostToDevice, st));
-    if (ema) Y3_CHECK_HIP(hipMemcpyAsync(dev_ema, host_ema, ema_bytes, hipMemcpyHostToDevice, st));
+    Y3_CHECK_HIP(hipMemcpyAsync(plan->descs, host, desc_bytes, hipMemcpyHostToDevice, st));
+    if (ema) Y3_CHECK_HIP(hipMemcpyAsync(plan->ema, host_ema, ema_bytes, hipMemcpyHostToDevice, st));
+    if (lay.layerwise) Y3_CHECK_HIP(hipMemcpyAsync(plan->flags, host_flags, flag_bytes, hipMemcpyHostToDevice, st));
+    return y3_ctx_stage_release(ctx);
+}
+
+// y3_clip_update_multi (ema == nullptr: its three launches, scratch layout and upload as they always were) and
+// y3_clip_update_multi_ema (the shadow pointers ride in the same pinned staging buffer, behind the descriptors).
+static int clip_update_multi_impl(const char* who, y3_ctx* ctx, int kind, const y3_param_desc* params, int count,
+                                  float grad_scale, float clip_norm, float lr, float momentum, float decay, float beta2,
+                                  float eps, float* const* ema, float ema_step, void* scratch, size_t scratch_bytes) {
+    Y3_CHECK_ARG(ctx && params && scratch, "%s: null argument", who);
+    Y3_CHECK_ARG(count > 0 && count <= 65536, "%s: bad tensor count %d", who, count);
+    Y3_CHECK_ARG(kind >= 0 && kind <= 3, "%s: unknown optimizer kind %d", who, kind);
+    const size_t need = ema ? y3_clip_update_multi_ema_scratch_bytes(params, count)
+                            : y3_clip_update_multi_scratch_bytes(params, count);
+    MtPlan p;
     {
-        const int rc = y3_ctx_stage_release(ctx);
+        const int rc = mt_stage(who, ctx, kind, params, count, ema, ema_step, MT_CLIP, need, scratch, scratch_bytes, &p);
         if (rc != Y3_OK) return rc;
     }
-    hipLaunchKernelGGL(mt_prepare_kernel, dim3((unsigned)chunks), dim3(256), 0, st, descs, count, grad_scale, partial);
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(mt_prepare_kernel, dim3((unsigned)p.chunks), dim3(256), 0, st, p.descs, count, grad_scale, p.partial);
     Y3_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mt_norms_kernel, dim3(count), dim3(256), 0, st, descs, count, (int)chunks, partial, norm);
+    hipLaunchKernelGGL(mt_norms_kernel, dim3(count), dim3(256), 0, st, p.descs, count, (int)p.chunks, p.partial, p.stat);
     Y3_CHECK_HIP(hipGetLastError());
     if (ema)
-        hipLaunchKernelGGL(mt_update_ema_kernel, dim3((unsigned)chunks), dim3(256), 0, st, descs, dev_ema, count, norm,
+        hipLaunchKernelGGL(mt_update_ema_kernel, dim3((unsigned)p.chunks), dim3(256), 0, st, p.descs, p.ema, count, p.stat,
                            clip_norm, kind, lr, momentum, decay, beta2, eps, ema_step);
     else
-        hipLaunchKernelGGL(mt_update_kernel, dim3((unsigned)chunks), dim3(256), 0, st, descs, count, norm, clip_norm, kind,
-                           lr, momentum, decay, beta2, eps);
+        hipLaunchKernelGGL(mt_update_kernel, dim3((unsigned)p.chunks), dim3(256), 0, st, p.descs, count, p.stat, clip_norm,
+                           kind, lr, momentum, decay, beta2, eps);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
 }
@@ -1353,12 +1629,6 @@ extern "C" int y3_clip_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* 
                                   beta2, eps, nullptr, 0.f, scratch, scratch_bytes);
 }
 
-// [the plain call's scratch, rounded up to 256][shadow pointer per tensor]
-extern "C" size_t y3_clip_update_multi_ema_scratch_bytes(const y3_param_desc* params, int count) {
-    if (!params || count <= 0) return 0;
-    return mt_ema_offset(params, count) + (size_t)count * sizeof(float*);
-}
-
 static bool ema_step_ok(float s) { return s >= 0.f && s <= 1.f; }      // (false for NaN)
 
 extern "C" int y3_clip_update_multi_ema(y3_ctx* ctx, int kind, const y3_param_desc* params, int count, float grad_scale,
@@ -1368,6 +1638,48 @@ extern "C" int y3_clip_update_multi_ema(y3_ctx* ctx, int kind, const y3_param_de
     Y3_CHECK_ARG(ema_step_ok(ema_step), "y3_clip_update_multi_ema: ema_step %g is not in [0, 1]", (double)ema_step);
     return clip_update_multi_impl("y3_clip_update_multi_ema", ctx, kind, params, count, grad_scale, clip_norm, lr, momentum,
                                   decay, beta2, eps, ema, ema_step, scratch, scratch_bytes);
+}
+
+// AdamW / LARS: prepare, norms, update.  LAMB: prepare, norms, direction, norms of r, apply.
+extern "C" int y3_layerwise_update_multi(y3_ctx* ctx, int kind, const y3_param_desc* params, int count,
+                                         const y3_layerwise_hp* hp, float* const* ema, float* ratio_dev, void* scratch,
+                                         size_t scratch_bytes) {
+    const char* who = "y3_layerwise_update_multi";
+    Y3_CHECK_ARG(ctx && params && hp && scratch, "%s: null argument", who);
+    Y3_CHECK_ARG(count > 0 && count <= 65536, "%s: bad tensor count %d", who, count);
+    Y3_CHECK_ARG(kind >= Y3_OPT_ADAMW && kind <= Y3_OPT_LAMB, "%s: unknown optimizer kind %d", who, kind);
+    const float all[] = {hp->grad_scale, hp->clip_norm, hp->lr, hp->lr_t, hp->momentum, hp->beta1, hp->beta2, hp->eps,
+                         hp->bias1, hp->bias2, hp->trust, hp->ema_step};
+    static_assert(sizeof(all) == sizeof(y3_layerwise_hp), "every member of y3_layerwise_hp is checked");
+    for (float v : all) Y3_CHECK_ARG(std::isfinite(v), "%s: a hyper-parameter is not finite", who);
+    Y3_CHECK_ARG(hp->trust >= 0.f && hp->lr >= 0.f && hp->eps >= 0.f, "%s: negative trust, lr or eps", who);
+    Y3_CHECK_ARG(ema_step_ok(hp->ema_step), "%s: ema_step %g is not in [0, 1]", who, (double)hp->ema_step);
+    MtPlan p;
+    {
+        const int rc = mt_stage(who, ctx, kind, params, count, ema, hp->ema_step, MT_LAYERWISE,
+                                y3_layerwise_update_multi_scratch_bytes(params, count), scratch, scratch_bytes, &p);
+        if (rc != Y3_OK) return rc;
+    }
+    hipStream_t st = ctx->stream;
+    const dim3 per_chunk((unsigned)p.chunks), per_tensor(count), wg(256);
+    hipLaunchKernelGGL(lw_prepare_kernel, per_chunk, wg, 0, st, p.descs, count, hp->grad_scale, p.partial);
+    Y3_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lw_norms_kernel, per_tensor, wg, 0, st, p.descs, p.flags, count, (int)p.chunks, p.partial, kind,
+                       hp->clip_norm, hp->trust, p.stat, ratio_dev);
+    Y3_CHECK_HIP(hipGetLastError());
+    if (kind != Y3_OPT_LAMB) {
+        hipLaunchKernelGGL(lw_update_kernel, per_chunk, wg, 0, st, p.descs, p.ema, count, p.stat, kind, *hp);
+        Y3_CHECK_HIP(hipGetLastError());
+        return Y3_OK;
+    }
+    hipLaunchKernelGGL(lw_direction_kernel, per_chunk, wg, 0, st, p.descs, count, p.stat, *hp, p.partial);
+    Y3_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lw_rnorm_kernel, per_tensor, wg, 0, st, p.descs, p.flags, count, (int)p.chunks, p.partial, p.stat,
+                       ratio_dev);
+    Y3_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lw_apply_kernel, per_chunk, wg, 0, st, p.descs, p.ema, count, p.stat, hp->lr, hp->ema_step);
+    Y3_CHECK_HIP(hipGetLastError());
+    return Y3_OK;
 }
 
 extern "C" int y3_ema_update(y3_ctx* ctx, float* shadow, const float* w, long long n, float ema_step) {

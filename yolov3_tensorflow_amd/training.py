@@ -20,11 +20,16 @@ CLIP_NORM = 100.0  # train.py:113-114
 
 class Optimizer(object):
     """Hyper-parameters + slot variables of one of the four update rules the reference can select
-    (utils/misc_utils.py:151-161; TF1 definitions)."""
+    (utils/misc_utils.py:151-161; TF1 definitions), or of one of the layer-wise rules for large global
+    batches (include/yolo355.h, "Layer-wise update rules"): 'adamw' (decoupled weight decay), 'lars' (momentum with a
+    per-tensor trust ratio; `trust` is its coefficient) and 'lamb' (Adam with one).  For those three the model's
+    weight_decay is the rule's lambda, not an L2 term in the gradient."""
 
-    KINDS = ('sgd', 'momentum', 'adam', 'rmsprop')
+    KINDS = ('sgd', 'momentum', 'adam', 'rmsprop', 'adamw', 'lars', 'lamb')      # in ABI order
+    LAYERWISE = KINDS[4:]                                                       # y3_layerwise_update_multi's
+    _EPSILON = dict(adam=1e-8, adamw=1e-8, lamb=1e-6)
 
-    def __init__(self, kind, learning_rate, momentum=0.9, decay=0.9, beta1=0.9, beta2=0.999, epsilon=None):
+    def __init__(self, kind, learning_rate, momentum=0.9, decay=0.9, beta1=0.9, beta2=0.999, epsilon=None, trust=0.001):
         if kind not in self.KINDS:
             raise ValueError('Unsupported optimizer type!')
         self.kind = kind
@@ -32,7 +37,8 @@ class Optimizer(object):
         self.momentum = momentum
         self.decay = decay
         self.beta1, self.beta2 = beta1, beta2
-        self.epsilon = epsilon if epsilon is not None else (1e-8 if kind == 'adam' else 1e-10)
+        self.epsilon = epsilon if epsilon is not None else self._EPSILON.get(kind, 1e-10)
+        self.trust = trust
         self.slots = {}                      # variable op_name -> (slot0, slot1) device tensors
         self.step = 0                        # number of apply_gradients calls (adam's t)
 
@@ -45,9 +51,9 @@ class Optimizer(object):
             z = lambda: torch.zeros_like(var.tensor)
             if self.kind == 'sgd':
                 s = (None, None)
-            elif self.kind == 'momentum':
+            elif self.kind in ('momentum', 'lars'):
                 s = (z(), None)
-            elif self.kind == 'adam':
+            elif self.kind in ('adam', 'adamw', 'lamb'):
                 s = (z(), z())
             else:                            # rmsprop: ms initialised to ones, mom to zeros (TF1)
                 s = (torch.ones_like(var.tensor), z())
@@ -590,9 +596,13 @@ class Trainer(object):
             for i, v in enumerate(self.order):
                 g = self.views[v.op_name]
                 s0, s1 = self.opt._slots_for(v)
-                wd = float(self.model.weight_decay) if v.op_name.endswith('/weights') else 0.0
+                kernel = v.op_name.endswith('/weights')
+                wd = float(self.model.weight_decay) if kernel else 0.0
+                # the layer-wise rules adapt the conv kernels only: gamma, beta and biases take ratio 1 (the old entry
+                # points ignore the word)
                 arr[i] = _lib.ParamDesc(v.tensor.data_ptr(), g.data_ptr(), 0 if s0 is None else s0.data_ptr(),
-                                        0 if s1 is None else s1.data_ptr(), v.tensor.numel(), wd, 0)
+                                        0 if s1 is None else s1.data_ptr(), v.tensor.numel(), wd,
+                                        0 if kernel else _lib.Y3_PARAM_NO_ADAPT)
                 keep.append((v.tensor, s0, s1))
             self._descs, self._descs_keep, self._descs_sig = arr, keep, sig
             if self.ema is not None:        # the HOST array of shadow pointers of y3_clip_update_multi_ema, in self.order
@@ -600,8 +610,13 @@ class Trainer(object):
         return self._descs, self._descs_keep
 
     def apply_gradients(self):
-        """all-reduce (mean over ranks) -> + weight_decay*w on conv kernels -> clip_by_norm -> update."""
+        """all-reduce (mean over ranks) -> + weight_decay*w on conv kernels -> clip_by_norm -> update.
+        adamw / lars / lamb: all-reduce -> clip_by_norm -> the rule, with weight_decay as its lambda on the conv kernels."""
         self._no_update_while_averaged('apply_gradients()')
+        if self.opt.kind in Optimizer.LAYERWISE and os.environ.get('Y3_TRAIN_PER_TENSOR_UPDATE') == '1':
+            raise RuntimeError("Y3_TRAIN_PER_TENSOR_UPDATE=1 runs one y3_clip_update per variable, which knows the kinds "
+                               "%s only: '%s' needs every tensor's norms and goes through y3_layerwise_update_multi"
+                               % (', '.join(Optimizer.KINDS[:4]), self.opt.kind))
         L = _lib.lib()
         dev = self.flat.device
         ctx = fw.context(dev)
@@ -616,6 +631,12 @@ class Trainer(object):
             lr = lr * np.sqrt(1.0 - self.opt.beta2 ** t) / (1.0 - self.opt.beta1 ** t)
         decay = self.opt.beta1 if self.opt.kind == 'adam' else self.opt.decay
         st = _train_state(self.model)
+        if self.opt.kind in Optimizer.LAYERWISE:
+            self._apply_layerwise(L, ctx, st, dev, kind, lr, world, ema_step)
+            for v in self.order:
+                v.touch()
+            self.global_step += 1.0
+            return
         if os.environ.get('Y3_TRAIN_PER_TENSOR_UPDATE') == '1':     # experiment hook: one y3_clip_update per variable
             sc = _scratch(st, 'opt', L.y3_optimizer_scratch_bytes(), dev)
             for v in self.order:
@@ -647,6 +668,35 @@ class Trainer(object):
         for v in self.order:
             v.touch()
         self.global_step += 1.0
+
+    def _apply_layerwise(self, L, ctx, st, dev, kind, lr, world, ema_step):
+        """adamw / lars / lamb: ONE y3_layerwise_update_multi call (three launches, lamb five) for every pair; the step's
+        ratios stay on the device for trust_ratios()."""
+        t, b1, b2 = self.opt.step, float(self.opt.beta1), float(self.opt.beta2)
+        adaptive = self.opt.kind != 'lars'                       # (the host forms the bias corrections in double)
+        hp = _lib.LayerwiseHp(grad_scale=1.0 / world, clip_norm=self.clip_norm, lr=lr,
+                              lr_t=lr * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t) if adaptive else lr,
+                              momentum=self.opt.momentum, beta1=b1, beta2=b2, eps=self.opt.epsilon,
+                              bias1=1.0 / (1.0 - b1 ** t) if adaptive else 1.0,
+                              bias2=1.0 / (1.0 - b2 ** t) if adaptive else 1.0,
+                              trust=self.opt.trust, ema_step=0.0 if ema_step is None else ema_step.value)
+        descs, keep = self._param_descs()
+        if getattr(self, '_ratios', None) is None or self._ratios.numel() != len(self.order):
+            self._ratios = torch.ones(len(self.order), dtype=torch.float32, device=dev)
+        sc = _scratch(st, 'opt_multi', L.y3_layerwise_update_multi_scratch_bytes(descs, len(self.order)), dev)
+        _lib.check(L.y3_layerwise_update_multi(ctx, kind, descs, len(self.order), ctypes.byref(hp),
+                                               None if ema_step is None else self._ema_arr, fw.ptr(self._ratios),
+                                               fw.ptr(sc), ctypes.c_size_t(sc.numel())))
+
+    def trust_ratios(self):
+        """{op_name: the ratio the last apply_gradients used for that variable} (adamw: 1 everywhere; gamma, beta and
+        biases: 1).  Synchronises the device once: meant for logging, not for every step."""
+        if self.opt.kind not in Optimizer.LAYERWISE:
+            raise RuntimeError("the '%s' rule has no trust ratios (adamw, lars and lamb report them)" % self.opt.kind)
+        if getattr(self, '_ratios', None) is None:
+            raise RuntimeError('trust_ratios() needs an apply_gradients() before it')
+        values = self._ratios.cpu().tolist()
+        return {v.op_name: values[i] for i, v in enumerate(self.order)}
 
     def step(self, images, y_true):
         """One training step on a batch; returns [total, xy, wh, conf, class] (device scalars):
