@@ -37,6 +37,7 @@ OPTIONS = (
     ('use_voc_07_metric', _flag, False, 'true: the 11-point VOC 2007 AP'),
     ('batch_size', int, 32, 'images per device batch (the reference evaluates one at a time)'),
     ('compute_dtype', str, 'f32_wino', 'f32_wino (exact fp32, Winograd 3x3 kernels) | f32 | f32_bf16x6 (docs/history_r01_r05.md 4.3-4.4)'),
+    ('spp', _flag, False, 'true: the YOLOv3-SPP architecture (yolov3.spp; a checkpoint or darknet file of that architecture)'),
     ('map_on_device', _flag, False, 'true: match detections and compute AP on the device (eval_utils.DeviceEval, DESIGN.md 4.5)'),
     ('coco_metric', _flag, False, 'true: also report the twelve COCO numbers (AP@[.50:.95], AP50, AP75, AP / AR by size, AR@1/10/100); '
                                   'on the device with --map_on_device true, else eval_utils.coco_eval on the host'),
@@ -75,6 +76,7 @@ def main(argv=None):
 
     yolo_model = y3.yolov3(args.class_num, args.anchors)
     yolo_model.compute_dtype = args.compute_dtype
+    yolo_model.spp = args.spp
     with y3.variable_scope('yolov3'):
         yolo_model.forward(torch.zeros((1, 64, 64, 3)), False)            # create the variables
         if args.restore_path.endswith('.npz'):       # native checkpoint (train.py best_model_*.npz, convert_weight.py)

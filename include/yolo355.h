@@ -316,6 +316,18 @@ int y3_nms(y3_ctx* ctx, int mode, const float* boxes, const float* scores, int n
  * The net decides per layer and input size which kernel runs (y3_net_layer_fused, y3_net_layer_is_streamk) and packs the
  * layers' weights for those kernels itself: the caller hands over the variables, never a packed kernel. */
 int y3_net_create(y3_ctx* ctx, int class_num, y3_net** out);
+/* The same with an architecture; y3_net_create is architecture 0.  Y3_ARCH_YOLOV3_SPP (darknet's yolov3-spp.cfg): the first
+ * yolo_block of the head (f = 512, the 13-grid) becomes
+ *     1x1 512, 3x3 1024, 1x1 512, SPP, 1x1 512 (Cin = 2048), 3x3 1024, 1x1 512 (= route), 3x3 1024
+ * instead of 1x1 512, 3x3 1024, 1x1 512, 3x3 1024, 1x1 512 (= route), 3x3 1024; the rest of the graph is unchanged.  76 convs,
+ * 73 with BN, 371 variables; layer 55 reads spp(output of layer 54) (y3_net_layer_pool; "SPP" below).  Conv outputs stay
+ * the only tensors: the pooled input lives in the workspace for its layer only.  An unknown architecture is Y3_EINVAL. */
+#define Y3_ARCH_YOLOV3 0
+#define Y3_ARCH_YOLOV3_SPP 1
+int y3_net_create_arch(y3_ctx* ctx, int class_num, int arch, y3_net** out);
+int y3_net_arch(const y3_net* net);
+/* 1: layer i reads spp(src), cin = 4 * channels(src); else 0 */
+int y3_net_layer_pool(const y3_net* net, int i);
 int y3_net_destroy(y3_net* net);
 /* 0 = fp32 (default); 1 = bf16 storage: intermediate activations are bf16, the three feature maps stay fp32; 2 / 3 = fp32
  * tensors with the products on the bf16 matrix pipe (y3_conv2d_fwd_split with planes = 3 / 2); 4 = fp32 with the Winograd
@@ -651,6 +663,31 @@ int y3_net_train_set_bn_sync(y3_net* net, y3_bn_sync_fn fn, void* user, double* 
 int y3_net_train_saved(const y3_net* net, int layer, size_t* z_offset, size_t* stats_offset);
 /* the element type of that z: 1 bf16 (net dtype 1, every BN layer but the Cin = 3 stem), 0 fp32 */
 int y3_net_train_saved_type(const y3_net* net, int layer);
+/* test hook: the byte offset inside the last forward's workspace of a pool layer's materialised spp(x) [n,h,w,4c] (bf16 in net
+ * dtype 1, else fp32); SIZE_MAX for every other layer */
+int y3_net_train_saved_pool(const y3_net* net, int layer, size_t* offset);
+
+/* ---- SPP: the spatial pyramid pooling block of YOLOv3-SPP ------------------------------------------------------------
+ * For an NHWC tensor x [n,h,w,c] (fp32 or bf16):
+ *   mp_k(x)[n,y,x',ch] = the maximum of x[n,y+dy,x'+dx,ch] over |dy|,|dx| <= k/2, restricted to positions inside the map
+ *                        (max-pool k x k, stride 1, with padding that never wins);
+ *   spp(x) = concat_channels([mp_13(x), mp_9(x), mp_5(x), x]), shape [n,h,w,4c]  (yolov3-spp.cfg's route -1,-3,-5,-6).
+ * Max is exact: spp is exact in fp32 and in bf16, every output equals one input element bit for bit.  mp_9 = mp_5 o mp_5 and
+ * mp_13 = mp_5 o mp_5 o mp_5 hold exactly; the kernel uses that.  Inputs are finite; NaN behaviour is unspecified.
+ * Backward, with g [n,h,w,4c] in fp32 and x as stored: the window of (q, ch, k) sends its gradient to the FIRST position, in
+ * row-major order of the window (y ascending, then x ascending), whose stored value equals the window's maximum (torch's CPU
+ * max_pool2d rule; ties are not rare in bf16).  With slot(13) = 0, slot(9) = 1, slot(5) = 2:
+ *   dx[p,ch] = g[p,3c+ch] + sum_{k=5,9,13} sum_{q : argmax_k(q,ch) = p} g[q, slot(k)*c+ch]
+ * summed in fp32 in exactly this order: the identity term first, then k = 5, 9, 13, and within a k the q in row-major order.
+ * accumulate != 0: the finished sum is added to what dx held; otherwise it overwrites.  No floating-point atomics: the same
+ * bits on every run.
+ * y3_spp_fwd: out [n,h,w,4c] in x's type, one launch that writes all four slots.  y3_spp_bwd: one launch that recomputes the
+ * argmax from x (no index tensor); x_stride is the channel stride of x in elements, so that x may be the last slot of a
+ * materialised spp(x) (x + 3c, stride 4c); dx [n,h,w,c] fp32.  c % 8 == 0, x_stride % 8 == 0, n,h,w,c > 0, any h and w;
+ * pointers 16-byte aligned; element offsets are 64-bit.  Bad arguments are Y3_EINVAL before any launch. */
+int y3_spp_fwd(y3_ctx* ctx, const void* x, int bf16, int n, int h, int w, int c, void* out);
+int y3_spp_bwd(y3_ctx* ctx, const void* x, int x_stride, int bf16, const float* g, int n, int h, int w, int c,
+               int accumulate, float* dx);
 
 /* ---- next row 8(f)#1: target assignment on the device (utils/data_utils.py:51-115 `process_box`) ------------
  * boxes [n][kmax][5] = (x_min,y_min,x_max,y_max,mix_weight) in resized-image pixels, labels [n][kmax] int32,

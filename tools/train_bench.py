@@ -95,6 +95,7 @@ def main():
                     help="the loss's box term (yolov3.box_loss): the reference's squared errors, or one IoU term")
     ap.add_argument('--ema_decay', type=float, default=0,
                     help='above 0: keep the weight moving average in the update kernel (training.Trainer(ema_decay=...))')
+    ap.add_argument('--spp', action='store_true', help='the YOLOv3-SPP architecture (yolov3.spp): 76 convs and the pooling block')
     ap.add_argument('--sync_bn', action='store_true', help='A/B of synchronised batch norm over a one-rank nccl group')
     ap.add_argument('--rounds', type=int, default=4, help='--sync_bn: rounds per arm')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sync_bn_rate.txt'))
@@ -106,6 +107,7 @@ def main():
     import bench
     model = y3.yolov3(80, bench.ANCHORS, batch_norm_decay=0.99)
     model.compute_dtype = a.precision
+    model.spp = a.spp
     model.box_loss = a.box_loss
     x = torch.rand((a.batch, a.size, a.size, 3), device='cuda')
     yt = synthetic_y_true(a.batch, a.size, 80, bench.ANCHORS, 0, 'cuda')
@@ -126,11 +128,17 @@ def main():
             loss = trainer.step(x, yt)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
-    flops = 3 * bench.conv_flops(model._train['topo_table'] if 'topo_table' in model._train else
-                                 [(l['k'], l['stride'], l['cin'], l['cout'], l['bn']) for l in model._train['topo'].layers],
-                                 a.batch, a.size, a.size).sum()
-    print('train step [%s, box_loss %s%s]: batch %d @%d, %s%s: %.1f ms/step, %.1f images/s, %.1f TFLOP/s (3x forward FLOPs), loss %.3f, peak mem %.1f GB'
-          % (a.precision, a.box_loss, ', ema_decay %g' % a.ema_decay if a.ema_decay else '', a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
+    # 3x the forward's direct-convolution FLOPs: bench.conv_flops for the default architecture, as ever; it knows that head's
+    # divisors only, so the SPP net's come from the net's own tensor table (the same formula)
+    topo = model._train['topo']
+    if a.spp:
+        flops = 3 * sum(2.0 * l['k'] ** 2 * l['cin'] * l['cout'] * (a.size // topo.tensors[l['dst']]['sdiv']) ** 2 * a.batch
+                        for l in topo.layers)
+    else:
+        flops = 3 * bench.conv_flops([(l['k'], l['stride'], l['cin'], l['cout'], l['bn']) for l in topo.layers],
+                                     a.batch, a.size, a.size).sum()
+    print('train step [%s%s, box_loss %s%s]: batch %d @%d, %s%s: %.1f ms/step, %.1f images/s, %.1f TFLOP/s (3x forward FLOPs), loss %.3f, peak mem %.1f GB'
+          % (a.precision, ', spp' if a.spp else '', a.box_loss, ', ema_decay %g' % a.ema_decay if a.ema_decay else '', a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
              flops / dt / 1e12, float(loss[0]), torch.cuda.max_memory_allocated() / 1e9))
 
 

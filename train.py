@@ -37,6 +37,11 @@ def _scopes(x):
     return None if x in (None, '', 'None', 'none') else [s for s in x.split(',') if s]
 
 
+# the default of --restore_exclude (args.py:26): the detection convs, whose shape follows the class count; keyed by --spp
+DETECTION_CONVS = {False: ['yolov3/yolov3_head/Conv_14', 'yolov3/yolov3_head/Conv_6', 'yolov3/yolov3_head/Conv_22'],
+                   True: ['yolov3/yolov3_head/Conv_15', 'yolov3/yolov3_head/Conv_7', 'yolov3/yolov3_head/Conv_23']}
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="YOLO-V3 training procedure (options = the variables of args.py).")
     # paths
@@ -81,8 +86,8 @@ def build_parser():
                    help='default [learning_rate_init, 3e-5, 1e-5]')
     # load and finetune
     p.add_argument('--restore_include', type=_scopes, default=None, help='comma separated scopes, or None')
-    p.add_argument('--restore_exclude', type=_scopes,
-                   default=['yolov3/yolov3_head/Conv_14', 'yolov3/yolov3_head/Conv_6', 'yolov3/yolov3_head/Conv_22'])
+    p.add_argument('--restore_exclude', type=_scopes, default=DETECTION_CONVS[False],
+                   help='default: the three detection convs (with --spp true their names are one higher: Conv_15, Conv_7, Conv_23)')
     p.add_argument('--update_part', type=_scopes, default=['yolov3/yolov3_head'],
                    help="comma separated scopes to train; 'None' = the whole model")
     # tf.data parameters (args.py:33-34)
@@ -140,6 +145,9 @@ def build_parser():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compute_dtype', choices=['f32', 'f32_wino', 'f32_bf16x6', 'f32_bf16x3', 'bf16'], default='f32',
                    help='train-step mode: fp32-accurate modes, or bf16 = mixed precision on the bf16 matrix pipe')
+    p.add_argument('--spp', type=_bool, default=False,
+                   help='true: the YOLOv3-SPP architecture (yolov3.spp): a spatial pyramid pooling block and one more 1x1 conv in '
+                        'the 13-grid head; 371 variables, head names after Conv_2 shifted by one (darknet: yolov3-spp.weights)')
     p.add_argument('--box_loss', choices=['mse', 'giou', 'diou', 'ciou'], default='mse',
                    help="the box term of the loss: mse = the reference's squared-error xy and wh terms; giou / diou / ciou = one "
                         "IoU term in their place (yolov3.box_loss; defined in include/yolo355.h).  Under an IoU kind the "
@@ -252,6 +260,8 @@ def validate(model, y3, args, lines):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.spp and args.restore_exclude == DETECTION_CONVS[False]:      # (the default: the same three layers under their SPP names)
+        args.restore_exclude = DETECTION_CONVS[True]
     os.environ['Y3_FIX_CROP_LABELS'] = '1' if args.fix_crop_labels else '0'      # (read by the feeder's workers too)
     import functools
     import torch
@@ -298,6 +308,7 @@ def main(argv=None):
     yolo_model = y3.yolov3(args.class_num, args.anchors, args.use_label_smooth, args.use_focal_loss,
                            args.batch_norm_decay, args.weight_decay, use_static_shape=False)
     yolo_model.compute_dtype = args.compute_dtype
+    yolo_model.spp = args.spp
     yolo_model.box_loss = args.box_loss
     with y3.variable_scope('yolov3'):
         yolo_model.forward(torch.zeros((1, 64, 64, 3)), False)                 # create the variables

@@ -131,6 +131,12 @@ PROTOTYPES = {
     "y3_nms": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "y3_net_create": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
+    "y3_net_create_arch": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
+    "y3_net_arch": (c_int, [c_void_p]),
+    "y3_net_layer_pool": (c_int, [c_void_p, c_int]),
+    "y3_net_train_saved_pool": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "y3_spp_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "y3_spp_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "y3_net_destroy": (c_int, [c_void_p]),
     "y3_net_num_layers": (c_int, [c_void_p]),
     "y3_net_layer_info": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),

@@ -41,6 +41,7 @@ SOURCES = [
     ("y3_coco.hip", ["-ffp-contract=off"]),
     ("y3_mosaic.hip", ["-ffp-contract=off"]),
     ("y3_affine.hip", ["-ffp-contract=off"]),
+    ("y3_spp.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -400,16 +400,26 @@ extern "C" int y3_conv_schedule(const y3_conv_desc* conv, int tmode_taps, int wi
 // ------------------------------------------------------------------------------------------------
 // (struct Tensor / Layer / y3_net: y3_net.h)
 
-extern "C" int y3_net_create(y3_ctx* ctx, int class_num, y3_net** out) {
+extern "C" int y3_net_create_arch(y3_ctx* ctx, int class_num, int arch, y3_net** out) {
     // ctx may be NULL: the graph, layer table and workspace plan are host-only; forward then needs a ctx.
     Y3_CHECK_ARG(out, "y3_net_create: null out pointer");
     Y3_CHECK_ARG(class_num > 0, "y3_net_create: class_num must be positive");
+    Y3_CHECK_ARG(arch == Y3_ARCH_YOLOV3 || arch == Y3_ARCH_YOLOV3_SPP, "y3_net_create_arch: unknown architecture %d", arch);
     y3_net* net = new y3_net;
     net->ctx = ctx;
     net->class_num = class_num;
+    net->arch = arch;
     net->build();
     *out = net;
     return Y3_OK;
+}
+
+extern "C" int y3_net_create(y3_ctx* ctx, int class_num, y3_net** out) { return y3_net_create_arch(ctx, class_num, Y3_ARCH_YOLOV3, out); }
+
+extern "C" int y3_net_arch(const y3_net* net) { return net ? net->arch : Y3_ARCH_YOLOV3; }
+
+extern "C" int y3_net_layer_pool(const y3_net* net, int i) {
+    return net && i >= 0 && i < (int)net->layers.size() ? net->layers[i].pool : 0;
 }
 
 extern "C" int y3_net_set_dtype(y3_net* net, int dtype) {
@@ -569,7 +579,7 @@ ConvRoute y3_route_dgrad(const y3_net& net, int i, int n, int h, int w) {
     // gradient that writes that dy last - its first consumer in forward order - where that is a stride-1 1x1 conv on the direct
     // kernel: the finished dy is in registers there, and the separate pass over z and dy is skipped.
     const int pj = l.src - 1;
-    bool fuse = Y3_BN_FUSE && r.kind == RouteKind::Direct && l.up < 0 && pj >= 0 && net.layers[pj].bn;
+    bool fuse = Y3_BN_FUSE && r.kind == RouteKind::Direct && l.up < 0 && !l.pool && pj >= 0 && net.layers[pj].bn;      // (a pool layer's data gradient does not write dy of src)
     for (int j = 0; j < i; ++j)        // (no earlier layer reads l.src)
         fuse = fuse && net.layers[j].src != l.src && net.layers[j].up != l.src && net.layers[j].resid != l.src;
     r.bn_blocks = fuse ? y3_conv_dgrad_stats_blocks_impl(&d) : 0;
@@ -797,6 +807,12 @@ extern "C" int y3_net_forward(y3_net* net, const float* x, int n, int h, int w, 
         const float *pw = wk[i ? i - 1 : 0], *lw = wk[i];
         float *src = ptr(l.src), *up = ptr(l.up), *res = ptr(l.resid), *y = ptr(l.dst);
         int rc = Y3_OK;
+        if (l.pool) {      // spp(src) into its buffer of the arena, then the conv as a plain 1x1 over it (timed with the conv)
+            float* pooled = reinterpret_cast<float*>(base + net->pool_offsets[i]);
+            const bool half = net->dtype == NetDtype::BF16 && l.src != 0 && net->tensors[l.src].ext < 0;
+            if (int prc = y3_spp_fwd(net->ctx, src, half, n, d.h, d.w, net->tensors[l.src].c, pooled)) return prc;
+            src = pooled;
+        }
         switch (r.kind) {
         case RouteKind::InNext: break;
         case RouteKind::StemS2F32:

@@ -1,4 +1,4 @@
-// The 75-conv graph object shared by the inference plan (y3_abi.hip: y3_net_forward) and the train step
+// The conv graph object (75 convs; YOLOv3-SPP: 76 and one pooling block) shared by the inference plan (y3_abi.hip: y3_net_forward) and the train step
 // (y3_net_train.hip).  Tensor ids: 0 = network input; 1.. = conv outputs in creation order.
 #pragma once
 #include <vector>
@@ -109,6 +109,7 @@ struct Layer {
     int k, stride, cin, cout, bn, act;
     int src, up, resid, dst;  // tensor ids (-1 = none)
     int c_up;
+    int pool;                 // 1: the layer reads spp(src) (y3_spp_fwd), cin = 4 * channels(src); conv outputs stay the only tensors
     const float *scale, *shift;     // folded BN (detection convs: ones, bias), bound by y3_net_set_params
     const void* w[(int)Packing::Count];     // the kernel in every packing the inference routes may read (y3_net_set_params)
 };
@@ -119,6 +120,7 @@ void y3_train_state_free(y3_train_state* s);
 struct y3_net {
     y3_ctx* ctx;
     int class_num;
+    int arch = Y3_ARCH_YOLOV3;
     y3_train_state* train = nullptr;
     void* wgrad_stream = nullptr;   // y3_net_train_set_wgrad_stream: the weight gradients of backward run on this stream (nullptr: on the context's)
     int box_loss = Y3_BOX_MSE;      // y3_net_train_set_box_loss: the box term of the train step's loss, all three scales
@@ -133,6 +135,7 @@ struct y3_net {
     // cached plan
     int pn = 0, ph = 0, pw = 0;
     std::vector<size_t> offsets;  // byte offset of each tensor in the workspace (SIZE_MAX if external)
+    std::vector<size_t> pool_offsets;   // per layer: its pooled input spp(src), alive for that layer only (SIZE_MAX: none)
     size_t plan_bytes = 0;    // arena + conv scratch + flag regions
     size_t arena_bytes = 0;   // activations only; the conv (stream-K) scratch follows at this offset
     size_t scratch_bytes = 0; // the largest scratch of the routes (shared by all layers: launches on one stream are ordered)
@@ -146,12 +149,13 @@ struct y3_net {
     size_t sets_used = 0;
 
     int add_conv(int src, int cout, int k, int stride = 1, bool bn = true, bool act = true, int resid = -1,
-                 int up = -1) {
+                 int up = -1, bool pool = false) {
         Layer l;
         l.k = k; l.stride = stride; l.cout = cout; l.bn = bn; l.act = act;
         l.src = src; l.up = up; l.resid = resid;
         l.c_up = up >= 0 ? tensors[up].c : 0;
-        l.cin = tensors[src].c + l.c_up;
+        l.pool = pool ? 1 : 0;
+        l.cin = pool ? 4 * tensors[src].c : tensors[src].c + l.c_up;
         l.scale = l.shift = nullptr;
         std::fill(std::begin(l.w), std::end(l.w), nullptr);
         Tensor t;
@@ -170,11 +174,13 @@ struct y3_net {
         const int a = add_conv(x, f, 1);
         return add_conv(a, 2 * f, 3, 1, true, true, /*resid=*/x);
     }
-    // utils/layer_utils.py:71-79 ; `up` >= 0 means the input is concat([upsample(up), x])
-    void yolo_block(int x, int f, int up, int* route, int* net) {
+    // utils/layer_utils.py:71-79 ; `up` >= 0 means the input is concat([upsample(up), x]).  spp: the pooling block and one
+    // more 1x1 conv, which reads it, behind the third conv (darknet's yolov3-spp.cfg)
+    void yolo_block(int x, int f, int up, int* route, int* net, bool spp = false) {
         int t = add_conv(x, f, 1, 1, true, true, -1, up);
         t = add_conv(t, 2 * f, 3);
         t = add_conv(t, f, 1);
+        if (spp) t = add_conv(t, f, 1, 1, true, true, -1, -1, /*pool=*/true);
         t = add_conv(t, 2 * f, 3);
         t = add_conv(t, f, 1);
         *route = t;
@@ -201,7 +207,7 @@ struct y3_net {
         // model.py:53-78 yolov3_head
         const int det = 3 * (5 + class_num);
         int inter1, net1, inter2, net2, inter3, net3;
-        yolo_block(route3, 512, -1, &inter1, &net1);
+        yolo_block(route3, 512, -1, &inter1, &net1, arch == Y3_ARCH_YOLOV3_SPP);
         const int fm1 = add_conv(net1, det, 1, 1, false, false);
         tensors[fm1].ext = 0;
         const int i1 = add_conv(inter1, 256, 1);
@@ -224,6 +230,16 @@ struct y3_net {
     // the channel stride of layer i's output gradient in the train step: Cout, the detection convs' padded to a multiple of 32
     int dz_stride(int i) const { return layers[i].bn ? layers[i].cout : ((3 * (5 + class_num) + 31) / 32) * 32; }
 
+    // the widest channel count a layer reads or writes (the default graph: 1024; SPP: the pooled 2048)
+    int max_channels() const {
+        int m = 0;
+        for (const Layer& l : layers) m = std::max({m, l.cin, l.cout});
+        return m;
+    }
+
+    // spp(src) of a pool layer, in the element type of src
+    size_t pool_bytes(int li, int n, int h, int w) const { return layers[li].pool ? 4 * tensor_bytes(layers[li].src, n, h, w) : 0; }
+
     size_t tensor_bytes(int id, int n, int h, int w) const {
         const Tensor& t = tensors[id];
         const size_t esize = (dtype == NetDtype::BF16 && t.ext < 0 && id != 0) ? 2 : sizeof(float);
@@ -239,13 +255,18 @@ struct y3_net {
         A.reset(nullptr, 0, true);
         std::vector<Buf> live(tensors.size());
         offsets.assign(tensors.size(), SIZE_MAX);
+        pool_offsets.assign(layers.size(), SIZE_MAX);
         for (size_t li = 0; li < layers.size(); ++li) {
             const Layer& l = layers[li];
             for (size_t t = 1; t < tensors.size(); ++t)
                 if (live[t].ok() && tensors[t].last_use < (int)li) A.release(live[t]);
-            if (tensors[l.dst].ext >= 0) continue;
-            live[l.dst] = A.alloc(tensor_bytes(l.dst, n, h, w));
-            offsets[l.dst] = live[l.dst].off;
+            Buf pooled = l.pool ? A.alloc(pool_bytes((int)li, n, h, w)) : Buf();
+            pool_offsets[li] = pooled.off;
+            if (tensors[l.dst].ext < 0) {
+                live[l.dst] = A.alloc(tensor_bytes(l.dst, n, h, w));
+                offsets[l.dst] = live[l.dst].off;
+            }
+            A.release(pooled);
         }
         arena_bytes = Arena::round(A.peak);
         scratch_bytes = 0;

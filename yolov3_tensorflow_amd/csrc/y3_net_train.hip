@@ -19,7 +19,8 @@
 namespace {
 
 constexpr float BN_EPS = 1e-5f;      // model.py:37
-constexpr int MAXC = 1024;           // widest channel count of the graph (ones / zeros vectors, per-channel scratch)
+// (the ones / zeros vectors and the per-channel scratch take the graph's own widest channel count, y3_net::max_channels)
+constexpr int BN_MAXC = 1024;        // widest batch-norm layer of either architecture (the exchange buffer of y3_net_train_set_bn_sync)
 // Rows of y3_bias_grad's partial sums as `bias_sc` is sized; the [det_pad] result sits behind them.  The reduction itself
 // uses at most RED_BLOCKS = 512 rows (y3_train.hip): a kept over-allocation, the workspace size is pinned
 // (tests/golden/conv_routes.json).
@@ -126,8 +127,9 @@ void alloc_scratch(const y3_net* net, y3_train_state& S, int n, int h, int w) {
     Arena& A = S.arena;
     const size_t nl = net->layers.size();
     const int det_pad = det_pad_of(net);
-    S.ones = A.alloc(MAXC * 4);
-    S.zeros = A.alloc(MAXC * 4);
+    const int MAXC = net->max_channels();
+    S.ones = A.alloc((size_t)MAXC * 4);
+    S.zeros = A.alloc((size_t)MAXC * 4);
     size_t sk = 0, wg = 0;
     S.routes.resize(nl);
     for (size_t i = 0; i < nl; ++i) {
@@ -163,8 +165,9 @@ struct Forward : Pass {
     int fill_constants() {           // the ones / zeros vectors (not in the dry run)
         if (A.overflow) { y3_set_error("y3_net_train_forward: workspace too small"); return Y3_EINVAL; }
         void* stage = nullptr;
+        const size_t MAXC = (size_t)net->max_channels();
         if (int rc = y3_ctx_stage_acquire(ctx, MAXC * 4, &stage)) return rc;
-        for (int i = 0; i < MAXC; ++i) static_cast<float*>(stage)[i] = 1.f;
+        for (size_t i = 0; i < MAXC; ++i) static_cast<float*>(stage)[i] = 1.f;
         Y3_CHECK_HIP(hipMemcpyAsync(A.p(S.ones), stage, MAXC * 4, hipMemcpyHostToDevice, ctx->stream));
         if (int rc = y3_ctx_stage_release(ctx)) return rc;
         Y3_CHECK_HIP(hipMemsetAsync(A.p(S.zeros), 0, MAXC * 4, ctx->stream));
@@ -186,6 +189,18 @@ struct Forward : Pass {
             Y3_TRY(y3_concat_channels(ctx, A.p(upt), cu, s.xin, cx, in_rows, A.p(S.xin[s.i])));
         }
         A.release(upt);
+        s.xin = A.p(S.xin[s.i]);
+        return Y3_OK;
+    }
+
+    // a pool layer's input spp(src), materialised in the element type of src: the conv and its weight gradient read it as a
+    // plain [rows, 4c] input, backward reads x back out of its last slot
+    int pool_input(Step& s) {
+        const Layer& l = s.l;
+        if (!l.pool) return Y3_OK;
+        const long long in_rows = (long long)n * s.d.h * s.d.w;
+        S.xin[s.i] = A.alloc((size_t)in_rows * l.cin * (s.half ? 2 : 4));
+        Y3_TRY(y3_spp_fwd(ctx, s.xin, s.half, n, s.d.h, s.d.w, net->tensors[l.src].c, A.p(S.xin[s.i])));
         s.xin = A.p(S.xin[s.i]);
         return Y3_OK;
     }
@@ -270,6 +285,7 @@ struct Forward : Pass {
                    (long long)n * (d.h / l.stride) * (d.w / l.stride)};
             Y3_TRY(ctx_pending_error(ctx));     // (the conv launches below go to the launchers: refuse after a stream-K time-out)
             Y3_STEP(concat_input(s));
+            Y3_STEP(pool_input(s));
             Y3_STEP(conv(s));
             if (l.bn) Y3_STEP(batch_norm(s));
             const int e = net->tensors[l.dst].ext;
@@ -589,6 +605,24 @@ struct Backward : Pass {
         return Y3_OK;
     }
 
+    // a pool layer: the data gradient into a [rows, 4c] buffer; y3_spp_bwd takes the argmax from x, the last slot of the
+    // spp(x) the forward kept (S.xin), and writes the gradient of src - so the BN backward reduction of the layer below is
+    // never fused here (y3_route_dgrad)
+    int pool_gradient(const Step& s, const float* wk, const y3_sk_opts& so) {
+        const Layer& l = s.l;
+        const int c = net->tensors[l.src].c;
+        const bool half = net->dtype == NetDtype::BF16;
+        const long long in_rows = (long long)n * s.d.h * s.d.w;
+        Buf dpool = A.alloc((size_t)in_rows * l.cin * 4);
+        Y3_STEP(launch_dgrad(s, wk, so, 0, A.p(dpool)));
+        int acc;
+        const Buf g = grads.contribute(l.src, tbytes(l.src), &acc);
+        const char* x = at(reinterpret_cast<const char*>(A.p(S.xin[s.i])), (long long)3 * c * (half ? 2 : 4));
+        Y3_TRY(y3_spp_bwd(ctx, x, l.cin, half, A.p(dpool), n, s.d.h, s.d.w, c, acc, A.p(g)));
+        A.release(dpool);
+        return Y3_OK;
+    }
+
     // the gradient of the layer's input, where a layer below trains: into the gradients of src (and, a concat input, of up)
     int data_gradient(Step& s) {
         const Layer& l = s.l;
@@ -615,6 +649,8 @@ struct Backward : Pass {
                 Y3_TRY(y3_slice_accumulate(ctx, A.p(dcat), cin, cu, in_rows, cin - cu, acc, A.p(g)));
             }
             A.release(dcat);
+        } else if (l.pool) {         // the gradient of spp(src), then the pool's backward into the gradient of src
+            Y3_STEP(pool_gradient(s, A.p(wk), so));
         } else {
             const Buf g = grads.contribute(src, tbytes(src), &acc);
             // src is the output of layer src - 1: fuse its BN backward reduction where this is the last contribution
@@ -742,8 +778,8 @@ extern "C" int y3_net_train_set_box_loss(y3_net* net, int box_loss) {
 extern "C" int y3_net_train_set_bn_sync(y3_net* net, y3_bn_sync_fn fn, void* user, double* exchange_dev, size_t exchange_bytes) {
     Y3_CHECK_ARG(net, "y3_net_train_set_bn_sync: null net");
     if (fn)
-        Y3_CHECK_ARG(exchange_dev && exchange_bytes >= (size_t)(2 * MAXC + 1) * sizeof(double),
-                     "y3_net_train_set_bn_sync: the exchange buffer must hold %d doubles", 2 * MAXC + 1);
+        Y3_CHECK_ARG(exchange_dev && exchange_bytes >= (size_t)(2 * BN_MAXC + 1) * sizeof(double),
+                     "y3_net_train_set_bn_sync: the exchange buffer must hold %d doubles", 2 * BN_MAXC + 1);
     net->bn_sync_fn = fn;
     net->bn_sync_user = fn ? user : nullptr;
     net->bn_sync_buf = fn ? exchange_dev : nullptr;
@@ -828,6 +864,15 @@ extern "C" int y3_net_train_saved(const y3_net* net, int layer, size_t* z_offset
     const y3_train_state& S = *net->train;
     if (z_offset) *z_offset = S.z[layer].off;
     if (stats_offset) *stats_offset = S.stats[layer].off;
+    return Y3_OK;
+}
+
+// offset (bytes into the workspace of the last forward) of a pool layer's materialised spp(x), in the element type of x (bf16 in
+// net dtype 1); SIZE_MAX for every other layer (test hook of tests/test_spp_gpu.py)
+extern "C" int y3_net_train_saved_pool(const y3_net* net, int layer, size_t* offset) {
+    Y3_CHECK_ARG(net && net->train && net->train->have_fwd && layer >= 0 && layer < (int)net->layers.size() && offset,
+                 "y3_net_train_saved_pool: no forward state for layer %d", layer);
+    *offset = net->layers[layer].pool ? net->train->xin[layer].off : SIZE_MAX;
     return Y3_OK;
 }
 

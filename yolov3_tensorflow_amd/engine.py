@@ -208,6 +208,34 @@ def concat_channels(a, b):
     return y
 
 
+def spp_fwd(x):
+    """spp(x) = concat([mp_13(x), mp_9(x), mp_5(x), x]) of an NHWC fp32 or bf16 device tensor (y3_spp_fwd; c % 8 == 0)."""
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("spp_fwd: x must be a contiguous [N, H, W, C] fp32 or bf16 tensor")
+    n, h, w, c = x.shape
+    y = torch.empty((n, h, w, 4 * c), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().y3_spp_fwd(fw.context(x.device), fw.ptr(x), int(x.dtype == torch.bfloat16), n, h, w, c, fw.ptr(y)))
+    return y
+
+
+def spp_bwd(x, g, accumulate_into=None, x_stride=None):
+    """The gradient of spp's input (y3_spp_bwd): x [N,H,W,C] fp32 or bf16 as the forward read it - or, with x_stride, a view
+    whose rows are x_stride elements apart (the last slot of a materialised spp(x): pooled[..., 3 * C:], x_stride = 4 * C);
+    g [N,H,W,4C] fp32 -> dx [N,H,W,C] fp32, added to accumulate_into when given."""
+    n, h, w, c = x.shape
+    if tuple(g.shape) != (n, h, w, 4 * c) or g.dtype != torch.float32 or not g.is_contiguous():
+        raise ValueError("spp_bwd: g must be a contiguous [N, H, W, 4C] fp32 tensor")
+    if x_stride is None:
+        if not x.is_contiguous():
+            raise ValueError("spp_bwd: a strided x needs x_stride")
+        x_stride = c
+    dx = accumulate_into if accumulate_into is not None else torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().y3_spp_bwd(fw.context(x.device), ctypes.c_void_p(x.data_ptr()), int(x_stride),
+                                     int(x.dtype == torch.bfloat16), fw.ptr(g), n, h, w, c, 1 if accumulate_into is not None else 0,
+                                     fw.ptr(dx)))
+    return dx
+
+
 def add(a, b):
     if a.shape != b.shape:
         raise ValueError("add: shapes differ: %s vs %s" % (tuple(a.shape), tuple(b.shape)))

@@ -30,6 +30,9 @@ BOX_LOSSES = {'mse': 0, 'giou': 1, 'diou': 2, 'ciou': 3}
 _SIDE_STREAMS = {}      # (device index, parts) -> the side streams of yolov3._forward_on_streams, shared by every model
 
 class yolov3(object):
+    # what a new model's `spp` starts as.  A caller that cannot reach the model a script builds (tools/run_spp.py around
+    # test_single_image.py and video_test.py, which have no --spp option) sets it before the script runs.
+    default_spp = False
 
     def __init__(self, class_num, anchors, use_label_smooth=False, use_focal_loss=False,
                  batch_norm_decay=0.999, weight_decay=5e-4, use_static_shape=True):
@@ -52,6 +55,9 @@ class yolov3(object):
         # the box term of the loss, 'mse' | 'giou' | 'diou' | 'ciou' (BOX_LOSSES; defined in include/yolo355.h at
         # y3_loss_layer_box): under an IoU kind loss_layer / compute_loss report the box term as xy_loss and wh_loss is 0
         self.box_loss = 'mse'
+        # True: the YOLOv3-SPP architecture (include/yolo355.h, Y3_ARCH_YOLOV3_SPP): one pooling block and one more 1x1
+        # conv in the 13-grid head, 76 convs, 371 variables, head names after Conv_2 shifted by one.  Set before the first forward.
+        self.spp = bool(type(self).default_spp)
 
     @property
     def box_loss(self):
@@ -101,12 +107,13 @@ class yolov3(object):
             raise ValueError("compute_dtype must be one of %s" % (sorted(NET_DTYPES),))
         ctx = fw.context(device)
         scope = fw.current_scope_name()
-        key = (ctx.value, scope, self.compute_dtype)
+        arch = 1 if self.spp else 0
+        key = (ctx.value, scope, self.compute_dtype, arch)
         ent = self._nets.get(key)
         L = _lib.lib()
         if ent is None:
             h = ctypes.c_void_p()
-            _lib.check(L.y3_net_create(ctx, int(self.class_num), ctypes.byref(h)))
+            _lib.check(L.y3_net_create_arch(ctx, int(self.class_num), arch, ctypes.byref(h)))
             if NET_DTYPES[self.compute_dtype]:
                 _lib.check(L.y3_net_set_dtype(h, NET_DTYPES[self.compute_dtype]))
             table = self._layer_table(h)
@@ -115,7 +122,7 @@ class yolov3(object):
             self._nets[key] = ent
         # the library packs the parameters (y3_net_set_params): one buffer per (device, scope, dtype), repacked when a variable
         # of this net changes, and bound by the nets of the other streams (their forwards wait for this stream)
-        pkey = (str(device), scope, self.compute_dtype)
+        pkey = (str(device), scope, self.compute_dtype, arch)
         p = self._params.get(pkey)
         if p is None or p['checked'] != fw.global_version():
             versions = tuple(v.version for layer in ent['layers'] for v in
@@ -245,7 +252,7 @@ class yolov3(object):
             route_1, route_2, route_3 = darknet53_body(x)
 
         with fw.variable_scope('yolov3_head'):
-            inter1, net = yolo_block(route_3, 512)
+            inter1, net = yolo_block(route_3, 512, spp=bool(self.spp))
             feature_map_1 = _conv_layer(net, det, 1, 1, use_bn=False, activation=False)
 
             inter1 = conv2d(inter1, 256, 1)

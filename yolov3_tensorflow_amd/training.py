@@ -64,11 +64,16 @@ class Optimizer(object):
 # --------------------------------------------------------------------------------------------------------
 # graph topology (queried from the C++ launch plan: one source of truth)
 # --------------------------------------------------------------------------------------------------------
+def _arch(model):
+    """The Y3_ARCH_* code of the model: 1 (YOLOv3-SPP) with model.spp set, else 0."""
+    return 1 if model.spp else 0
+
+
 class _Topology(object):
-    def __init__(self, class_num):
+    def __init__(self, class_num, arch=0):
         L = _lib.lib()
         h = ctypes.c_void_p()
-        _lib.check(L.y3_net_create(None, int(class_num), ctypes.byref(h)))
+        _lib.check(L.y3_net_create_arch(None, int(class_num), int(arch), ctypes.byref(h)))
         self.layers = []
         ci = lambda: ctypes.c_int()
         for i in range(L.y3_net_num_layers(h)):
@@ -97,8 +102,10 @@ def _scratch(state, key, nbytes, device):
 def _train_state(model):
     st = getattr(model, '_train', None)
     if st is None:
-        st = dict(topo=_Topology(model.class_num), net=None)
+        st = dict(topo=_Topology(model.class_num, _arch(model)), net=None, arch=_arch(model))
         model._train = st
+    if st['arch'] != _arch(model):
+        raise ValueError("model.spp must be set before the first training forward (the train net is built for it)")
     return st
 
 
@@ -114,7 +121,7 @@ def _train_net(model, ctx, dev=None):
     L = _lib.lib()
     if st['net'] is None or st.get('net_ctx') != ctx.value:
         h = ctypes.c_void_p()
-        _lib.check(L.y3_net_create(ctx, int(model.class_num), ctypes.byref(h)))
+        _lib.check(L.y3_net_create_arch(ctx, int(model.class_num), st['arch'], ctypes.byref(h)))
         st['net'], st['net_ctx'] = h, ctx.value
     mode = getattr(model, 'compute_dtype', 'f32')
     if mode not in _TRAIN_DTYPES:

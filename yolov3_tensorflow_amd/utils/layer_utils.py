@@ -64,17 +64,24 @@ def darknet53_body(inputs):
     return stage_out[2], stage_out[3], stage_out[4]
 
 
-def yolo_block(inputs, filters):
+def spp_block(inputs):
+    """The pooling block of YOLOv3-SPP: concat([maxpool13, maxpool9, maxpool5, inputs]) on channels, pools of stride 1 with
+    padding that never wins (include/yolo355.h, "SPP")."""
+    return engine.spp_fwd(fw.as_device_f32(inputs))
+
+
+def yolo_block(inputs, filters, spp=False):
     """Alternating 1x1(filters) / 3x3(2*filters), six convs; the fifth output is the route
-    (reference utils/layer_utils.py:71-79).  Returns (route, net)."""
+    (reference utils/layer_utils.py:71-79).  Returns (route, net).  spp=True: the YOLOv3-SPP form, the pooling block and one
+    more 1x1 conv behind the third conv (seven convs: 1x1, 3x3, 1x1, SPP, 1x1, 3x3, 1x1 = the route, 3x3)."""
     net = inputs
     route = None
-    for i in range(6):
-        if i % 2 == 0:
-            net = conv2d(net, filters, 1)
-        else:
-            net = conv2d(net, filters * 2, 3)
-        if i == 4:
+    kernels = (1, 3, 1, 1, 3, 1, 3) if spp else (1, 3, 1, 3, 1, 3)
+    for i, k in enumerate(kernels):
+        if spp and i == 3:
+            net = spp_block(net)
+        net = conv2d(net, filters if k == 1 else filters * 2, k)
+        if i == len(kernels) - 2:
             route = net
     return route, net
 
