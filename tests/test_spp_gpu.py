@@ -360,9 +360,12 @@ def _pool_argmax(model, n, gh, gw):
     return {k: sc.first_argmax(x.numpy(), k) for k in sc.WINDOWS}
 
 
-def _spp_step(optimizer, update, dtype, wgrad_stream, class_num=80, hw=(256, 256), bs=4, data_seeds=(21, 5), mix_up=None):
+def _spp_step(optimizer, update, dtype, wgrad_stream, class_num=80, hw=(256, 256), bs=4, data_seeds=(21, 5), mix_up=None,
+              box_loss='mse', ema_decay=None):
     """tests/test_train_gpu.py::_step_matches_oracle for the SPP architecture: the fp64 oracle takes the device's LeakyReLU
-    branches and the device's pool argmax.  Returns what the caller gates: (trainer, loss, oracle step, params)."""
+    branches and the device's pool argmax.  Returns what the caller gates: (trainer, loss, oracle step, params).
+    run['raw_grads']: every gradient view as backward left it, before apply_gradients (lamb overwrites the views with its
+    direction, every rule clips in place)."""
     import yolov3_tensorflow_amd as y3
     from yolov3_tensorflow_amd import training
     from yolov3_tensorflow_amd.utils.misc_utils import config_optimizer
@@ -375,13 +378,23 @@ def _spp_step(optimizer, update, dtype, wgrad_stream, class_num=80, hw=(256, 256
     lr = 1e-3
     model = _fresh_spp_model(params, class_num, batch_norm_decay=0.99, weight_decay=5e-4)
     model.compute_dtype = dtype
+    model.box_loss = box_loss
     prefixes = UPDATE_SETS[update]
     upd = None if prefixes is None else [v for v in y3.global_variables(scope='yolov3')
                                          if any(v.op_name.startswith(p) for p in prefixes)]
-    trainer = training.Trainer(model, config_optimizer(optimizer, lr), update_vars=upd, wgrad_stream=wgrad_stream)
+    trainer = training.Trainer(model, config_optimizer(optimizer, lr), update_vars=upd, wgrad_stream=wgrad_stream,
+                               ema_decay=ema_decay)
     trainer.capture = []
+    raw_grads = {}
+    apply_gradients = trainer.apply_gradients
+
+    def keep_then_apply():
+        raw_grads.update({k: v.clone() for k, v in trainer.views.items()})
+        apply_gradients()
+    trainer.apply_gradients = keep_then_apply
     with y3.variable_scope('yolov3'):
         loss = trainer.step(x, yts)
+    del trainer.apply_gradients
     masks = {}
     for rec in trainer.capture:
         if rec['z'] is not None:
@@ -390,7 +403,11 @@ def _spp_step(optimizer, update, dtype, wgrad_stream, class_num=80, hw=(256, 256
     trainer.capture = None
     argmax = _pool_argmax(model, n, h // 32, w // 32)
     return dict(trainer=trainer, model=model, loss=loss, params=params, x=x, yts=yts, masks=masks, argmax=argmax, lr=lr,
-                names=None if upd is None else set(v.op_name for v in upd if v.trainable), class_num=class_num)
+                raw_grads=raw_grads, names=None if upd is None else set(v.op_name for v in upd if v.trainable), class_num=class_num)
+
+
+GRAD_TOL = 2e-4                      # tests/test_train_gpu.py::_step_matches_oracle
+LOSS_RTOL, LOSS_ATOL = 1e-4, 1e-6    # the same
 
 
 def _gate_against_fp64(run, optimizer, what, min_iou_margin=None):
@@ -409,9 +426,8 @@ def _gate_against_fp64(run, optimizer, what, min_iou_margin=None):
         print('smallest |best IoU - 0.5| per scale: %s' % ref['iou_margins'])
         assert min(ref['iou_margins']) >= min_iou_margin, ref['iou_margins']
     for a, b in zip(run['loss'], ref['loss']):
-        assert abs(float(a) - b) <= 1e-4 * abs(b) + 1e-6, ([float(v) for v in run['loss']], ref['loss'])
+        assert abs(float(a) - b) <= LOSS_RTOL * abs(b) + LOSS_ATOL, ([float(v) for v in run['loss']], ref['loss'])
     assert set(trainer.views) == set(ref['grads'])
-    GRAD_TOL = 2e-4      # tests/test_train_gpu.py::_step_matches_oracle
     errs = {name: rel_err(trainer.views[name].cpu().numpy(), g) for name, g in ref['grads'].items()}
     worst = max(errs, key=errs.get)
     print('%s: gradient rel err vs the fp64 SPP oracle on the GPU\'s branches and argmax: worst %.2e (%s), median %.2e over %d tensors'

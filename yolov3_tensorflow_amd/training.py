@@ -679,8 +679,10 @@ class Trainer(object):
     def _apply_layerwise(self, L, ctx, st, dev, kind, lr, world, ema_step):
         """adamw / lars / lamb: ONE y3_layerwise_update_multi call (three launches, lamb five) for every pair; the step's
         ratios stay on the device for trust_ratios()."""
-        t, b1, b2 = self.opt.step, float(self.opt.beta1), float(self.opt.beta2)
-        adaptive = self.opt.kind != 'lars'                       # (the host forms the bias corrections in double)
+        # the bias corrections are formed in double FROM THE FLOAT32 BETAS, the ones the kernel's m and v run on: from
+        # the double 0.999 (float32: 0.99900001287) 1 - beta2^t is 1.3e-5 off at t = 1, and v * bias2 is then not gh^2
+        t, b1, b2 = self.opt.step, float(np.float32(self.opt.beta1)), float(np.float32(self.opt.beta2))
+        adaptive = self.opt.kind != 'lars'
         hp = _lib.LayerwiseHp(grad_scale=1.0 / world, clip_norm=self.clip_norm, lr=lr,
                               lr_t=lr * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t) if adaptive else lr,
                               momentum=self.opt.momentum, beta1=b1, beta2=b2, eps=self.opt.epsilon,
