@@ -560,7 +560,22 @@ int y3_pad_channels(y3_ctx* ctx, const float* src, int c_src, long long rows, in
  * 0 to the term and gets exactly 0 in its four box lanes whatever its logits hold (exp(f2) = inf included): no NaN or inf
  * reaches loss4 or grad from it.  The box term is reported in the xy slot of loss4 / loss5 and the wh slot is exactly 0.0f;
  * the total stays the sum of the slots.  The conf and class terms and the ignore mask (plain IoU) do not depend on the kind:
- * their slots and gradient lanes are the same bits under every kind.  An unknown kind is Y3_EINVAL before any launch. */
+ * their slots and gradient lanes are the same bits under every kind.  An unknown kind is Y3_EINVAL before any launch.
+ *
+ * Conf rule (y3_loss_layer_conf; y3_loss_layer_box is its ignore_thresh = 0.5f, obj_iou_ratio = 0.f call, the reference's
+ * rule).  Two numbers decide what the objectness logit x = f[4] of a record is trained towards:
+ *   ignore = (best < ignore_thresh), best the record's largest plain IoU with the image's true boxes of this scale, computed
+ *            exactly as for the reference's 0.5 (darknet's yolov3.cfg: ignore_thresh = .7);
+ *   z      = the target.  object_mask == 0: z = 0 (selected, not multiplied).  object_mask != 0, with r = obj_iou_ratio:
+ *            z = (1 - r) + r * q,  q = the plain iou above (box_iou) of the record's decoded prediction with its OWN true box
+ *            y_true[0:4]; a q that is NaN, infinite or below 0 counts as 0 (a saturated f[2] gives inf / inf).  q is a
+ *            CONSTANT of the gradient (stop-gradient), under every box_loss kind.
+ *   conf term = sum over records of cmask * bce(z, x) * mixup_weight / N,  cmask = m + (1 - m) * ignore,  m = object_mask,
+ *            bce(z, x) = max(x, 0) - x z + log(1 + exp(-|x|));  d/dx = cmask * (sigmoid(x) - z).  With use_focal_loss the
+ *            factor is (z - sigmoid(x))^2 and its derivative follows.
+ * The box, class and mix-up arithmetic does not depend on either number.  With r == 0 the kernel is the one without the
+ * option (a template parameter), and (0.5f, 0.f) gives the bits of y3_loss_layer_box for every kind.  ignore_thresh or
+ * obj_iou_ratio outside [0, 1], NaN included, is Y3_EINVAL before any launch. */
 #define Y3_BOX_MSE 0
 #define Y3_BOX_GIOU 1
 #define Y3_BOX_DIOU 2
@@ -574,6 +589,10 @@ int y3_loss_layer_box(y3_ctx* ctx, const float* feature_map, const float* y_true
                       int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
                       int use_focal_loss, int box_loss, int accumulate, float* loss4, float* grad, int grad_stride,
                       void* scratch, size_t scratch_bytes);
+int y3_loss_layer_conf(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
+                       int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
+                       int use_focal_loss, int box_loss, float ignore_thresh, float obj_iou_ratio, int accumulate,
+                       float* loss4, float* grad, int grad_stride, void* scratch, size_t scratch_bytes);
 
 /* ---- a14 as ONE call: the train step of train.py:72-115 on the y3_net graph ---------------------------------------
  * The per-op entry points above, sequenced by the library over a caller-owned workspace (whole-graph entries;
@@ -645,6 +664,10 @@ int y3_net_train_set_wgrad_stream(y3_net* net, void* stream);
  * has Y3_BOX_MSE.  Valid for every net dtype (the loss of the bf16 step is fp32 too); launches nothing and leaves the
  * workspace size as it was.  An unknown kind is Y3_EINVAL and the net keeps the kind it had. */
 int y3_net_train_set_box_loss(y3_net* net, int box_loss);
+/* The conf rule of y3_net_train_loss / _step (ignore_thresh and obj_iou_ratio, defined at y3_loss_layer_conf), for all three
+ * scales; a new net has (0.5f, 0.f), the reference's.  Valid for every net dtype; launches nothing and leaves the workspace
+ * size as it was.  A value outside [0, 1] (NaN included) is Y3_EINVAL and the net keeps both values it had. */
+int y3_net_train_set_conf_rule(y3_net* net, float ignore_thresh, float obj_iou_ratio);
 /* Optional synchronised batch norm for a data-parallel caller (off by default; a NULL fn switches it off again).  With a hook
  * set, y3_net_train_forward / _backward / _step run every BN layer's finalize as its two halves (y3_bn_sync_*): the sums half
  * is enqueued on the context's stream into exchange_dev, fn(user, layer, phase, doubles) is called on the host thread (phase 0
@@ -692,10 +715,27 @@ int y3_spp_bwd(y3_ctx* ctx, const void* x, int x_stride, int bf16, const float* 
 /* ---- next row 8(f)#1: target assignment on the device (utils/data_utils.py:51-115 `process_box`) ------------
  * boxes [n][kmax][5] = (x_min,y_min,x_max,y_max,mix_weight) in resized-image pixels, labels [n][kmax] int32,
  * counts [n] int32 (boxes actually present per image), anchors: 9 (w,h) pairs.  Writes the three y_true
- * tensors [n][g][g][3][6+C] (zero, mix weight 1, then the per-box entries in box order). */
+ * tensors [n][g][g][3][6+C] (zero, mix weight 1, then the per-box entries in box order).
+ *
+ * Multi-anchor positives (y3_process_box_multi; y3_process_box is its assign_iou_thresh = 1 call, the option off; darknet's
+ * yolov3.cfg calls the threshold iou_thresh and uses 0.213).  Per image, boxes are taken in order.  For box i, with
+ * (bw, bh) = (x_max - x_min, y_max - y_min) and centre (cx, cy), the nine shape IoUs are computed in float32, in numpy's
+ * operation order:
+ *   w_k = min(bw/2, aw_k/2) - max(-bw/2, -aw_k/2),  h_k likewise,  iou_k = (w_k h_k) / (bw bh + aw_k ah_k - w_k h_k + 1e-10)
+ * and best = the first maximum.  Then for anchor k = 0..8 ASCENDING: if k == best, or iou_k > assign_iou_thresh (a float32
+ * compare), the record (scale of k: stride 8, 16, 32 for k / 3 = 0, 1, 2;  cell (floor(cx / stride), floor(cy / stride));
+ * anchor slot k % 3) is written as the single record is today: the four box fields (cx, cy, bw, bh), mask 1 and the mix
+ * weight are written, the class one-hot bit is set and never cleared, a centre outside that scale's grid skips that write,
+ * and a later write overwrites an earlier one, whichever box or anchor made it.  That order is the definition: one thread
+ * walks an image, no atomics, the same bytes on every run.  assign_iou_thresh >= 1 writes the best anchor only (a shape IoU
+ * never exceeds 1): y3_process_box's output bit for bit.  A threshold <= 0 or NaN is Y3_EINVAL before any launch.
+ * The executable form of this rule is utils.data_utils.process_box_host (numpy float32). */
 int y3_process_box(y3_ctx* ctx, const float* boxes, const int32_t* labels, const int32_t* counts, int n, int kmax,
                    int class_num, int img_w, int img_h, const float* anchors_host18, float* y_true_13,
                    float* y_true_26, float* y_true_52);
+int y3_process_box_multi(y3_ctx* ctx, const float* boxes, const int32_t* labels, const int32_t* counts, int n, int kmax,
+                         int class_num, int img_w, int img_h, const float* anchors_host18, float assign_iou_thresh,
+                         float* y_true_13, float* y_true_26, float* y_true_52);
 
 /* ---- row 8(f)#1, the feeder's pixel work on the device (utils/data_utils.py:118-172 parse_data after its draws:
  * mix_up blend, random_color_distort, the crop window of the expanded canvas, cv2.resize with the drawn interpolation,

@@ -82,7 +82,7 @@ def sync_bn_ab(a, model, upd, x, yt):
         f.write('\n'.join(lines) + '\n')
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--size', type=int, default=416)
@@ -93,13 +93,21 @@ def main():
                     help='the train mode (training._TRAIN_DTYPES): bf16 = mixed precision on the bf16 matrix pipe')
     ap.add_argument('--box_loss', default='mse', choices=['mse', 'giou', 'diou', 'ciou'],
                     help="the loss's box term (yolov3.box_loss): the reference's squared errors, or one IoU term")
+    ap.add_argument('--ignore_thresh', type=float, default=0.5,
+                    help="the loss's ignore threshold (yolov3.ignore_thresh; the reference: 0.5, darknet: 0.7)")
+    ap.add_argument('--obj_iou_ratio', type=float, default=0.0,
+                    help='r of the objectness target (1 - r) + r * IoU of a positive (yolov3.obj_iou_ratio; 0: target 1)')
     ap.add_argument('--ema_decay', type=float, default=0,
                     help='above 0: keep the weight moving average in the update kernel (training.Trainer(ema_decay=...))')
     ap.add_argument('--spp', action='store_true', help='the YOLOv3-SPP architecture (yolov3.spp): 76 convs and the pooling block')
     ap.add_argument('--sync_bn', action='store_true', help='A/B of synchronised batch norm over a one-rank nccl group')
     ap.add_argument('--rounds', type=int, default=4, help='--sync_bn: rounds per arm')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sync_bn_rate.txt'))
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     import torch
     import yolov3_tensorflow_amd as y3
     from yolov3_tensorflow_amd import training
@@ -109,7 +117,8 @@ def main():
     model.compute_dtype = a.precision
     model.spp = a.spp
     model.box_loss = a.box_loss
-    x = torch.rand((a.batch, a.size, a.size, 3), device='cuda')
+    model.ignore_thresh, model.obj_iou_ratio = a.ignore_thresh, a.obj_iou_ratio
+    x =torch.rand((a.batch, a.size, a.size, 3), device='cuda')
     yt = synthetic_y_true(a.batch, a.size, 80, bench.ANCHORS, 0, 'cuda')
     with y3.variable_scope('yolov3'):
         model.forward(torch.zeros((1, 64, 64, 3), device='cuda'))
@@ -138,7 +147,10 @@ def main():
         flops = 3 * bench.conv_flops([(l['k'], l['stride'], l['cin'], l['cout'], l['bn']) for l in topo.layers],
                                      a.batch, a.size, a.size).sum()
     print('train step [%s%s, box_loss %s%s]: batch %d @%d, %s%s: %.1f ms/step, %.1f images/s, %.1f TFLOP/s (3x forward FLOPs), loss %.3f, peak mem %.1f GB'
-          % (a.precision, ', spp' if a.spp else '', a.box_loss, ', ema_decay %g' % a.ema_decay if a.ema_decay else '', a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
+          % (a.precision, ', spp' if a.spp else '', a.box_loss,
+             (', ignore_thresh %g, obj_iou_ratio %g' % (a.ignore_thresh, a.obj_iou_ratio)
+              if (a.ignore_thresh, a.obj_iou_ratio) != (0.5, 0.0) else '') +
+             (', ema_decay %g' % a.ema_decay if a.ema_decay else ''), a.batch, a.size, a.optimizer, ' head-only' if a.head_only else '', dt * 1e3, a.batch / dt,
              flops / dt / 1e12, float(loss[0]), torch.cuda.max_memory_allocated() / 1e9))
 
 

@@ -152,6 +152,18 @@ def build_parser():
                    help="the box term of the loss: mse = the reference's squared-error xy and wh terms; giou / diou / ciou = one "
                         "IoU term in their place (yolov3.box_loss; defined in include/yolo355.h).  Under an IoU kind the "
                         "progress line's `xy` field holds the IoU box term and its `wh` field is 0.00")
+    p.add_argument('--ignore_thresh', type=float, default=0.5,
+                   help="the loss's ignore mask: a prediction without an object whose best IoU with a true box is not below "
+                        "this is left out of the conf term (yolov3.ignore_thresh, in [0, 1]; the reference: 0.5, darknet's "
+                        "yolov3.cfg: 0.7)")
+    p.add_argument('--obj_iou_ratio', type=float, default=0.0,
+                   help="r in [0, 1]: the objectness of a positive is trained towards (1 - r) + r * IoU(prediction, its true "
+                        "box) in place of 1 (yolov3.obj_iou_ratio; the IoU-loss recipes use 1 beside --box_loss giou / diou / "
+                        "ciou)")
+    p.add_argument('--assign_iou_thresh', type=float, default=1.0,
+                   help="below 1: besides its best anchor, a true box is a positive of every anchor whose shape IoU with it "
+                        "exceeds this (feeder.Feeder(assign_iou_thresh=...); darknet's yolov3.cfg: iou_thresh = 0.213).  The "
+                        "`Last batch` recall / precision still count every object once")
     p.add_argument('--sync_bn', type=_bool, default=False,
                    help='data-parallel runs: synchronised batch norm - every BN layer normalises with the statistics of the '
                         'global batch and all ranks keep the same moving statistics (training.Trainer(sync_bn=True)).  Cost: '
@@ -268,6 +280,7 @@ def main(argv=None):
     import torch.distributed as dist
     import yolov3_tensorflow_amd as y3
     from yolov3_tensorflow_amd import training, framework as fw
+    from yolov3_tensorflow_amd.utils.data_utils import process_box_batch
     from yolov3_tensorflow_amd.utils.eval_utils import evaluate_on_gpu, evaluate_on_device
     from yolov3_tensorflow_amd.utils.misc_utils import (parse_anchors, read_class_names, AverageMeter,
                                                         config_learning_rate, config_optimizer, load_weights,
@@ -310,6 +323,7 @@ def main(argv=None):
     yolo_model.compute_dtype = args.compute_dtype
     yolo_model.spp = args.spp
     yolo_model.box_loss = args.box_loss
+    yolo_model.ignore_thresh, yolo_model.obj_iou_ratio = args.ignore_thresh, args.obj_iou_ratio
     with y3.variable_scope('yolov3'):
         yolo_model.forward(torch.zeros((1, 64, 64, 3)), False)                 # create the variables
     variables = y3.global_variables(scope='yolov3')
@@ -361,7 +375,7 @@ def main(argv=None):
                     multi_scale=args.multi_scale_train, use_mix_up=args.use_mix_up, letterbox_resize=args.letterbox_resize,
                     num_threads=args.num_threads, prefetch=args.prefetech_buffer, seed=args.seed, rank=rank, world=world,
                     backend=args.feeder_backend, cache_bytes=_cache_bytes(args), mosaic=args.mosaic and args.augment,
-                    affine=affine_ranges(args))
+                    affine=affine_ranges(args), assign_iou_thresh=args.assign_iou_thresh)
     for epoch in range(args.total_epoches):
         meters = [AverageMeter() for _ in range(5)]
         feeder.mosaic = mosaic_in_epoch(args, epoch) and args.augment      # (read by the feeder once per epoch)
@@ -379,6 +393,11 @@ def main(argv=None):
             if gs % args.train_evaluation_step == 0 and gs > 0:
                 with y3.variable_scope('yolov3'):
                     y_pred = yolo_model.predict(yolo_model.forward(images, False))
+                if args.assign_iou_thresh < 1:
+                    # the evaluators gather "objects" from y_true: with extra positives one object would be counted several
+                    # times, so these steps build plain targets from the boxes the batch carries
+                    y_true = process_box_batch(batch.boxes, batch.labels, batch.counts, batch.img_size, args.class_num,
+                                               args.anchors)
                 if args.batch_eval_on_device:
                     recall, precision = evaluate_on_device(y_pred, y_true, args.class_num, args.nms_topk, args.score_threshold,
                                                            args.nms_threshold, iou_thresh=args.nms_threshold)

@@ -105,6 +105,7 @@ PROTOTYPES = {
                                   POINTER(TrainOpts), c_void_p, c_void_p, c_size_t, c_void_p, GradReadyFn, c_void_p]),
     "y3_net_train_set_wgrad_stream": (c_int, [c_void_p, c_void_p]),
     "y3_net_train_set_box_loss": (c_int, [c_void_p, c_int]),
+    "y3_net_train_set_conf_rule": (c_int, [c_void_p, c_float, c_float]),
     "y3_net_train_set_bn_sync": (c_int, [c_void_p, BnSyncFn, c_void_p, c_void_p, c_size_t]),
     "y3_net_train_saved": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "y3_net_train_saved_type": (c_int, [c_void_p, c_int]),
@@ -195,8 +196,13 @@ PROTOTYPES = {
                               POINTER(c_float), c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     "y3_loss_layer_box": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                   POINTER(c_float), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    "y3_loss_layer_conf": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   POINTER(c_float), c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_size_t]),
     "y3_process_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                POINTER(c_float), c_void_p, c_void_p, c_void_p]),
+    "y3_process_box_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                     POINTER(c_float), c_float, c_void_p, c_void_p, c_void_p]),
     "y3_feed_run": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                             c_void_p, c_int, c_int]),
     "y3_mosaic_scratch_bytes": (c_size_t, [c_int]),

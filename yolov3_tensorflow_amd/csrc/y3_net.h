@@ -124,6 +124,8 @@ struct y3_net {
     y3_train_state* train = nullptr;
     void* wgrad_stream = nullptr;   // y3_net_train_set_wgrad_stream: the weight gradients of backward run on this stream (nullptr: on the context's)
     int box_loss = Y3_BOX_MSE;      // y3_net_train_set_box_loss: the box term of the train step's loss, all three scales
+    float ignore_thresh = 0.5f;     // y3_net_train_set_conf_rule: the ignore mask's threshold ...
+    float obj_iou_ratio = 0.f;      // ... and r of the objectness target (1 - r) + r * IoU, all three scales
     void* own_stream = nullptr;     // the low-priority stream y3_net_train_set_wgrad_stream(net, Y3_OWN_STREAM) created (destroyed with the net)
     // y3_net_train_set_bn_sync: the host hook between the two halves of every BN finalize, and the caller's exchange buffer
     y3_bn_sync_fn bn_sync_fn = nullptr;

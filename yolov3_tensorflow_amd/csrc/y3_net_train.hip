@@ -332,9 +332,10 @@ int loss_impl(y3_net* net, const float* const y_true[3], const y3_train_opts* o,
         Y3_CHECK_HIP(hipMemsetAsync(A.p(S.fm_grad[i]), 0, (size_t)S.n * gh * gw * det_pad * 4, ctx->stream));   // pad lanes stay 0
         // model.py:352-355: anchors [6:9], [3:6], [0:3] for the 13-, 26-, 52-grid maps
         const float* anc = o->anchors + 2 * 3 * (2 - i);
-        const int rc = y3_loss_layer_box(ctx, A.p(S.tens[S.fm_tensor[i]]), y_true[i], S.n, gh, gw, C, S.h, S.w, anc,
-                                         o->use_label_smooth, o->use_focal_loss, net->box_loss, i > 0, A.p(S.loss4),
-                                         A.p(S.fm_grad[i]), det_pad, A.p(S.loss_sc), S.loss_sc.bytes);
+        const int rc = y3_loss_layer_conf(ctx, A.p(S.tens[S.fm_tensor[i]]), y_true[i], S.n, gh, gw, C, S.h, S.w, anc,
+                                          o->use_label_smooth, o->use_focal_loss, net->box_loss, net->ignore_thresh,
+                                          net->obj_iou_ratio, i > 0, A.p(S.loss4), A.p(S.fm_grad[i]), det_pad,
+                                          A.p(S.loss_sc), S.loss_sc.bytes);
         if (rc != Y3_OK) return rc;
     }
     if (!dry && loss5) {
@@ -772,6 +773,17 @@ extern "C" int y3_net_train_set_box_loss(y3_net* net, int box_loss) {
     Y3_CHECK_ARG(net, "y3_net_train_set_box_loss: null net");
     Y3_CHECK_ARG(box_loss >= Y3_BOX_MSE && box_loss <= Y3_BOX_CIOU, "y3_net_train_set_box_loss: unknown box_loss kind %d", box_loss);
     net->box_loss = box_loss;
+    return Y3_OK;
+}
+
+extern "C" int y3_net_train_set_conf_rule(y3_net* net, float ignore_thresh, float obj_iou_ratio) {
+    Y3_CHECK_ARG(net, "y3_net_train_set_conf_rule: null net");
+    Y3_CHECK_ARG(ignore_thresh >= 0.f && ignore_thresh <= 1.f, "y3_net_train_set_conf_rule: ignore_thresh %g outside [0, 1]",
+                 (double)ignore_thresh);
+    Y3_CHECK_ARG(obj_iou_ratio >= 0.f && obj_iou_ratio <= 1.f, "y3_net_train_set_conf_rule: obj_iou_ratio %g outside [0, 1]",
+                 (double)obj_iou_ratio);
+    net->ignore_thresh = ignore_thresh;
+    net->obj_iou_ratio = obj_iou_ratio;
     return Y3_OK;
 }
 

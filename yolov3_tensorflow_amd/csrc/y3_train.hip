@@ -5,6 +5,7 @@
 // All are HBM-bound streaming/reduction kernels: 16-byte-per-lane accesses along the channel axis,
 // per-workgroup partial sums written to a scratch array and combined by a finalize kernel in a FIXED order
 // (fp64 accumulation) so that every statistic and gradient is run-to-run deterministic (no float atomics).
+#include <cfloat>
 #include <cmath>
 #include <vector>
 #include "y3_bf16.h"
@@ -417,6 +418,8 @@ struct LossArgs {
     float ra_w[3], ra_h[3];       // anchors / ratio
     int label_smooth, focal;
     int grad_stride;              // floats per cell-row of 3 anchors in `grad` (>= 3*(5+C); padded for the dgrad)
+    float ignore_thresh;          // ignore = best IoU < ignore_thresh (the reference: 0.5)
+    float obj_ratio;              // r of the objectness target (1 - r) + r * IoU; read by the OBJQ kernels only
 };
 
 __global__ void __launch_bounds__(256) loss_collect_gt_kernel(const LossArgs a) {
@@ -510,7 +513,9 @@ __device__ __forceinline__ float box_term_(float px, float py, float pw, float p
 // (The form this replaces ran one wave per record with the box / conf arithmetic on lane 0 alone: 0.84 ms for the
 // 52-grid of a bs=64 batch, 530 MB; profiles/r02_train_c4_kernel_stats.csv.)
 // BOX (Y3_BOX_*): 0 keeps the reference's xy / wh terms; an IoU kind replaces them by one box term, summed in the xy slot.
-template <int BOX>
+// OBJQ: the objectness target of an object record is (1 - r) + r * IoU(prediction, its own true box) in place of 1
+// (include/yolo355.h, "conf rule"); false is r == 0 and compiles to the code without the option.
+template <int BOX, bool OBJQ>
 __global__ void __launch_bounds__(256) loss_kernel(const LossArgs a) {
     extern __shared__ float gts[];                         // [V][4] of this image
     __shared__ float red[4][4];
@@ -548,13 +553,13 @@ __global__ void __launch_bounds__(256) loss_kernel(const LossArgs a) {
             const float ex = expf(f2), ey = expf(f3);
             const float px = (sx + (float)gx) * a.ratio_w, py = (sy + (float)gy) * a.ratio_h;
             const float pw = (ex * a.ra_w[anc]) * a.ratio_w, ph = (ey * a.ra_h[anc]) * a.ratio_h;
-            // ignore mask (model.py:220-237): best IoU with this image's GT boxes of THIS scale < 0.5
+            // ignore mask (model.py:220-237): best IoU with this image's GT boxes of THIS scale < ignore_thresh (0.5 there)
             float best = -INFINITY;
             for (int v = 0; v < V; ++v)
                 best = fmaxf(best, iou_(px, py, pw, ph, gts[4 * v], gts[4 * v + 1], gts[4 * v + 2], gts[4 * v + 3]));
             for (int v = V; v < G; ++v)                  // more boxes than the LDS stages (no real annotation): from memory
                 best = fmaxf(best, iou_(px, py, pw, ph, gt_n[4 * v], gt_n[4 * v + 1], gt_n[4 * v + 2], gt_n[4 * v + 3]));
-            const float ignore = best < 0.5f ? 1.f : 0.f;
+            const float ignore = best < a.ignore_thresh ? 1.f : 0.f;
             const float bls = 2.f - (y2 / a.img_w) * (y3 / a.img_h);
             const float wgt = m * bls * mixw;
             if constexpr (BOX == Y3_BOX_MSE) {
@@ -592,15 +597,24 @@ __global__ void __launch_bounds__(256) loss_kernel(const LossArgs a) {
                 g3 = obj ? gw_ * dph * ph : 0.f;
             }
             // conf (model.py:280-292)
+            // z, the target: object_mask, or with OBJQ (1 - r) + r * q for an object record, q its plain IoU with its own
+            // true box, a constant of the gradient; a q that is NaN (inf / inf of a saturated f[2]), inf or < 0 counts as 0.
+            // Selected on m, not multiplied, as the IoU box term is.
+            float z = m;
+            if constexpr (OBJQ) {
+                float q = iou_(px, py, pw, ph, y0, y1, y2, y3);
+                q = (q >= 0.f && q <= FLT_MAX) ? q : 0.f;
+                z = m != 0.f ? (1.f - a.obj_ratio) + a.obj_ratio * q : 0.f;
+            }
             const float pc = sigmoid_(xc);
             const float cmask = m + (1.f - m) * ignore;
-            const float b = bce_(m, xc);
+            const float b = bce_(z, xc);
             float lc = cmask * b;
-            float gc = cmask * (pc - m);
+            float gc = cmask * (pc - z);
             if (a.focal) {
-                const float dm = m - pc;
+                const float dm = z - pc;
                 const float fo = dm * dm;                                   // alpha=1, gamma=2
-                gc = cmask * ((pc - m) * fo + b * (-2.f * dm * pc * (1.f - pc)));
+                gc = cmask * ((pc - z) * fo + b * (-2.f * dm * pc * (1.f - pc)));
                 lc *= fo;
             }
             l_conf += lc * mixw;
@@ -1122,6 +1136,7 @@ struct TargetArgs {
     float* y[3];          // y_true_13 / 26 / 52 : [N][g][g][3][6+C]
     int N, kmax, C, img_w, img_h;
     float anc_w[9], anc_h[9];
+    float thresh;         // extra positives: every anchor whose shape IoU > thresh (+inf: the best anchor only)
 };
 
 __global__ void __launch_bounds__(256) target_fill_kernel(float* __restrict__ y, long long cells, int T) {
@@ -1142,22 +1157,30 @@ __global__ void target_assign_kernel(const TargetArgs a) {
         const float bw = b[2] - b[0], bh = b[3] - b[1];
         int best = 0;
         float best_iou = -INFINITY;
+        float ious[9];
+#pragma unroll
         for (int k = 0; k < 9; ++k) {
             const float w = fminf(bw / 2.f, a.anc_w[k] / 2.f) - fmaxf(-bw / 2.f, -a.anc_w[k] / 2.f);
             const float h = fminf(bh / 2.f, a.anc_h[k] / 2.f) - fmaxf(-bh / 2.f, -a.anc_h[k] / 2.f);
             const float iou = (w * h) / (bw * bh + a.anc_w[k] * a.anc_h[k] - w * h + 1e-10f);
+            ious[k] = iou;
             if (iou > best_iou) { best_iou = iou; best = k; }      // np.argmax: first maximum
         }
-        const int group = 2 - best / 3;                              // 0 -> 13-grid
-        const float stride = best / 3 == 0 ? 8.f : (best / 3 == 1 ? 16.f : 32.f);
-        const int gx = (int)floorf(cx / stride), gy = (int)floorf(cy / stride);
-        const int gw = a.img_w / (int)stride, gh = a.img_h / (int)stride;
-        if (gx < 0 || gy < 0 || gx >= gw || gy >= gh) continue;     // numpy would raise IndexError here
-        float* y = a.y[group] + ((((size_t)n * gh + gy) * gw + gx) * 3 + best % 3) * T;
-        y[0] = cx; y[1] = cy; y[2] = bw; y[3] = bh; y[4] = 1.f;
         const int c = a.labels[(size_t)n * a.kmax + i];
-        if (c >= 0 && c < a.C) y[5 + c] = 1.f;
-        y[T - 1] = b[4];
+        // the best anchor, and every anchor above the threshold, in ascending k: a later write overwrites an earlier one
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            if (!(k == best || ious[k] > a.thresh)) continue;
+            const int group = 2 - k / 3;                             // 0 -> 13-grid
+            const float stride = k / 3 == 0 ? 8.f : (k / 3 == 1 ? 16.f : 32.f);
+            const int gx = (int)floorf(cx / stride), gy = (int)floorf(cy / stride);
+            const int gw = a.img_w / (int)stride, gh = a.img_h / (int)stride;
+            if (gx < 0 || gy < 0 || gx >= gw || gy >= gh) continue; // numpy would raise IndexError here
+            float* y = a.y[group] + ((((size_t)n * gh + gy) * gw + gx) * 3 + k % 3) * T;
+            y[0] = cx; y[1] = cy; y[2] = bw; y[3] = bh; y[4] = 1.f;
+            if (c >= 0 && c < a.C) y[5 + c] = 1.f;
+            y[T - 1] = b[4];
+        }
     }
 }
 
@@ -1402,13 +1425,15 @@ extern "C" size_t y3_loss_scratch_bytes(int n, int gh, int gw) {
            blocks * n * 4 * sizeof(float) + 256;
 }
 
-extern "C" int y3_loss_layer_box(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
-                                 int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
-                                 int use_focal_loss, int box_loss, int accumulate, float* loss4, float* grad,
-                                 int grad_stride, void* scratch, size_t scratch_bytes) {
+extern "C" int y3_loss_layer_conf(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
+                                  int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
+                                  int use_focal_loss, int box_loss, float ignore_thresh, float obj_iou_ratio, int accumulate,
+                                  float* loss4, float* grad, int grad_stride, void* scratch, size_t scratch_bytes) {
     Y3_CHECK_ARG(ctx && feature_map && y_true && anchors3_host && loss4 && grad && scratch,
                  "y3_loss_layer: null argument");
     Y3_CHECK_ARG(box_loss >= Y3_BOX_MSE && box_loss <= Y3_BOX_CIOU, "y3_loss_layer: unknown box_loss kind %d", box_loss);
+    Y3_CHECK_ARG(ignore_thresh >= 0.f && ignore_thresh <= 1.f, "y3_loss_layer: ignore_thresh %g outside [0, 1]", (double)ignore_thresh);
+    Y3_CHECK_ARG(obj_iou_ratio >= 0.f && obj_iou_ratio <= 1.f, "y3_loss_layer: obj_iou_ratio %g outside [0, 1]", (double)obj_iou_ratio);
     Y3_CHECK_ARG(n > 0 && gh > 0 && gw > 0 && class_num > 0 && img_h > 0 && img_w > 0, "y3_loss_layer: bad shape");
     Y3_CHECK_ARG(scratch_bytes >= y3_loss_scratch_bytes(n, gh, gw), "y3_loss_layer: scratch too small");
     Y3_CHECK_ARG(grad_stride >= 3 * (5 + class_num), "y3_loss_layer: grad_stride smaller than 3*(5+C)");
@@ -1429,6 +1454,7 @@ extern "C" int y3_loss_layer_box(y3_ctx* ctx, const float* feature_map, const fl
         a.ra_w[k] = a.anc_w[k] / a.ratio_w; a.ra_h[k] = a.anc_h[k] / a.ratio_h;
     }
     a.label_smooth = use_label_smooth; a.focal = use_focal_loss; a.grad_stride = grad_stride;
+    a.ignore_thresh = ignore_thresh; a.obj_ratio = obj_iou_ratio;
     Y3_CHECK_HIP(hipMemsetAsync(a.gt_count, 0, (size_t)n * sizeof(int), ctx->stream));
     hipLaunchKernelGGL(loss_collect_gt_kernel, dim3(blocks, n), dim3(256), 0, ctx->stream, a);
     Y3_CHECK_HIP(hipGetLastError());
@@ -1438,14 +1464,25 @@ extern "C" int y3_loss_layer_box(y3_ctx* ctx, const float* feature_map, const fl
     // order in which the collecting kernel's atomic counter handed out the slots.
     a.vmax = cells < 2048 ? cells : 2048;
     const size_t lds = (size_t)a.vmax * 4 * sizeof(float);
-    auto kernel = box_loss == Y3_BOX_GIOU ? loss_kernel<Y3_BOX_GIOU> : box_loss == Y3_BOX_DIOU ? loss_kernel<Y3_BOX_DIOU> :
-                  box_loss == Y3_BOX_CIOU ? loss_kernel<Y3_BOX_CIOU> : loss_kernel<Y3_BOX_MSE>;
+    auto kernel = box_loss == Y3_BOX_GIOU ? loss_kernel<Y3_BOX_GIOU, false> : box_loss == Y3_BOX_DIOU ? loss_kernel<Y3_BOX_DIOU, false> :
+                  box_loss == Y3_BOX_CIOU ? loss_kernel<Y3_BOX_CIOU, false> : loss_kernel<Y3_BOX_MSE, false>;
+    if (obj_iou_ratio != 0.f)
+        kernel = box_loss == Y3_BOX_GIOU ? loss_kernel<Y3_BOX_GIOU, true> : box_loss == Y3_BOX_DIOU ? loss_kernel<Y3_BOX_DIOU, true> :
+                 box_loss == Y3_BOX_CIOU ? loss_kernel<Y3_BOX_CIOU, true> : loss_kernel<Y3_BOX_MSE, true>;
     hipLaunchKernelGGL(kernel, dim3(blocks, n), dim3(256), lds, ctx->stream, a);
     Y3_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(4), dim3(256), 0, ctx->stream, a.partial, blocks * n,
                        1.f / (float)n, accumulate, loss4);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
+}
+
+extern "C" int y3_loss_layer_box(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
+                                 int class_num, int img_h, int img_w, const float* anchors3_host, int use_label_smooth,
+                                 int use_focal_loss, int box_loss, int accumulate, float* loss4, float* grad,
+                                 int grad_stride, void* scratch, size_t scratch_bytes) {
+    return y3_loss_layer_conf(ctx, feature_map, y_true, n, gh, gw, class_num, img_h, img_w, anchors3_host, use_label_smooth,
+                              use_focal_loss, box_loss, 0.5f, 0.f, accumulate, loss4, grad, grad_stride, scratch, scratch_bytes);
 }
 
 extern "C" int y3_loss_layer(y3_ctx* ctx, const float* feature_map, const float* y_true, int n, int gh, int gw,
@@ -1712,11 +1749,12 @@ extern "C" int y3_box_iou(y3_ctx* ctx, const float* pred_boxes, long long num_pr
     return Y3_OK;
 }
 
-extern "C" int y3_process_box(y3_ctx* ctx, const float* boxes, const int32_t* labels, const int32_t* counts, int n,
-                              int kmax, int class_num, int img_w, int img_h, const float* anchors_host18,
-                              float* y_true_13, float* y_true_26, float* y_true_52) {
+extern "C" int y3_process_box_multi(y3_ctx* ctx, const float* boxes, const int32_t* labels, const int32_t* counts, int n,
+                                    int kmax, int class_num, int img_w, int img_h, const float* anchors_host18,
+                                    float assign_iou_thresh, float* y_true_13, float* y_true_26, float* y_true_52) {
     Y3_CHECK_ARG(ctx && boxes && labels && counts && anchors_host18 && y_true_13 && y_true_26 && y_true_52,
                  "y3_process_box: null argument");
+    Y3_CHECK_ARG(assign_iou_thresh > 0.f, "y3_process_box: assign_iou_thresh %g is not positive", (double)assign_iou_thresh);
     Y3_CHECK_ARG(n > 0 && kmax > 0 && class_num > 0, "y3_process_box: non-positive dimension");
     Y3_CHECK_ARG(img_w > 0 && img_h > 0 && img_w % 32 == 0 && img_h % 32 == 0,
                  "y3_process_box: image size must be a positive multiple of 32");
@@ -1725,6 +1763,7 @@ extern "C" int y3_process_box(y3_ctx* ctx, const float* boxes, const int32_t* la
     a.y[0] = y_true_13; a.y[1] = y_true_26; a.y[2] = y_true_52;
     a.N = n; a.kmax = kmax; a.C = class_num; a.img_w = img_w; a.img_h = img_h;
     for (int k = 0; k < 9; ++k) { a.anc_w[k] = anchors_host18[2 * k]; a.anc_h[k] = anchors_host18[2 * k + 1]; }
+    a.thresh = assign_iou_thresh >= 1.f ? INFINITY : assign_iou_thresh;      // >= 1: the option is off
     const int T = 6 + class_num;
     const int strides[3] = {32, 16, 8};
     for (int s = 0; s < 3; ++s) {
@@ -1735,6 +1774,13 @@ extern "C" int y3_process_box(y3_ctx* ctx, const float* boxes, const int32_t* la
     hipLaunchKernelGGL(target_assign_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, a);
     Y3_CHECK_HIP(hipGetLastError());
     return Y3_OK;
+}
+
+extern "C" int y3_process_box(y3_ctx* ctx, const float* boxes, const int32_t* labels, const int32_t* counts, int n,
+                              int kmax, int class_num, int img_w, int img_h, const float* anchors_host18,
+                              float* y_true_13, float* y_true_26, float* y_true_52) {
+    return y3_process_box_multi(ctx, boxes, labels, counts, n, kmax, class_num, img_w, img_h, anchors_host18, 1.f, y_true_13,
+                                y_true_26, y_true_52);
 }
 
 // ---- the bf16 train step's passes (y3_internal.h) ---------------------------------------------------------------------

@@ -321,8 +321,11 @@ class Feeder(object):
                  letterbox_resize=True, num_threads=10, prefetch=5, shuffle=None, seed=0, rank=0, world=1, interval=10,
                  device=None, drop_remainder=False, backend=None, pixels=None, cache_bytes=0, mosaic=False,
                  mosaic_min_side=2.0, mosaic_min_visible=0.25, affine=None, affine_min_side=2.0, affine_min_area=0.1,
-                 affine_max_aspect=20.0):
-        self.lines = [l for l in lines if (l.strip() if isinstance(l, str) else l)]
+                 affine_max_aspect=20.0, assign_iou_thresh=1.0):
+        from .utils.data_utils import _check_assign_iou_thresh
+        # below 1: every anchor whose shape IoU with a box exceeds it is a positive too (utils.data_utils.process_box_host)
+        self.assign_iou_thresh = _check_assign_iou_thresh(assign_iou_thresh)
+        self.lines =[l for l in lines if (l.strip() if isinstance(l, str) else l)]
         self.batch_size, self.class_num = int(batch_size), int(class_num)
         self.img_size, self.anchors = list(img_size), np.asarray(anchors, np.float32).reshape(9, 2)
         self.mode = mode
@@ -577,7 +580,7 @@ class Feeder(object):
                 out = Batch()
                 out.image_ids, out.images, out.img_size = ids, images, size
                 out.boxes, out.labels, out.counts = bx, lb, ct
-                out.y_true = process_box_batch(bx, lb, ct, size, self.class_num, self.anchors)
+                out.y_true = process_box_batch(bx, lb, ct, size, self.class_num, self.anchors, self.assign_iou_thresh)
                 self.batches_served += 1
                 yield out
         finally:

@@ -55,6 +55,12 @@ class yolov3(object):
         # the box term of the loss, 'mse' | 'giou' | 'diou' | 'ciou' (BOX_LOSSES; defined in include/yolo355.h at
         # y3_loss_layer_box): under an IoU kind loss_layer / compute_loss report the box term as xy_loss and wh_loss is 0
         self.box_loss = 'mse'
+        # the conf rule of the loss (include/yolo355.h at y3_loss_layer_conf), both in [0, 1]: a record without an object
+        # whose best IoU with a true box is not below ignore_thresh is left out of the conf term (the reference: 0.5,
+        # darknet's yolov3.cfg: 0.7); the objectness target of an object record is (1 - r) + r * IoU(prediction, its box),
+        # r = obj_iou_ratio (0: the reference's target 1)
+        self.ignore_thresh = 0.5
+        self.obj_iou_ratio = 0.0
         # True: the YOLOv3-SPP architecture (include/yolo355.h, Y3_ARCH_YOLOV3_SPP): one pooling block and one more 1x1
         # conv in the 13-grid head, 76 convs, 371 variables, head names after Conv_2 shifted by one.  Set before the first forward.
         self.spp = bool(type(self).default_spp)
@@ -68,6 +74,29 @@ class yolov3(object):
         if name not in BOX_LOSSES:
             raise ValueError("box_loss must be one of %s (got %r)" % (sorted(BOX_LOSSES), name))
         self._box_loss = name
+
+    @staticmethod
+    def _unit_interval(what, v):
+        v = float(v)
+        if not 0.0 <= v <= 1.0:            # (NaN fails both compares)
+            raise ValueError("%s must lie in [0, 1] (got %r)" % (what, v))
+        return v
+
+    @property
+    def ignore_thresh(self):
+        return self._ignore_thresh
+
+    @ignore_thresh.setter
+    def ignore_thresh(self, v):
+        self._ignore_thresh = self._unit_interval('ignore_thresh', v)
+
+    @property
+    def obj_iou_ratio(self):
+        return self._obj_iou_ratio
+
+    @obj_iou_ratio.setter
+    def obj_iou_ratio(self, v):
+        self._obj_iou_ratio = self._unit_interval('obj_iou_ratio', v)
 
     # ------------------------------------------------------------------------------------------
     # variables

@@ -141,6 +141,7 @@ def _train_net(model, ctx, dev=None):
         st['wgrad_key'] = key
         st['ws_shape'] = None            # (the allocation sequence of backward changes with it)
     _set_box_loss(model, st)
+    _set_conf_rule(model, st)
     # synchronised batch norm (include/yolo355.h: y3_net_train_set_bn_sync): the distributed.BnSync a Trainer(sync_bn=True)
     # left on the model, installed while it is active
     sync = getattr(model, 'bn_sync', None)
@@ -176,6 +177,20 @@ def _set_box_loss(model, st):
     if st.get('box_loss_key') != key:
         _lib.check(_lib.lib().y3_net_train_set_box_loss(st['net'], key[0]))
         st['box_loss_key'] = key
+
+
+def _conf_rule(model):
+    """(ignore_thresh, obj_iou_ratio) of the model ((0.5, 0) for a model object from before the attributes)."""
+    return float(getattr(model, 'ignore_thresh', 0.5)), float(getattr(model, 'obj_iou_ratio', 0.0))
+
+
+def _set_conf_rule(model, st):
+    """model.ignore_thresh / obj_iou_ratio on the train net (include/yolo355.h: y3_net_train_set_conf_rule), whenever either
+    has changed."""
+    key = _conf_rule(model) + (st['net'].value,)
+    if st.get('conf_rule_key') != key:
+        _lib.check(_lib.lib().y3_net_train_set_conf_rule(st['net'], key[0], key[1]))
+        st['conf_rule_key'] = key
 
 
 def _checked(model, rc):
@@ -298,12 +313,13 @@ def _loss_one_scale(model, fm, y_true, anchors, loss4, accumulate, grad):
     st = _train_state(model)
     sc = _scratch(st, 'loss', L.y3_loss_scratch_bytes(n, gh, gw), fm.device)
     anc = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 2))
-    _lib.check(L.y3_loss_layer_box(fw.context(fm.device), fw.ptr(fm), fw.ptr(y_true), n, gh, gw, C,
-                                   int(model.img_size[0]), int(model.img_size[1]),
-                                   anc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                   1 if model.use_label_smooth else 0, 1 if model.use_focal_loss else 0, _box_kind(model),
-                                   1 if accumulate else 0, fw.ptr(loss4), fw.ptr(grad), int(grad.shape[-1]),
-                                   fw.ptr(sc), ctypes.c_size_t(sc.numel())))
+    ignore_thresh, obj_iou_ratio = _conf_rule(model)
+    _lib.check(L.y3_loss_layer_conf(fw.context(fm.device), fw.ptr(fm), fw.ptr(y_true), n, gh, gw, C,
+                                    int(model.img_size[0]), int(model.img_size[1]),
+                                    anc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                    1 if model.use_label_smooth else 0, 1 if model.use_focal_loss else 0, _box_kind(model),
+                                    ignore_thresh, obj_iou_ratio, 1 if accumulate else 0, fw.ptr(loss4), fw.ptr(grad),
+                                    int(grad.shape[-1]), fw.ptr(sc), ctypes.c_size_t(sc.numel())))
 
 
 def loss_layer(model, feature_map_i, y_true, anchors):
@@ -330,7 +346,8 @@ def compute_loss(model, y_pred, y_true):
             if tuple(y.shape) != tuple(f.shape[:3]) + (3, 6 + int(model.class_num)):
                 raise ValueError("y_true shape %s does not match the feature map %s" % (tuple(y.shape), tuple(f.shape)))
         opts, anc = _opts(model)
-        _set_box_loss(model, st)         # (the attribute may have changed since the forward)
+        _set_box_loss(model, st)         # (the attributes may have changed since the forward)
+        _set_conf_rule(model, st)
         loss5 = torch.empty(5, dtype=torch.float32, device=dev)
         _lib.check(L.y3_net_train_loss(st['net'], fw.ptr(yt[0]), fw.ptr(yt[1]), fw.ptr(yt[2]), ctypes.byref(opts),
                                        fw.ptr(loss5)))

@@ -43,7 +43,14 @@ def parse_line(line):
     return line_idx, pic_path, boxes, labels, img_width, img_height
 
 
-def process_box(boxes, labels, img_size, class_num, anchors):
+def _check_assign_iou_thresh(t):
+    t = float(t)
+    if not t > 0.0:
+        raise ValueError("assign_iou_thresh must be positive (>= 1 switches the extra positives off); got %r" % (t,))
+    return t
+
+
+def process_box(boxes, labels, img_size, class_num, anchors, assign_iou_thresh=1.0):
     '''
     Generate the y_true label, i.e. the ground truth feature_maps in 3 different scales
     (reference utils/data_utils.py:51-115), for ONE image, on the device.
@@ -53,17 +60,69 @@ def process_box(boxes, labels, img_size, class_num, anchors):
         img_size: [width, height]
         class_num: int.
         anchors: [9, 2] shape, float32 dtype.
+        assign_iou_thresh: below 1, every anchor whose shape IoU with a box exceeds it is a positive too (process_box_host).
     returns y_true_13, y_true_26, y_true_52 as numpy arrays (like the reference).
     '''
     boxes = np.asarray(boxes, np.float32).reshape(1, -1, 5)
     labels = np.asarray(labels).reshape(1, -1)
-    ys = process_box_batch(boxes, labels, [boxes.shape[1]], img_size, class_num, anchors)
+    ys = process_box_batch(boxes, labels, [boxes.shape[1]], img_size, class_num, anchors, assign_iou_thresh)
     return tuple(y[0].cpu().numpy() for y in ys)
 
 
-def process_box_batch(boxes, labels, counts, img_size, class_num, anchors):
+def process_box_host(boxes, labels, img_size, class_num, anchors, assign_iou_thresh=1.0):
+    """The target assignment rule of include/yolo355.h (y3_process_box_multi) in executable form: plain numpy float32 on the
+    host, one image.  boxes [K,5] (x_min, y_min, x_max, y_max, mix weight), labels [K], img_size [width, height]; returns
+    y_true_13, y_true_26, y_true_52 as numpy arrays [g_h, g_w, 3, 6 + class_num].  Boxes in order; for each, the best anchor
+    (first maximum of the nine shape IoUs) and, with assign_iou_thresh < 1, every anchor whose IoU exceeds it (a float32
+    compare), anchors ascending; a later write overwrites an earlier one, class bits are never cleared, a centre outside a
+    scale's grid skips that write, a label outside [0, class_num) sets no class bit."""
+    f32 = np.float32
+    t = _check_assign_iou_thresh(assign_iou_thresh)
+    thresh = f32(np.inf) if t >= 1.0 else f32(t)
+    anchors = np.asarray(anchors, f32).reshape(9, 2)
+    boxes = np.asarray(boxes, f32).reshape(-1, 5)
+    labels = np.asarray(labels).reshape(-1)
+    W, H, C = int(img_size[0]), int(img_size[1]), int(class_num)
+    ys = [np.zeros((H // s, W // s, 3, 6 + C), f32) for s in (32, 16, 8)]
+    for y in ys:
+        y[..., -1] = 1.
+    two, eps = f32(2), f32(1e-10)
+    for i in range(boxes.shape[0]):
+        x0, y0, x1, y1, mixw = boxes[i]
+        cx, cy = (x0 + x1) / two, (y0 + y1) / two
+        bw, bh = x1 - x0, y1 - y0
+        ious = np.empty(9, f32)
+        for k in range(9):
+            aw, ah = anchors[k]
+            w = np.minimum(bw / two, aw / two) - np.maximum(-bw / two, -aw / two)
+            h = np.minimum(bh / two, ah / two) - np.maximum(-bh / two, -ah / two)
+            with np.errstate(all='ignore'):
+                ious[k] = (w * h) / (bw * bh + aw * ah - w * h + eps)
+        best, best_iou = 0, f32(-np.inf)
+        for k in range(9):
+            if ious[k] > best_iou:
+                best, best_iou = k, ious[k]
+        for k in range(9):
+            if not (k == best or ious[k] > thresh):
+                continue
+            stride = f32((8., 16., 32.)[k // 3])
+            gx, gy = np.floor(cx / stride), np.floor(cy / stride)
+            y = ys[2 - k // 3]
+            if not (0 <= gx < y.shape[1] and 0 <= gy < y.shape[0]):
+                continue
+            rec = y[int(gy), int(gx), k % 3]
+            rec[0], rec[1], rec[2], rec[3], rec[4] = cx, cy, bw, bh, 1.
+            if 0 <= int(labels[i]) < C:
+                rec[5 + int(labels[i])] = 1.
+            rec[-1] = mixw
+    return ys[0], ys[1], ys[2]
+
+
+def process_box_batch(boxes, labels, counts, img_size, class_num, anchors, assign_iou_thresh=1.0):
     """Batched device form: boxes [N,Kmax,5], labels [N,Kmax], counts [N] -> three device tensors
-    [N,g,g,3,6+C] ready for yolov3.compute_loss (no host round trip per image)."""
+    [N,g,g,3,6+C] ready for yolov3.compute_loss (no host round trip per image).  assign_iou_thresh < 1: the extra positives
+    of y3_process_box_multi (include/yolo355.h; process_box_host is the rule on the host)."""
+    thresh = _check_assign_iou_thresh(assign_iou_thresh)
     b = fw.as_device_f32(boxes)
     if b.dim() != 3 or b.shape[2] != 5:
         raise ValueError("boxes must be [N, Kmax, 5]")
@@ -78,9 +137,9 @@ def process_box_batch(boxes, labels, counts, img_size, class_num, anchors):
     C = int(class_num)
     anc = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(9, 2))
     ys = [torch.empty((n, h // s, w // s, 3, 6 + C), dtype=torch.float32, device=dev) for s in (32, 16, 8)]
-    _lib.check(_lib.lib().y3_process_box(fw.context(dev), fw.ptr(b), fw.ptr(lab), fw.ptr(cnt), n, kmax, C, w, h,
-                                         anc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                         fw.ptr(ys[0]), fw.ptr(ys[1]), fw.ptr(ys[2])))
+    _lib.check(_lib.lib().y3_process_box_multi(fw.context(dev), fw.ptr(b), fw.ptr(lab), fw.ptr(cnt), n, kmax, C, w, h,
+                                               anc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), thresh,
+                                               fw.ptr(ys[0]), fw.ptr(ys[1]), fw.ptr(ys[2])))
     return ys
 
 
