@@ -54,6 +54,9 @@ def ref_conv(x, w_hwio, scale, shift, k, stride, act, resid=None):
     (3, 21, 27, 1, 1, 192, 136, True, 0, 0), (2, 38, 38, 1, 1, 512, 256, True, 0, 0), (1, 19, 19, 1, 1, 1024, 512, False, 0, 0),
     (2, 13, 17, 1, 1, 128, 100, False, 0, 0), (2, 13, 17, 1, 1, 128, 255, True, 0, 1), (16, 76, 76, 1, 1, 256, 255, False, 0, 1),
     (4, 38, 38, 1, 1, 768, 256, False, 256, 0),
+    # the /32 and /16 layers of a 32 x 64 input (maps 1x2 and 2x4: a 3x3 conv on a map one pixel high, whose top and bottom
+    # taps read only padding); the per-op twins of tests/test_bf16_plan_gpu.py's (1,32,64) step
+    (1, 1, 2, 3, 1, 512, 1024, False, 0, 0), (2, 1, 2, 1, 1, 1024, 512, False, 0, 0), (1, 2, 4, 1, 1, 768, 256, False, 256, 0),
 ])
 def test_bf16_conv_matches_fp64_on_rounded_operands(n, h, w, k, stride, cin, cout, resid, c_up, out_f32):
     from yolov3_tensorflow_amd import framework as fw, _lib

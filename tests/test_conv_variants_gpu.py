@@ -6,8 +6,8 @@ against the fp64 reference through the same cases as the default path (tests/tes
 epilogue and the data / weight gradients of the train step; and every tile shape of the bf16 kernels forced in turn
 (Y3_BF16X_TILE=A..E for the 3x3 convs; Y3_BF16R=1 sends every 1x1 conv with Cin % 64 == 0 to the ring kernel - the product
 only those with Cin >= 512 - with Y3_BF16R_TILE=a..g forcing its tile; Y3_BF16R=0 none) through the bf16 conv cases of tests/test_bf16_gpu.py
-(the every-Cin ring setting also through the whole bf16 forward: the fused first residual block reads another weight packing
-and must step aside); and each form of the F(4x4,3x3) conv forced on EVERY case (Y3_WINO44_V=1 two kernels, =0 one kernel -
+(the every-Cin ring setting also through the whole bf16 forward, and through the plan-equals-composition walk of
+tests/test_bf16_plan_gpu.py: the fused first residual block reads another weight packing and must step aside); and each form of the F(4x4,3x3) conv forced on EVERY case (Y3_WINO44_V=1 two kernels, =0 one kernel -
 the product takes two where Cout >= 512), the whole fp32 forward included."""
 import os
 import subprocess
@@ -51,6 +51,9 @@ def test_forced_bf16_tiles(env):
     what = [os.path.join(HERE, 'test_bf16_gpu.py') + '::test_bf16_conv_matches_fp64_on_rounded_operands']
     if env == {'Y3_BF16R': '1'}:      # ... and the whole forward: every 1x1 conv of the net on the ring kernel's packing
         what.append(os.path.join(HERE, 'test_bf16_gpu.py') + '::test_bf16_forward_tracks_the_fp32_oracle')
+        # ... held to its op-by-op composition over the size walk: the composer follows the fused flags 1, 2, 0, 0 and packs
+        # every kernel with this build's y3_pack_conv_weights_bf16
+        what.append(os.path.join(HERE, 'test_bf16_plan_gpu.py') + '::test_plan_equals_its_composition_whatever_the_library_routes')
     r = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu'] + what,
                        env=e, cwd=os.path.dirname(HERE), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = r.stdout.decode(errors='replace')
